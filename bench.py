@@ -2,10 +2,16 @@
 """Benchmark of the BESS hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode score|train] [--comm auto|native|c10d]
-                    [--workload c2|c4] [--c4-point S,K] [--c4-graph]
+                    [--workload c2|c4] [--c4-point S,K] [--c4-graph] [--full] [--dump-outputs DIR]
 
 Metric (BASELINE.json): positive+negative triples scored per second, and the
 achieved GB/s of the dominant (gather + score) kernel against the roofline.
+
+A plain run sets up, warms up (W steps), times K steps and prints the line; `ms_per_step` is the wall time of
+the K timed steps over K.  The extra objects below take runs of their own and come with `--full`, all but
+`roofline`, whose HIP events sit in the timed steps.  `--dump-outputs DIR` writes what the last timed
+step returned - loss and scores, and in training a fixed sample of the updated entity rows plus the relation
+table - as DIR/<name>.npy (float32); the inputs are seeded, so two builds can be compared array for array.
 
 Headline workload (BASELINE.json configs[1], "C2"): ogbl-biokg-shaped ComplEx,
 embedding_size 256 (W = Wr = 512, fp32, 2 KiB rows), 93,773 entities per shard,
@@ -18,7 +24,7 @@ loss: K1 gather (fused), K2-K6 scoring, K8 loss.  `--mode train` adds backward
 all-gathered, scores returned by all-to-all: the scheme the reference recommends
 for per-triple negatives, docs/source/bess.rst:75-86), K = 256 / N per shard pair.
 
-Extra objects on the same JSON line:
+Extra objects on the same JSON line (`--full`, but for `roofline`):
   roofline      dominant kernel of the headline leg.  The C2 table is 192 MB and
                 lives in the 256 MiB Infinity Cache: bound = "infinity-cache".
   roofline_hbm  (N = 1) the same launch on an HBM-resident shard (4 M rows, 8.2 GB),
@@ -79,6 +85,8 @@ C4_D = 256
 C4_GRAPH_DEADLINE_S = 180  # wall-clock bound on the recorded-collectives variant at N > 1 (see main)
 XGMI_LINKS, XGMI_LINK_GBS = 7, 153.0  # per GPU: 7 point-to-point links of ~153 GB/s (MI355X_MICROARCH.md)
 EXIT_ABANDONED = 3  # a leg hung and was abandoned: the line says so and the process does NOT report success
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files of all ranks together
+DUMP_SAMPLE_ROWS = 1024  # rows of an updated entity shard written by --dump-outputs (fixed, seeded sample)
 # (S per GPU, K per shard pair): SURVEY 8d's sweep - K in {32, 256, 2048}, S from the notebook's 512 to 65,536
 C4_SWEEP = ((512, 32), (4096, 256), (4096, 2048), (16384, 256), (65536, 256))
 
@@ -122,7 +130,8 @@ def make_group(comm: str, world: int, rank: int, dev: torch.device, distributed:
     return DistributedGroup(), f"c10d/{backend} (native self-check failed)"
 
 
-def build_c2(n_rows: int, n_shard: int, rank: int, dev: torch.device, group, distributed: bool):
+def build_c2(n_rows: int, n_shard: int, rank: int, dev: torch.device, group, distributed: bool,
+             return_scores: bool = False):
     """The headline model through the public constructors: only this rank's shard, on the device."""
     from besskge.bess import EmbeddingMovingBessKGE, ScoreMovingBessKGE
     from besskge.loss import LogSigmoidLoss
@@ -139,7 +148,7 @@ def build_c2(n_rows: int, n_shard: int, rank: int, dev: torch.device, group, dis
     ns = RandomShardedNegativeSampler(k_pair, sharding, 1234, "t", local_sampling=False, flat_negative_format=False)
     loss = LogSigmoidLoss(margin=12.0, negative_adversarial_sampling=True)
     cls = ScoreMovingBessKGE if distributed else EmbeddingMovingBessKGE
-    model = cls(negative_sampler=ns, score_fn=fn, loss_fn=loss)
+    model = cls(negative_sampler=ns, score_fn=fn, loss_fn=loss, return_scores=return_scores)
     for p in (fn.entity_embedding, fn.relation_embedding):
         p.requires_grad_(False)
     model.attach(group, {rank: 0})
@@ -162,6 +171,36 @@ def make_batches_c2(n_shard: int, rank: int, sharding, k_pair: int, pool: int, d
         )
         out.append({k: torch.from_numpy(v.astype(np.int32)).to(dev) for k, v in b.items()})
     return out
+
+
+def host_array(x) -> np.ndarray:
+    """Host copy of a tensor in float32 (float64 stays float64)."""
+    x = x.detach()
+    if x.dtype != torch.float64:
+        x = x.float()
+    return x.cpu().numpy()
+
+
+def table_outputs(score_fn) -> dict:
+    """What a training step leaves in the tables: a fixed, seeded sample of this rank's entity rows (all local
+    shards' rows flattened) and the whole relation table, on the host."""
+    ent = score_fn.entity_embedding.data
+    ent = ent.reshape(-1, ent.shape[-1])
+    rows = np.sort(np.random.default_rng(0).choice(ent.shape[0], size=min(DUMP_SAMPLE_ROWS, ent.shape[0]),
+                                                   replace=False))
+    return dict(entity_embedding_sample=host_array(ent[torch.from_numpy(rows).to(ent.device)]),
+                relation_embedding=host_array(score_fn.relation_embedding.data))
+
+
+def dump_outputs(out_dir: str, arrays: dict, world: int, rank: int) -> None:
+    """`--dump-outputs`: every array as out_dir/<name>.npy (with `_rank<r>` in the name when N > 1)."""
+    arrays = {k: v if isinstance(v, np.ndarray) else host_array(v) for k, v in arrays.items()}
+    total = world * sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes over all ranks, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, (k if world == 1 else f"{k}_rank{rank}") + ".npy"), a)
 
 
 def usable_cores() -> int:
@@ -352,11 +391,18 @@ def c4_leg(world: int, rank: int, dev: torch.device, group, distributed: bool, c
                 torch.cuda.synchronize()
                 reps = max(1, -(-steps // iters))
                 t0 = time.perf_counter()
-                for _ in range(reps):
+                for _ in range(reps - 1):
                     runner(**batch)
+                last = runner(**batch)
                 group.barrier()
                 torch.cuda.synchronize()
                 dt = (time.perf_counter() - t0) / (reps * iters)
+                if state.get("capture"):
+                    # --dump-outputs: what the last call returned (the final step's loss) and the tables it left
+                    outs = {k: host_array(v) for k, v in last.items() if torch.is_tensor(v)}
+                    outs.update(table_outputs(fn))
+                    state.setdefault("outputs", {})[(name, S_, K_)] = outs
+                last = None
                 if distributed:
                     t = torch.tensor([dt], dtype=torch.float64, device=dev)
                     dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -565,12 +611,20 @@ def main() -> None:
                     help="N > 1: also run the c4 sweep with the collectives recorded into a hipGraph.  Opt-in there: "
                          "recorded RCCL send/recv has only been rehearsed on one-rank communicators; it runs last, under "
                          "a deadline, and a hang ends the process with a non-zero code (never a silent success)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="headline leg only (no roofline_hbm / c4 / train_step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: roofline_hbm, train_step, cpu_baseline, the "
+                         "c4 sweep, xgmi (N > 1); without it the line is the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="--full without roofline_hbm / c4 / train_step / xgmi")
     ap.add_argument("--c4-max-s", type=int, default=65536, help="largest micro-batch of the c4 sweep (positives per GPU)")
     ap.add_argument("--entities-per-shard", type=int, default=N_ENTITY_C2,
                     help="rows per shard of the headline leg (default: the ogbl-biokg count)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -604,7 +658,9 @@ def main() -> None:
     group, comm_name = make_group(args.comm, world, rank, dev, distributed, backend)
     if args.workload == "c4":
         return main_c4(args, world, rank, dev, group, distributed, comm_name)
-    model, sharding, k_pair = build_c2(args.entities_per_shard, world, rank, dev, group, distributed)
+    # the timed steps return the scores as well as the loss (no device work: the scores are made either way)
+    model, sharding, k_pair = build_c2(args.entities_per_shard, world, rank, dev, group, distributed,
+                                       return_scores=True)
     batches = make_batches_c2(world, rank, sharding, k_pair, pool=8, dev=dev)
     lr = 1e-3
 
@@ -620,23 +676,27 @@ def main() -> None:
     streams = [main_stream] if args.mode == "train" or args.streams == 1 else \
         [torch.cuda.Stream(device=dev) for _ in range(args.streams)]
 
-    def step(i: int) -> None:
+    def step(i: int):
         b = batches[i % len(batches)]
         with torch.cuda.stream(streams[i % len(streams)]):
             if args.mode == "train":
-                model.train_step_replicas([b], lr)
-            else:
-                with torch.no_grad():
-                    model.forward_replicas([b])
+                return model.train_step_replicas([b], lr)
+            with torch.no_grad():
+                return model.forward_replicas([b])
 
-    def run_steps(first: int, count: int) -> None:
-        """`count` scoring / training steps.  With more than one GPU the forward is software
-        pipelined: the row gathers and all-gathers of micro-batch i + 1 are issued before the
-        scoring of micro-batch i, so that they run under its scoring kernel (on the other stream)."""
+    def run_steps(first: int, count: int):
+        """`count` scoring / training steps; returns what the last one returned (one dict per local replica).
+        With more than one GPU the forward is software pipelined: the row gathers and all-gathers of micro-batch
+        i + 1 are issued before the scoring of micro-batch i, so that they run under its scoring kernel (on the
+        other stream)."""
+        last = first + count - 1
+        if count < 1:
+            return None
         if not distributed or args.mode == "train":
-            for i in range(first, first + count):
+            for i in range(first, last):
                 step(i)
-            return
+            return step(last)
+        out = None
         with torch.no_grad():
             with torch.cuda.stream(streams[first % len(streams)]):
                 ctx = model.forward_begin([batches[first % len(batches)]])
@@ -646,8 +706,12 @@ def main() -> None:
                     with torch.cuda.stream(streams[(i + 1) % len(streams)]):
                         nxt = model.forward_begin([batches[(i + 1) % len(batches)]])
                 with torch.cuda.stream(streams[i % len(streams)]):
-                    model.forward_finish(ctx)
+                    if i == last:
+                        out = model.forward_finish(ctx)
+                    else:
+                        model.forward_finish(ctx)
                 ctx = nxt
+        return out
 
     def fence() -> None:
         if distributed:
@@ -666,7 +730,7 @@ def main() -> None:
     timed = ["bess_neg_score_pertriple_fwd", "bess_neg_score_pertriple_fwd_dq"]
     nat.start_kernel_timing(timed)
     t0 = time.perf_counter()
-    run_steps(0, args.steps)
+    last = run_steps(0, args.steps)
     fence()
     elapsed = time.perf_counter() - t0
     kernel_ms = nat.stop_kernel_timing()
@@ -674,8 +738,16 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        (outs,) = last  # one local replica
+        outs = {k: v for k, v in outs.items() if torch.is_tensor(v)}
+        if args.mode == "train":
+            outs.update(table_outputs(model.score_fn))
+        dump_outputs(args.dump_outputs, outs, world, rank)
+    last = outs = None
+    model.return_scores = False  # the extra legs time the step as they always have: loss only
 
-    extra_legs = not args.no_extra_legs
+    extra_legs = args.full and not args.no_extra_legs
     train_extra = hbm = None
     if not distributed and args.mode == "score" and extra_legs:
         train_extra = train_leg(model, batches, args.steps)
@@ -754,7 +826,7 @@ def main() -> None:
         line["roofline_hbm"] = hbm
     if train_extra is not None:
         line["train_step"] = train_extra
-    if rank == 0 and not distributed and not args.no_cpu_baseline:
+    if rank == 0 and not distributed and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline()
     if extra_legs:
         c4_steps = max(16, min(args.steps, 48))
@@ -818,7 +890,7 @@ def main_c4(args, world: int, rank: int, dev, group, distributed: bool, comm_nam
     S_, K_ = (int(x) for x in args.c4_point.split(","))
     if S_ % world:
         raise SystemExit(f"--c4-point: S = {S_} is not a multiple of n_shard = {world}")
-    state: dict = {"max_s": 1 << 30}
+    state: dict = {"max_s": 1 << 30, "capture": bool(args.dump_outputs)}
     sweep = ((S_, K_),)
     c4_leg(world, rank, dev, group, distributed, comm_name, args.steps, state, variants=("eager", "plan"), sweep=sweep,
            warmup_calls=-(-args.warmup // 8))
@@ -829,6 +901,8 @@ def main_c4(args, world: int, rank: int, dev, group, distributed: bool, comm_nam
     if "ms_per_step" not in point:
         raise SystemExit(f"c4 leg failed: {point}")
     which = min(("eager", "plan", "graph"), key=lambda v: point.get(f"{v}_ms_per_step", 1e30))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, state["outputs"][(which, S_, K_)], world, rank)
     n_neg = point["negatives_per_triple"]
     valu = dict(point["valu"])
     valu.update(kernel="k_l1_fwd_pk + k_neg_shared_bwd (both products), whole step", peak=VALU_PEAK_TLOPS,
@@ -853,12 +927,12 @@ def main_c4(args, world: int, rank: int, dev, group, distributed: bool, comm_nam
         "roofline": valu,
         "c4": c4_summary(state, world, comm_name),
     }
-    if world > 1:
+    if args.full and world > 1:
         try:
             out["xgmi"] = xgmi_leg(group, world, rank, dev)
         except Exception as e:  # noqa: BLE001
             out["xgmi"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-    if rank == 0 and world == 1 and not distributed and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not distributed and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c4(min(S_, 1024), K_)
     finish(out, rank, distributed, group)
 
