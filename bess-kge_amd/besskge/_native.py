@@ -14,6 +14,7 @@ import contextlib
 import ctypes
 import pathlib
 import sys
+import threading
 from typing import Any, List, Optional, Sequence, Tuple
 
 import torch
@@ -227,44 +228,53 @@ ECOMM_BASE = 10000
 
 _lib: Optional[ctypes.CDLL] = None
 
-# Optional per-launch timing of selected entry points with HIP events recorded
-# on the stream the kernel is launched on (bench.py's roofline leg).
+# Optional per-launch timing with HIP events recorded on the stream the call is issued to (bench.py's roofline leg,
+# profiles/): the log holds (entry point, raw stream, start event, end event) in issue order.
 _timing: Optional[list] = None
-_timed_names: Tuple[str, ...] = ()
+_timed_names: frozenset = frozenset()
+
+# Entry points that are timed under the name of the call they are a variant of.
+TIMING_LABELS = {
+    "bess_neg_score_pertriple_fwd_dq_masked": "bess_neg_score_pertriple_fwd_dq",
+    "bess_neg_score_shared_fwd_ws": "bess_neg_score_shared_fwd",
+    "bess_neg_score_shared_fwd_masked": "bess_neg_score_shared_fwd",
+    "bess_neg_score_shared_fwd_pruned": "bess_neg_score_shared_fwd",
+    "bess_neg_score_shared_bwd_ws": "bess_neg_score_shared_bwd",
+    "bess_neg_score_shared_bwd_parts": "bess_neg_score_shared_bwd",
+    "bess_sparse_sgd_lists_axpy": "bess_sparse_sgd_lists",
+    "bess_coalesced_update_axpy": "bess_coalesced_update",
+    "bess_topk_update_flagged": "bess_topk_update",
+}
+
+
+class _Recording(threading.local):
+    plan: Optional["Plan"] = None  # the plan the calling host thread is recording (`record_plan`), if any
+
+
+_recording = _Recording()
 
 
 def start_kernel_timing(names: Sequence[str]) -> None:
-    """Record a HIP event pair around every call of the named entry points."""
+    """Record a HIP event pair around every call whose label is named: an entry point of `TIMING_LABELS` has the
+    label given there, every other its own name."""
     global _timing, _timed_names
-    _timing, _timed_names = [], tuple(names)
+    _timing, _timed_names = [], frozenset(names)
+
+
+def kernel_timing_log() -> list:
+    """[(entry point, raw stream, start event, end event)] of the timed calls so far, in issue order."""
+    return list(_timing or [])
 
 
 def stop_kernel_timing() -> dict:
-    """{entry point: [milliseconds per launch]} since start_kernel_timing()."""
+    """{label: [milliseconds per launch]} since start_kernel_timing()."""
     global _timing
     rec, _timing = _timing or [], None
     torch.cuda.synchronize()
     out: dict = {}
-    for name, a, b in rec:
-        out.setdefault(name, []).append(a.elapsed_time(b))
+    for name, _, a, b in rec:
+        out.setdefault(TIMING_LABELS.get(name, name), []).append(a.elapsed_time(b))
     return out
-
-
-class _Timed:
-    def __init__(self, name: str, dev: torch.device) -> None:
-        self.on = _timing is not None and name in _timed_names
-        self.name, self.dev = name, dev
-
-    def __enter__(self) -> None:
-        if self.on:
-            self.a = torch.cuda.Event(enable_timing=True)
-            self.b = torch.cuda.Event(enable_timing=True)
-            self.a.record(torch.cuda.current_stream(self.dev))
-
-    def __exit__(self, *exc: Any) -> None:
-        if self.on:
-            self.b.record(torch.cuda.current_stream(self.dev))
-            _timing.append((self.name, self.a, self.b))  # type: ignore
 
 
 def library_path() -> pathlib.Path:
@@ -390,6 +400,29 @@ def _on(dev: torch.device) -> Any:
     return torch.cuda.device(dev)
 
 
+def _launch(name: str, dev: torch.device, *args: Any) -> None:
+    """Call entry point `name` with `args` and PyTorch's current stream of `dev`: the one path of every call that puts
+    work on a stream.  The call is bracketed with HIP events while its label is timed, and noted in the calling
+    thread's plan while that thread records one (`record_plan`)."""
+    if dev.index is not None and torch.cuda.current_device() != dev.index:
+        with torch.cuda.device(dev):  # (rare: see _on)
+            return _launch(name, dev, *args)
+    stream = _stream(dev)
+    log = _timing
+    if log is None or TIMING_LABELS.get(name, name) not in _timed_names:
+        rc = getattr(load(), name)(*args, stream)
+    else:
+        s = torch.cuda.current_stream(dev)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(s)
+        rc = getattr(load(), name)(*args, stream)
+        b.record(s)
+        log.append((name, stream, a, b))
+    if rc == 0 and _recording.plan is not None:
+        _recording.plan._add(name, args)
+    _check(rc, name)
+
+
 class RowSource:
     """`rows[i] = base[idx[i]]` (idx None: identity).  `base` is a contiguous
     [*, W] table-dtype tensor: a shard, a receive buffer or plain embeddings."""
@@ -434,9 +467,7 @@ def gather_rows(table: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tens
         _rows(out, "out", W)
         if out.shape[0] != n or out.dtype != table.dtype:
             raise ValueError("gather_rows: `out` does not match idx / table dtype")
-    with _on(dev), _Timed("bess_gather_rows", dev):
-        rc = load().bess_gather_rows(_dtype_code(table), W, table.data_ptr(), ip, n, out.data_ptr(), _stream(dev))
-    _check(rc, "bess_gather_rows")
+    _launch("bess_gather_rows", dev, _dtype_code(table), W, table.data_ptr(), ip, n, out.data_ptr())
     return out
 
 
@@ -462,11 +493,9 @@ def score_triple_fwd(d: ModelDesc, head: RowSource, tail: RowSource, rel_table: 
                      rel_idx: torch.Tensor) -> torch.Tensor:
     dev, n = _triple_operands(d, head, tail, rel_table, rel_idx)
     out = torch.empty((n,), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_score_triple_fwd(
-            ctypes.byref(d), head.base.data_ptr(), _idx(head.idx, "head_idx"), tail.base.data_ptr(),
-            _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n, out.data_ptr(), _stream(dev))
-    _check(rc, "bess_score_triple_fwd")
+    _launch("bess_score_triple_fwd", dev, ctypes.byref(d), head.base.data_ptr(), _idx(head.idx, "head_idx"),
+            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n,
+            out.data_ptr())
     return out
 
 
@@ -482,12 +511,9 @@ def score_triple_bwd(d: ModelDesc, head: RowSource, tail: RowSource, rel_table: 
         raise ValueError("score_triple_bwd: gradient shapes do not match")
     dh = torch.empty((n, d.width), dtype=torch.float32, device=dev)
     dt = torch.empty((n, d.width), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_score_triple_bwd(
-            ctypes.byref(d), head.base.data_ptr(), _idx(head.idx, "head_idx"), tail.base.data_ptr(),
-            _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n, d_out.data_ptr(),
-            dh.data_ptr(), dt.data_ptr(), d_rel_table.data_ptr(), _stream(dev))
-    _check(rc, "bess_score_triple_bwd")
+    _launch("bess_score_triple_bwd", dev, ctypes.byref(d), head.base.data_ptr(), _idx(head.idx, "head_idx"),
+            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n,
+            d_out.data_ptr(), dh.data_ptr(), dt.data_ptr(), d_rel_table.data_ptr())
     return dh, dt
 
 
@@ -518,19 +544,13 @@ def query_triple_fwd(d: ModelDesc, side: int, head: RowSource, tail: RowSource, 
     if jobs:
         _same_device([("query rows", head.base)] + [("job dst", j[0]) for j in jobs] + [("job src", j[1]) for j in jobs])
         dst, src, val, words = _job_arrays(jobs, "query_triple_fwd")
-        with _on(dev):
-            rc = load().bess_query_triple_fwd_jobs(
-                ctypes.byref(d), side, head.base.data_ptr(), _idx(head.idx, "head_idx"), tail.base.data_ptr(),
-                _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n, q.data_ptr(), out.data_ptr(),
-                len(jobs), dst, src, val, words, _stream(dev))
-        _check(rc, "bess_query_triple_fwd_jobs")
+        _launch("bess_query_triple_fwd_jobs", dev, ctypes.byref(d), side, head.base.data_ptr(),
+                _idx(head.idx, "head_idx"), tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(),
+                rel_idx.data_ptr(), n, q.data_ptr(), out.data_ptr(), len(jobs), dst, src, val, words)
         return q, out
-    with _on(dev):
-        rc = load().bess_query_triple_fwd(
-            ctypes.byref(d), side, head.base.data_ptr(), _idx(head.idx, "head_idx"), tail.base.data_ptr(),
-            _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n, q.data_ptr(), out.data_ptr(),
-            _stream(dev))
-    _check(rc, "bess_query_triple_fwd")
+    _launch("bess_query_triple_fwd", dev, ctypes.byref(d), side, head.base.data_ptr(), _idx(head.idx, "head_idx"),
+            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n, q.data_ptr(),
+            out.data_ptr())
     return q, out
 
 
@@ -546,12 +566,9 @@ def query_triple_bwd(d: ModelDesc, side: int, head: RowSource, tail: RowSource, 
         raise ValueError("query_triple_bwd: gradient shapes do not match")
     dh = torch.empty((n, d.width), dtype=torch.float32, device=dev)
     dt = torch.empty((n, d.width), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_query_triple_bwd(
-            ctypes.byref(d), side, head.base.data_ptr(), _idx(head.idx, "head_idx"), tail.base.data_ptr(),
-            _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n, d_out.data_ptr(),
-            d_query.data_ptr(), dh.data_ptr(), dt.data_ptr(), d_rel_table.data_ptr(), _stream(dev))
-    _check(rc, "bess_query_triple_bwd")
+    _launch("bess_query_triple_bwd", dev, ctypes.byref(d), side, head.base.data_ptr(), _idx(head.idx, "head_idx"),
+            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n,
+            d_out.data_ptr(), d_query.data_ptr(), dh.data_ptr(), dt.data_ptr(), d_rel_table.data_ptr())
     return dh, dt
 
 
@@ -570,10 +587,8 @@ def _query_operands(d: ModelDesc, ent: RowSource, rel_table: torch.Tensor, rel_i
 def query_fwd(d: ModelDesc, side: int, ent: RowSource, rel_table: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
     dev, n = _query_operands(d, ent, rel_table, rel_idx)
     q = torch.empty((n, query_width(d)), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_query_fwd(ctypes.byref(d), side, ent.base.data_ptr(), _idx(ent.idx, "entity idx"),
-                                   rel_table.data_ptr(), rel_idx.data_ptr(), n, q.data_ptr(), _stream(dev))
-    _check(rc, "bess_query_fwd")
+    _launch("bess_query_fwd", dev, ctypes.byref(d), side, ent.base.data_ptr(), _idx(ent.idx, "entity idx"),
+            rel_table.data_ptr(), rel_idx.data_ptr(), n, q.data_ptr())
     return q
 
 
@@ -587,11 +602,8 @@ def query_bwd(d: ModelDesc, side: int, ent: RowSource, rel_table: torch.Tensor, 
     if tuple(d_query.shape) != (n, query_width(d)) or tuple(d_rel_table.shape) != tuple(rel_table.shape):
         raise ValueError("query_bwd: gradient shapes do not match")
     dx = torch.empty((n, d.width), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_query_bwd(ctypes.byref(d), side, ent.base.data_ptr(), _idx(ent.idx, "entity idx"),
-                                   rel_table.data_ptr(), rel_idx.data_ptr(), n, d_query.data_ptr(),
-                                   dx.data_ptr(), d_rel_table.data_ptr(), _stream(dev))
-    _check(rc, "bess_query_bwd")
+    _launch("bess_query_bwd", dev, ctypes.byref(d), side, ent.base.data_ptr(), _idx(ent.idx, "entity idx"),
+            rel_table.data_ptr(), rel_idx.data_ptr(), n, d_query.data_ptr(), dx.data_ptr(), d_rel_table.data_ptr())
     return dx
 
 
@@ -636,10 +648,8 @@ def neg_score_pertriple_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, n
     if tuple(out.shape) != (nq, n_neg):
         raise ValueError("neg_score_pertriple_fwd: bad `out` shape")
     ip, keep = _neg_idx_ptr(neg, dev)
-    with _on(dev), _Timed("bess_neg_score_pertriple_fwd", dev):
-        rc = load().bess_neg_score_pertriple_fwd(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), ip,
-                                                 n_neg, out.data_ptr(), n_neg, _stream(dev))
-    _check(rc, "bess_neg_score_pertriple_fwd")
+    _launch("bess_neg_score_pertriple_fwd", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), ip, n_neg,
+            out.data_ptr(), n_neg)
     del keep
     return out
 
@@ -675,13 +685,10 @@ def neg_score_pertriple_fwd_dq(d: ModelDesc, l: LossDesc, query: torch.Tensor, n
         if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 2 or not mask.is_contiguous():
             raise ValueError("neg_score_pertriple_fwd_dq: `mask` must be a contiguous 2-D bool / uint8 tensor")
         mrows, mcols = int(mask.shape[0]), int(mask.shape[1])
-    with _on(dev), _Timed("bess_neg_score_pertriple_fwd_dq", dev):
-        rc = load().bess_neg_score_pertriple_fwd_dq_masked(
-            ctypes.byref(d), ctypes.byref(l), query.data_ptr(), nq, neg.base.data_ptr(), ip, n_neg,
-            pos.data_ptr() if pos is not None else 0, weight.data_ptr(), weight.numel(),
+    _launch("bess_neg_score_pertriple_fwd_dq_masked", dev, ctypes.byref(d), ctypes.byref(l), query.data_ptr(), nq,
+            neg.base.data_ptr(), ip, n_neg, pos.data_ptr() if pos is not None else 0, weight.data_ptr(), weight.numel(),
             mask.data_ptr() if mask is not None else 0, mrows, mcols, out.data_ptr(), n_neg,
-            dq.data_ptr() if dq is not None else 0, st_ml.data_ptr(), st_acc.data_ptr(), _stream(dev))
-    _check(rc, "bess_neg_score_pertriple_fwd_dq_masked")
+            dq.data_ptr() if dq is not None else 0, st_ml.data_ptr(), st_acc.data_ptr())
     del keep
     return out, ((st_ml, st_acc) if defer else dq)
 
@@ -715,17 +722,13 @@ def pertriple_tail(d: ModelDesc, l: LossDesc, side: int, head: RowSource, tail: 
     row_loss, dp, loss = small[:n], small[n4: n4 + n], small[2 * n4: 2 * n4 + 1]
     dn = torch.empty((n, N), dtype=torch.float32, device=dev)
     rows = torch.empty((3 if want_d_query else 2, n, d.width), dtype=torch.float32, device=dev)
-    with _on(dev):
-        stream = _stream(dev)
-        counter = _counters(dev, stream, 1)
-        rc = load().bess_pertriple_tail(
-            ctypes.byref(d), ctypes.byref(l), side, head.base.data_ptr(), _idx(head.idx, "head_idx"),
-            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n,
-            st_ml.data_ptr(), st_acc.data_ptr(), items, pos.data_ptr(), neg.data_ptr(), N, int(neg.stride(0)),
-            weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(), dp.data_ptr(), dn.data_ptr(), N,
-            rows[2].data_ptr() if want_d_query else 0, rows[0].data_ptr(), rows[1].data_ptr(), d_rel_table.data_ptr(),
-            counter.data_ptr(), stream)
-    _check(rc, "bess_pertriple_tail")
+    counter = _counters(dev, 1)
+    _launch("bess_pertriple_tail", dev, ctypes.byref(d), ctypes.byref(l), side, head.base.data_ptr(),
+            _idx(head.idx, "head_idx"), tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(),
+            rel_idx.data_ptr(), n, st_ml.data_ptr(), st_acc.data_ptr(), items, pos.data_ptr(), neg.data_ptr(), N,
+            int(neg.stride(0)), weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(), dp.data_ptr(),
+            dn.data_ptr(), N, rows[2].data_ptr() if want_d_query else 0, rows[0].data_ptr(), rows[1].data_ptr(),
+            d_rel_table.data_ptr(), counter.data_ptr())
     res = (loss.reshape(()), dp, dn, rows[0], rows[1])
     return res + (rows[2],) if want_d_query else res
 
@@ -753,11 +756,8 @@ def neg_score_pertriple_fwd_partials(d: ModelDesc, l: LossDesc, query: torch.Ten
     st_ml = torch.empty((nq, items.value, 2), dtype=torch.float32, device=dev)
     st_acc = torch.empty((nq, items.value, d.width), dtype=torch.float32, device=dev)
     ip, keep = _neg_idx_ptr(neg, dev)
-    with _on(dev), _Timed("bess_neg_score_pertriple_fwd_partials", dev):
-        rc = load().bess_neg_score_pertriple_fwd_partials(
-            ctypes.byref(d), ctypes.byref(l), query.data_ptr(), nq, neg.base.data_ptr(), ip, n_neg, out.data_ptr(),
-            n_neg, st_ml.data_ptr(), st_acc.data_ptr(), _stream(dev))
-    _check(rc, "bess_neg_score_pertriple_fwd_partials")
+    _launch("bess_neg_score_pertriple_fwd_partials", dev, ctypes.byref(d), ctypes.byref(l), query.data_ptr(), nq,
+            neg.base.data_ptr(), ip, n_neg, out.data_ptr(), n_neg, st_ml.data_ptr(), st_acc.data_ptr())
     del keep
     return out, (st_ml, st_acc)
 
@@ -772,10 +772,8 @@ def combine_dq_partials(state: Tuple[torch.Tensor, torch.Tensor], norm: torch.Te
     if tuple(norm.shape) != (nq, 2) or not norm.is_contiguous():
         raise ValueError("combine_dq_partials: `norm` must be a contiguous [n_query, 2] tensor")
     dq = torch.empty((nq, W), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_combine_dq_partials(st_ml.data_ptr(), st_acc.data_ptr(), nq, items, W, norm.data_ptr(),
-                                             dq.data_ptr(), _stream(dev))
-    _check(rc, "bess_combine_dq_partials")
+    _launch("bess_combine_dq_partials", dev, st_ml.data_ptr(), st_acc.data_ptr(), nq, items, W, norm.data_ptr(),
+            dq.data_ptr())
     return dq
 
 
@@ -807,11 +805,8 @@ def neg_score_pertriple_bwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, n
         d.reserved[0] |= FLAG_DNEG_BY_ROW
         dn = d_neg_rows
     ip, keep = _neg_idx_ptr(neg, dev)
-    with _on(dev), _Timed("bess_neg_score_pertriple_bwd", dev):
-        rc = load().bess_neg_score_pertriple_bwd(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), ip,
-                                                 n_neg, d_out.data_ptr(), n_neg, dq.data_ptr() if want_d_query else 0,
-                                                 dn.data_ptr() if want_d_neg else 0, _stream(dev))
-    _check(rc, "bess_neg_score_pertriple_bwd")
+    _launch("bess_neg_score_pertriple_bwd", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), ip, n_neg,
+            d_out.data_ptr(), n_neg, dq.data_ptr() if want_d_query else 0, dn.data_ptr() if want_d_neg else 0)
     del keep
     return dq, (None if d_neg_rows is not None else dn)
 
@@ -824,10 +819,8 @@ def normalize_rows(neg: RowSource, n_part: int, normalize: bool) -> Tuple[torch.
     n = len(neg)
     hat = torch.empty((n, W), dtype=torch.float32, device=dev)
     inv = torch.empty((n, n_part), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_normalize_rows(_dtype_code(neg.base), neg.base.data_ptr(), _idx(neg.idx, "idx"), n, W, n_part,
-                                        int(normalize), hat.data_ptr(), inv.data_ptr(), _stream(dev))
-    _check(rc, "bess_normalize_rows")
+    _launch("bess_normalize_rows", dev, _dtype_code(neg.base), neg.base.data_ptr(), _idx(neg.idx, "idx"), n, W, n_part,
+            int(normalize), hat.data_ptr(), inv.data_ptr())
     return hat, inv
 
 
@@ -838,10 +831,8 @@ def normalize_rows_bwd(hat: torch.Tensor, inv: torch.Tensor, d_hat: torch.Tensor
     if hat.shape != d_hat.shape or inv.shape[0] != hat.shape[0]:
         raise ValueError("normalize_rows_bwd: shape mismatch")
     out = torch.empty_like(hat)
-    with _on(dev):
-        rc = load().bess_normalize_rows_bwd(hat.data_ptr(), inv.data_ptr(), d_hat.data_ptr(), hat.shape[0],
-                                            hat.shape[1], inv.shape[1], out.data_ptr(), _stream(dev))
-    _check(rc, "bess_normalize_rows_bwd")
+    _launch("bess_normalize_rows_bwd", dev, hat.data_ptr(), inv.data_ptr(), d_hat.data_ptr(), hat.shape[0],
+            hat.shape[1], inv.shape[1], out.data_ptr())
     return out
 
 
@@ -878,17 +869,13 @@ def neg_score_shared_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, pad_
             if mask.dtype != torch.bool or mask.dim() != 2 or not mask.is_contiguous():
                 raise ValueError("negative_mask must be a contiguous 2-D bool tensor")
             kd.mask, kd.mask_rows, kd.mask_cols = mask.data_ptr(), int(mask.shape[0]), int(mask.shape[1])
-    with _on(dev), _Timed("bess_neg_score_shared_fwd", dev):
-        if kd is None:
-            rc = lib.bess_neg_score_shared_fwd_ws(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                                                  _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld,
-                                                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream(dev))
-        else:
-            rc = lib.bess_neg_score_shared_fwd_masked(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                                                      _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld,
-                                                      ctypes.byref(kd), ws.data_ptr() if ws is not None else None,
-                                                      ws_bytes, _stream(dev))
-    _check(rc, "bess_neg_score_shared_fwd")
+    wp = ws.data_ptr() if ws is not None else None
+    if kd is None:
+        _launch("bess_neg_score_shared_fwd_ws", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+                _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, wp, ws_bytes)
+    else:
+        _launch("bess_neg_score_shared_fwd_masked", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+                _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, ctypes.byref(kd), wp, ws_bytes)
     return out if ld == n_neg else out[:, :n_neg]
 
 
@@ -914,12 +901,9 @@ def neg_score_shared_fwd_pruned(d: ModelDesc, query: torch.Tensor, neg: RowSourc
     lib = load()
     ws_bytes = int(lib.bess_neg_score_shared_workspace(ctypes.byref(d), nq, n_neg))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
-    with _on(dev), _Timed("bess_neg_score_shared_fwd", dev):
-        rc = lib.bess_neg_score_shared_fwd_pruned(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                                                  _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld,
-                                                  thr.data_ptr(), flags.data_ptr(), ldf,
-                                                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream(dev))
-    _check(rc, "bess_neg_score_shared_fwd_pruned")
+    _launch("bess_neg_score_shared_fwd_pruned", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, thr.data_ptr(), flags.data_ptr(), ldf,
+            ws.data_ptr() if ws is not None else None, ws_bytes)
     return (out if ld == n_neg else out[:, :n_neg]), flags
 
 
@@ -938,11 +922,8 @@ def neg_score_shared_pairs(d: ModelDesc, query: torch.Tensor, neg: RowSource, li
     lib = load()
     ws_bytes = int(lib.bess_neg_score_shared_fwd_pairs_workspace(ctypes.byref(d), int(like_n_query), int(like_n_neg)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    with _on(dev), _Timed("bess_neg_score_shared_fwd_pairs", dev):
-        rc = lib.bess_neg_score_shared_fwd_pairs(ctypes.byref(d), query.data_ptr(), neg.base.data_ptr(),
-                                                 _idx(neg.idx, "negative idx"), n, int(like_n_query), int(like_n_neg),
-                                                 out.data_ptr(), ws.data_ptr(), ws_bytes, _stream(dev))
-    _check(rc, "bess_neg_score_shared_fwd_pairs")
+    _launch("bess_neg_score_shared_fwd_pairs", dev, ctypes.byref(d), query.data_ptr(), neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n, int(like_n_query), int(like_n_neg), out.data_ptr(), ws.data_ptr(), ws_bytes)
     return out
 
 
@@ -972,12 +953,9 @@ def neg_score_shared_counts(d: ModelDesc, query: torch.Tensor, neg: RowSource, t
     lib = load()
     ws_bytes = int(lib.bess_neg_score_shared_fwd_counts_workspace(ctypes.byref(d), nq, n_neg))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
-    with _on(dev), _Timed("bess_neg_score_shared_fwd_counts", dev):
-        rc = lib.bess_neg_score_shared_fwd_counts(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                                                  _idx(neg.idx, "negative idx"), n_neg, thr.data_ptr(),
-                                                  excl.data_ptr(), counts.data_ptr(), int(bool(round_f16)),
-                                                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream(dev))
-    _check(rc, "bess_neg_score_shared_fwd_counts")
+    _launch("bess_neg_score_shared_fwd_counts", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n_neg, thr.data_ptr(), excl.data_ptr(), counts.data_ptr(),
+            int(bool(round_f16)), ws.data_ptr() if ws is not None else None, ws_bytes)
     return counts
 
 
@@ -1015,11 +993,8 @@ def neg_score_shared_bwd_parts(d: ModelDesc, query: torch.Tensor, neg: RowSource
     W = int(d.width)
     buf = torch.empty((n_dq * nq + n_de * n_neg, W), dtype=torch.float32, device=dev)
     dqp, dep = buf[: n_dq * nq].view(n_dq, nq, W), buf[n_dq * nq:].view(n_de, n_neg, W)
-    with _on(dev), _Timed("bess_neg_score_shared_bwd", dev):
-        rc = load().bess_neg_score_shared_bwd_parts(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                                                    _idx(neg.idx, "negative idx"), n_neg, d_out.data_ptr(), n_neg,
-                                                    dqp.data_ptr(), dep.data_ptr(), _stream(dev))
-    _check(rc, "bess_neg_score_shared_bwd_parts")
+    _launch("bess_neg_score_shared_bwd_parts", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n_neg, d_out.data_ptr(), n_neg, dqp.data_ptr(), dep.data_ptr())
     return dqp, dep
 
 
@@ -1047,14 +1022,11 @@ def query_triple_bwd_parts(d: ModelDesc, side: int, head: RowSource, tail: RowSo
     if tuple(acc_h.shape) != (int(head.base.shape[0]), W) or tuple(acc_t.shape) != (int(tail.base.shape[0]), W) \
             or acc_n.dim() != 2 or acc_n.shape[1] != W:
         raise ValueError("query_triple_bwd_parts: accumulators must cover the row spaces of the tables")
-    with _on(dev):
-        rc = load().bess_query_triple_bwd_parts(
-            ctypes.byref(d), side, head.base.data_ptr(), _idx(head.idx, "head_idx"), tail.base.data_ptr(),
-            _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n, d_out.data_ptr(),
-            dq_parts.data_ptr(), int(dq_parts.shape[0]), dneg_parts.data_ptr(), int(dneg_parts.shape[0]), n_neg,
-            _idx(neg_idx, "neg_idx", n_neg), acc_h.data_ptr(), acc_t.data_ptr(), acc_n.data_ptr(), d_rel_table.data_ptr(),
-            _stream(dev))
-    _check(rc, "bess_query_triple_bwd_parts")
+    _launch("bess_query_triple_bwd_parts", dev, ctypes.byref(d), side, head.base.data_ptr(), _idx(head.idx, "head_idx"),
+            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(), rel_idx.data_ptr(), n,
+            d_out.data_ptr(), dq_parts.data_ptr(), int(dq_parts.shape[0]), dneg_parts.data_ptr(),
+            int(dneg_parts.shape[0]), n_neg, _idx(neg_idx, "neg_idx", n_neg), acc_h.data_ptr(), acc_t.data_ptr(),
+            acc_n.data_ptr(), d_rel_table.data_ptr())
 
 
 def neg_score_shared_bwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, out: torch.Tensor,
@@ -1088,12 +1060,9 @@ def neg_score_shared_bwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, out:
     lib = load()
     ws_bytes = int(lib.bess_neg_score_shared_bwd_workspace(ctypes.byref(d), nq, n_neg))  # see neg_score_shared_fwd
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
-    with _on(dev), _Timed("bess_neg_score_shared_bwd", dev):
-        rc = lib.bess_neg_score_shared_bwd_ws(ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                                              _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), n_neg,
-                                              d_out.data_ptr(), n_neg, dq.data_ptr(), dn.data_ptr(),
-                                              ws.data_ptr() if ws is not None else None, ws_bytes, _stream(dev))
-    _check(rc, "bess_neg_score_shared_bwd")
+    _launch("bess_neg_score_shared_bwd_ws", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), n_neg, d_out.data_ptr(), n_neg, dq.data_ptr(),
+            dn.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes)
     if hat is not None and (d.reserved[1] & 1):
         dn = normalize_rows_bwd(hat, inv, dn)
     return dq, dn
@@ -1111,9 +1080,7 @@ def mask_scores(neg: torch.Tensor, diag_step: int, ht: bool, ppp: int, mask: Opt
         if mask.dtype != torch.bool or mask.dim() != 2 or not mask.is_contiguous():
             raise ValueError("negative_mask must be a contiguous 2-D bool tensor")
         mp, mrows, mcols = mask.data_ptr(), int(mask.shape[0]), int(mask.shape[1])
-    with _on(dev):
-        rc = load().bess_mask_scores(neg.data_ptr(), S, N, N, diag_step, int(ht), ppp, mp, mrows, mcols, _stream(dev))
-    _check(rc, "bess_mask_scores")
+    _launch("bess_mask_scores", dev, neg.data_ptr(), S, N, N, diag_step, int(ht), ppp, mp, mrows, mcols)
 
 
 _loss_counters: dict = {}  # (device, raw stream) -> int32 [TICKET_INTS], zero between calls
@@ -1134,23 +1101,19 @@ def loss_fwd_bwd(l: LossDesc, pos: torch.Tensor, neg: torch.Tensor, weight: torc
     dp = torch.empty((S,), dtype=torch.float32, device=dev) if want_grad else None
     dn = torch.empty((S, N), dtype=torch.float32, device=dev) if want_grad else None
     norm = torch.empty((S, 2), dtype=torch.float32, device=dev) if want_norm else None
-    with _on(dev):
-        stream = _stream(dev)
-        # (one launch: its last workgroup sums the row terms; the counter it needs is zero between calls)
-        capturing = torch.cuda.is_current_stream_capturing()
-        key = (dev, "capture") if capturing else (dev, stream)
-        counter = _loss_counters.get(key)
-        if counter is None:
-            counter = _loss_counters[key] = torch.zeros((TICKET_INTS,), dtype=torch.int32, device=dev)
-            if not capturing and (dev, "capture") not in _loss_counters:
-                # the counter of recorded steps exists before any recording starts (a tensor made while a
-                # stream is capturing would be cleared by a fill node at every replay: one more dispatch)
-                _loss_counters[(dev, "capture")] = torch.zeros((TICKET_INTS,), dtype=torch.int32, device=dev)
-        rc = load().bess_loss_fwd_bwd_one_launch(ctypes.byref(l), pos.data_ptr(), neg.data_ptr(), S, N, N,
-                                                 weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(),
-                                                 dp.data_ptr() if want_grad else 0, dn.data_ptr() if want_grad else 0, N,
-                                                 norm.data_ptr() if want_norm else 0, counter.data_ptr(), stream)
-    _check(rc, "bess_loss_fwd_bwd_one_launch")
+    # (one launch: its last workgroup sums the row terms; the counter it needs is zero between calls)
+    capturing = _capturing(dev)
+    key = (dev, "capture") if capturing else (dev, _stream(dev))
+    counter = _loss_counters.get(key)
+    if counter is None:
+        counter = _loss_counters[key] = torch.zeros((TICKET_INTS,), dtype=torch.int32, device=dev)
+        if not capturing and (dev, "capture") not in _loss_counters:
+            # the counter of recorded steps exists before any recording starts (a tensor made while a
+            # stream is capturing would be cleared by a fill node at every replay: one more dispatch)
+            _loss_counters[(dev, "capture")] = torch.zeros((TICKET_INTS,), dtype=torch.int32, device=dev)
+    _launch("bess_loss_fwd_bwd_one_launch", dev, ctypes.byref(l), pos.data_ptr(), neg.data_ptr(), S, N, N,
+            weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(), dp.data_ptr() if want_grad else 0,
+            dn.data_ptr() if want_grad else 0, N, norm.data_ptr() if want_norm else 0, counter.data_ptr())
     if want_norm:
         return loss.reshape(()), dp, dn, norm
     return loss.reshape(()), dp, dn
@@ -1159,13 +1122,19 @@ def loss_fwd_bwd(l: LossDesc, pos: torch.Tensor, neg: torch.Tensor, weight: torc
 _tail_counters: dict = {}  # (device, raw stream | "capture", slots) -> int32 [slots], zero between calls
 
 
-def _counters(dev: torch.device, stream: int, slots: int) -> torch.Tensor:
-    """Zeroed int32 counters that kernels of one stream leave zero again (one array per stream; recorded steps
-    share one that exists before any recording starts - a tensor made while a stream is capturing would be
+def _capturing(dev: torch.device) -> bool:
+    """Is PyTorch's current stream of `dev` being captured into a graph?"""
+    with _on(dev):
+        return torch.cuda.is_current_stream_capturing()
+
+
+def _counters(dev: torch.device, slots: int) -> torch.Tensor:
+    """Zeroed int32 counters that kernels of one stream leave zero again (one array per stream of `dev`; recorded
+    steps share one that exists before any recording starts - a tensor made while a stream is capturing would be
     cleared by a fill node at every replay)."""
     slots = max(1024, 1 << (slots - 1).bit_length())  # (>= BESS_TICKET_INTS)
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (dev, "capture" if capturing else stream, slots)
+    capturing = _capturing(dev)
+    key = (dev, "capture" if capturing else _stream(dev), slots)
     c = _tail_counters.get(key)
     if c is None:
         if capturing:
@@ -1215,15 +1184,11 @@ def neg_score_shared_fwd_loss(d: ModelDesc, l: LossDesc, query: torch.Tensor, ne
             if mask.dtype != torch.bool or mask.dim() != 2 or not mask.is_contiguous():
                 raise ValueError("negative_mask must be a contiguous 2-D bool tensor")
             kd.mask, kd.mask_rows, kd.mask_cols = mask.data_ptr(), int(mask.shape[0]), int(mask.shape[1])
-    with _on(dev), _Timed("bess_neg_score_shared_fwd_loss", dev):
-        stream = _stream(dev)
-        counters = _counters(dev, stream, (nq + 15) // 16 + 1)
-        rc = lib.bess_neg_score_shared_fwd_loss(
-            ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), _idx(neg.idx, "negative idx"), n_neg,
-            out.data_ptr(), ld, ctypes.byref(kd) if kd is not None else None, ctypes.byref(l), pos.data_ptr(),
-            weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(), dp.data_ptr(), dn.data_ptr(), ld,
-            counters.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes, stream)
-    _check(rc, "bess_neg_score_shared_fwd_loss")
+    counters = _counters(dev, (nq + 15) // 16 + 1)
+    _launch("bess_neg_score_shared_fwd_loss", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, ctypes.byref(kd) if kd is not None else None,
+            ctypes.byref(l), pos.data_ptr(), weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(),
+            dp.data_ptr(), dn.data_ptr(), ld, counters.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes)
     return out, loss.reshape(()), dp, dn
 
 
@@ -1236,9 +1201,7 @@ def scatter_add_rows(dst: torch.Tensor, idx: torch.Tensor, src: torch.Tensor, sc
     _rows(src, "src", W)
     n = int(src.shape[0])
     ip = _idx(idx, "idx", n)
-    with _on(dev):
-        rc = load().bess_scatter_add_rows(dst.data_ptr(), W, ip, src.data_ptr(), n, scale, _stream(dev))
-    _check(rc, "bess_scatter_add_rows")
+    _launch("bess_scatter_add_rows", dev, dst.data_ptr(), W, ip, src.data_ptr(), n, scale)
 
 
 def sparse_sgd(table: torch.Tensor, idx: torch.Tensor, grad: torch.Tensor, lr: float) -> None:
@@ -1249,9 +1212,7 @@ def sparse_sgd(table: torch.Tensor, idx: torch.Tensor, grad: torch.Tensor, lr: f
     _rows(grad, "grad", W)
     n = int(grad.shape[0])
     ip = _idx(idx, "idx", n)
-    with _on(dev), _Timed("bess_sparse_sgd", dev):
-        rc = load().bess_sparse_sgd(_dtype_code(table), W, table.data_ptr(), ip, grad.data_ptr(), n, lr, _stream(dev))
-    _check(rc, "bess_sparse_sgd")
+    _launch("bess_sparse_sgd", dev, _dtype_code(table), W, table.data_ptr(), ip, grad.data_ptr(), n, lr)
 
 
 def sparse_sgd_lists(table: torch.Tensor, lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], lr: float,
@@ -1280,11 +1241,8 @@ def sparse_sgd_lists(table: torch.Tensor, lists: Sequence[Tuple[torch.Tensor, to
         if x_table.dtype != table.dtype or not x_table.is_contiguous() or x_grad.numel() != x_table.numel():
             raise ValueError("sparse_sgd_lists: the axpy table must be contiguous, of the table's dtype, and match its gradient")
         x_n = int(x_table.numel())
-    with _on(dev), _Timed("bess_sparse_sgd_lists", dev):
-        rc = load().bess_sparse_sgd_lists_axpy(_dtype_code(table), W, table.data_ptr(), len(lists), ip, gp, rows, lr,
-                                               x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None,
-                                               x_n, float(x_alpha), _stream(dev))
-    _check(rc, "bess_sparse_sgd_lists")
+    _launch("bess_sparse_sgd_lists_axpy", dev, _dtype_code(table), W, table.data_ptr(), len(lists), ip, gp, rows, lr,
+            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha))
 
 
 def dense_sgd(table: torch.Tensor, grad: torch.Tensor, lr: float) -> None:
@@ -1292,9 +1250,7 @@ def dense_sgd(table: torch.Tensor, grad: torch.Tensor, lr: float) -> None:
     _f32(grad, "grad")
     if not table.is_contiguous() or table.numel() != grad.numel():
         raise ValueError("dense_sgd: table / grad mismatch")
-    with _on(dev):
-        rc = load().bess_dense_sgd(_dtype_code(table), table.data_ptr(), grad.data_ptr(), table.numel(), lr, _stream(dev))
-    _check(rc, "bess_dense_sgd")
+    _launch("bess_dense_sgd", dev, _dtype_code(table), table.data_ptr(), grad.data_ptr(), table.numel(), lr)
 
 
 SEGMENT_CAP = 256  # BESS_SEGMENT_CAP of include/besskge_hip.h
@@ -1320,12 +1276,9 @@ class SegmentIndex:
         ws = torch.empty((need.value,), dtype=torch.uint8, device=dev)
         self._allocate(n, n_rows, dev)
         bits = max(1, int(n_rows - 1).bit_length())
-        with _on(dev), _Timed("bess_build_segment_index", dev):
-            rc = load().bess_build_segment_index(ip, n, bits, self.refs.data_ptr(), self.seg_rows.data_ptr(),
-                                                 self.seg_offsets.data_ptr(), self.n_seg.data_ptr(),
-                                                 self.long_segs.data_ptr(), self.long_cap, ws.data_ptr(),
-                                                 need.value, _stream(dev))
-        _check(rc, "bess_build_segment_index")
+        _launch("bess_build_segment_index", dev, ip, n, bits, self.refs.data_ptr(), self.seg_rows.data_ptr(),
+                self.seg_offsets.data_ptr(), self.n_seg.data_ptr(), self.long_segs.data_ptr(), self.long_cap,
+                ws.data_ptr(), need.value)
         self._long_scratch(dev, width, scratch)
 
     def _allocate(self, n: int, n_rows: int, dev: torch.device) -> None:
@@ -1398,13 +1351,10 @@ def step_prologue(jobs: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], int
         seg = SegmentIndex.__new__(SegmentIndex)
         seg._allocate(n_ids, n_rows, dev)
     bits = max(1, int(max(1, n_rows) - 1).bit_length())
-    with _on(dev), _Timed("bess_step_prologue", dev):
-        rc = load().bess_step_prologue(
-            nj, dst, src, val, words, nl, lp, ll, bits,
-            seg.refs.data_ptr() if seg else None, seg.seg_rows.data_ptr() if seg else None,
-            seg.seg_offsets.data_ptr() if seg else None, seg.n_seg.data_ptr() if seg else None,
-            seg.long_segs.data_ptr() if seg else None, seg.long_cap if seg else 0, _stream(dev))
-    _check(rc, "bess_step_prologue")
+    _launch("bess_step_prologue", dev, nj, dst, src, val, words, nl, lp, ll, bits, seg.refs.data_ptr() if seg else None,
+            seg.seg_rows.data_ptr() if seg else None, seg.seg_offsets.data_ptr() if seg else None,
+            seg.n_seg.data_ptr() if seg else None, seg.long_segs.data_ptr() if seg else None,
+            seg.long_cap if seg else 0)
     if seg is not None:
         seg._long_scratch(dev, width, scratch)
     return seg
@@ -1449,18 +1399,11 @@ def neg_pertriple_grad_segments(d: ModelDesc, query: torch.Tensor, table: torch.
     if native and (seg.long_grad is None or seg.long_grad.shape[1] != d.width):
         seg.long_grad = torch.zeros((seg.long_cap, d.width), dtype=torch.float32, device=dev)
     long_grad = seg.long_grad
-    with _on(dev), _Timed("bess_neg_pertriple_grad_segments", dev):
-        rc = load().bess_neg_pertriple_grad_segments(ctypes.byref(d), query.data_ptr(), nq, table.data_ptr(), n_neg,
-                                                     d_out.data_ptr(), n_neg, seg.refs.data_ptr(),
-                                                     seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(),
-                                                     seg.n_seg.data_ptr(), seg.max_seg,
-                                                     0 if fused else grad.data_ptr(),
-                                                     float(fused_sgd_lr) if fused else 0.0,
-                                                     seg.long_segs.data_ptr() if native else None,
-                                                     seg.long_cap if native else 0,
-                                                     long_grad.data_ptr() if native else None,
-                                                     seg.long_count.data_ptr() if native else None, _stream(dev))
-    _check(rc, "bess_neg_pertriple_grad_segments")
+    _launch("bess_neg_pertriple_grad_segments", dev, ctypes.byref(d), query.data_ptr(), nq, table.data_ptr(), n_neg,
+            d_out.data_ptr(), n_neg, seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(),
+            seg.n_seg.data_ptr(), seg.max_seg, 0 if fused else grad.data_ptr(), float(fused_sgd_lr) if fused else 0.0,
+            seg.long_segs.data_ptr() if native else None, seg.long_cap if native else 0,
+            long_grad.data_ptr() if native else None, seg.long_count.data_ptr() if native else None)
     return grad
 
 
@@ -1471,10 +1414,8 @@ def pad_segments(seg: SegmentIndex, grad_seg: torch.Tensor) -> Tuple[torch.Tenso
     _f32(grad_seg, "grad_seg")
     if grad_seg.dim() != 2 or grad_seg.shape[0] != seg.max_seg or not grad_seg.is_contiguous():
         raise ValueError("pad_segments: grad_seg must be a contiguous [seg.max_seg, W] tensor")
-    with _on(dev):
-        rc = load().bess_pad_segments(seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg, grad_seg.data_ptr(),
-                                      int(grad_seg.shape[1]), _stream(dev))
-    _check(rc, "bess_pad_segments")
+    _launch("bess_pad_segments", dev, seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg, grad_seg.data_ptr(),
+            int(grad_seg.shape[1]))
     return seg.seg_rows[: seg.max_seg], grad_seg
 
 
@@ -1485,10 +1426,8 @@ def apply_segments_sgd(table: torch.Tensor, seg: SegmentIndex, grad_seg: torch.T
     _f32(grad_seg, "grad_seg")
     if tuple(grad_seg.shape) != (seg.max_seg, W):
         raise ValueError("apply_segments_sgd: grad_seg shape mismatch")
-    with _on(dev), _Timed("bess_apply_segments_sgd", dev):
-        rc = load().bess_apply_segments_sgd(_dtype_code(table), W, table.data_ptr(), seg.seg_rows.data_ptr(),
-                                            seg.n_seg.data_ptr(), seg.max_seg, grad_seg.data_ptr(), lr, _stream(dev))
-    _check(rc, "bess_apply_segments_sgd")
+    _launch("bess_apply_segments_sgd", dev, _dtype_code(table), W, table.data_ptr(), seg.seg_rows.data_ptr(),
+            seg.n_seg.data_ptr(), seg.max_seg, grad_seg.data_ptr(), lr)
 
 
 def segment_sum_rows(src: torch.Tensor, seg: SegmentIndex) -> torch.Tensor:
@@ -1499,10 +1438,8 @@ def segment_sum_rows(src: torch.Tensor, seg: SegmentIndex) -> torch.Tensor:
         raise ValueError("segment_sum_rows: src must be [n_refs, W]")
     W = int(src.shape[1])
     out = torch.empty((seg.max_seg, W), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_segment_sum_rows(W, src.data_ptr(), seg.refs.data_ptr(), seg.seg_offsets.data_ptr(),
-                                          seg.n_seg.data_ptr(), seg.max_seg, out.data_ptr(), _stream(dev))
-    _check(rc, "bess_segment_sum_rows")
+    _launch("bess_segment_sum_rows", dev, W, src.data_ptr(), seg.refs.data_ptr(), seg.seg_offsets.data_ptr(),
+            seg.n_seg.data_ptr(), seg.max_seg, out.data_ptr())
     return out
 
 
@@ -1518,13 +1455,10 @@ def apply_segments_opt(o: OptDesc, table: torch.Tensor, seg: SegmentIndex, grad_
         raise ValueError("apply_segments_opt: grad_seg shape mismatch")
     _state_ok(state1, table, o, "state1")
     _state_ok(state2, table, o, "state2")
-    with _on(dev):
-        rc = load().bess_apply_segments_opt(ctypes.byref(o), _dtype_code(table), W, table.data_ptr(),
-                                            seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
-                                            grad_seg.data_ptr(), state1.data_ptr() if state1 is not None else 0,
-                                            state2.data_ptr() if state2 is not None else 0,
-                                            keep.data_ptr() if keep is not None else None, _stream(dev))
-    _check(rc, "bess_apply_segments_opt")
+    _launch("bess_apply_segments_opt", dev, ctypes.byref(o), _dtype_code(table), W, table.data_ptr(),
+            seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg, grad_seg.data_ptr(),
+            state1.data_ptr() if state1 is not None else 0, state2.data_ptr() if state2 is not None else 0,
+            keep.data_ptr() if keep is not None else None)
 
 
 MAX_ROW_LISTS = 8  # BESS_MAX_ROW_LISTS
@@ -1566,14 +1500,12 @@ def coalesced_update(o: Optional[OptDesc], table: torch.Tensor, seg: SegmentInde
         if x_table.dtype != table.dtype or not x_table.is_contiguous() or x_grad.numel() != x_table.numel():
             raise ValueError("coalesced_update: the axpy table must be contiguous, of the table's dtype, and match its gradient")
         x_n = int(x_table.numel())
-    with _on(dev), _Timed("bess_coalesced_update", dev):
-        rc = load().bess_coalesced_update_axpy(
-            ctypes.byref(o) if o is not None else None, _dtype_code(table), W, table.data_ptr(), len(grads), ptrs, rows,
-            seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
+    _launch("bess_coalesced_update_axpy", dev, ctypes.byref(o) if o is not None else None, _dtype_code(table), W,
+            table.data_ptr(), len(grads), ptrs, rows, seg.refs.data_ptr(), seg.seg_rows.data_ptr(),
+            seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
             state1.data_ptr() if state1 is not None else None, state2.data_ptr() if state2 is not None else None,
             keep.data_ptr() if keep is not None else None, out.data_ptr() if out is not None else None,
-            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha), _stream(dev))
-    _check(rc, "bess_coalesced_update")
+            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha))
     return out
 
 
@@ -1628,13 +1560,10 @@ def direct_update(o: OptDesc, table: torch.Tensor, id_lists: Sequence[torch.Tens
         if x_table.dtype != table.dtype or not x_table.is_contiguous() or x_grad.numel() != x_table.numel():
             raise ValueError("direct_update: the axpy table must be contiguous, of the table's dtype, and match its gradient")
         x_n = int(x_table.numel())
-    with _on(dev), _Timed("bess_direct_update", dev):
-        rc = load().bess_direct_update(
-            ctypes.byref(o), _dtype_code(table), W, table.data_ptr(), len(id_lists), ptrs, lens, scratch.acc.data_ptr(),
-            scratch.claim.data_ptr(), scratch.generation.data_ptr(),
+    _launch("bess_direct_update", dev, ctypes.byref(o), _dtype_code(table), W, table.data_ptr(), len(id_lists), ptrs,
+            lens, scratch.acc.data_ptr(), scratch.claim.data_ptr(), scratch.generation.data_ptr(),
             state1.data_ptr() if state1 is not None else None, state2.data_ptr() if state2 is not None else None,
-            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha), _stream(dev))
-    _check(rc, "bess_direct_update")
+            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha))
 
 
 def assign_state_rows(seg: Any, slot_map: torch.Tensor, counter: torch.Tensor, capacity: int,
@@ -1643,11 +1572,8 @@ def assign_state_rows(seg: Any, slot_map: torch.Tensor, counter: torch.Tensor, c
     dev = _same_device([("seg_rows", seg.seg_rows), ("slot_map", slot_map), ("counter", counter), ("keep", keep)])
     if slot_map.dtype != torch.int32 or counter.dtype != torch.int32 or not slot_map.is_contiguous():
         raise ValueError("assign_state_rows: slot_map / counter must be int32")
-    with _on(dev):
-        rc = load().bess_assign_state_rows(seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
-                                           keep.data_ptr() if keep is not None else None, slot_map.data_ptr(),
-                                           counter.data_ptr(), int(capacity), _stream(dev))
-    _check(rc, "bess_assign_state_rows")
+    _launch("bess_assign_state_rows", dev, seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
+            keep.data_ptr() if keep is not None else None, slot_map.data_ptr(), counter.data_ptr(), int(capacity))
 
 
 def _state_ok(st: Optional[torch.Tensor], table: torch.Tensor, o: Optional[OptDesc], name: str) -> None:
@@ -1664,11 +1590,8 @@ def map_extra_rows(seg: SegmentIndex, extra: SegmentIndex) -> Tuple[torch.Tensor
     dev = _same_device([("seg_rows", seg.seg_rows), ("extra_rows", extra.seg_rows)])
     xmap = torch.empty((seg.max_seg,), dtype=torch.int32, device=dev)
     keep = torch.empty((extra.max_seg,), dtype=torch.int32, device=dev)
-    with _on(dev):
-        rc = load().bess_map_extra_rows(seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
-                                        extra.seg_rows.data_ptr(), extra.n_seg.data_ptr(), extra.max_seg,
-                                        xmap.data_ptr(), keep.data_ptr(), _stream(dev))
-    _check(rc, "bess_map_extra_rows")
+    _launch("bess_map_extra_rows", dev, seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
+            extra.seg_rows.data_ptr(), extra.n_seg.data_ptr(), extra.max_seg, xmap.data_ptr(), keep.data_ptr())
     return xmap, keep
 
 
@@ -1698,16 +1621,12 @@ def neg_pertriple_step_segments(d: ModelDesc, query: torch.Tensor, table: torch.
             raise ValueError("neg_pertriple_step_segments: extra_map / extra_sum shapes")
     if seg.long_grad is None or seg.long_grad.shape[1] != d.width:
         seg.long_grad = torch.zeros((seg.long_cap, d.width), dtype=torch.float32, device=dev)
-    with _on(dev), _Timed("bess_neg_pertriple_step_segments", dev):
-        rc = load().bess_neg_pertriple_step_segments(
-            ctypes.byref(d), query.data_ptr(), nq, table.data_ptr(), n_neg, d_out.data_ptr(), n_neg,
-            seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr(),
-            seg.max_seg, seg.long_segs.data_ptr(), seg.long_cap, seg.long_grad.data_ptr(), seg.long_count.data_ptr(),
-            ctypes.byref(o), state1.data_ptr() if state1 is not None else None,
-            state2.data_ptr() if state2 is not None else None,
-            extra_map.data_ptr() if extra_map is not None else None,
-            extra_sum.data_ptr() if extra_sum is not None else None, _stream(dev))
-    _check(rc, "bess_neg_pertriple_step_segments")
+    _launch("bess_neg_pertriple_step_segments", dev, ctypes.byref(d), query.data_ptr(), nq, table.data_ptr(), n_neg,
+            d_out.data_ptr(), n_neg, seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(),
+            seg.n_seg.data_ptr(), seg.max_seg, seg.long_segs.data_ptr(), seg.long_cap, seg.long_grad.data_ptr(),
+            seg.long_count.data_ptr(), ctypes.byref(o), state1.data_ptr() if state1 is not None else None,
+            state2.data_ptr() if state2 is not None else None, extra_map.data_ptr() if extra_map is not None else None,
+            extra_sum.data_ptr() if extra_sum is not None else None)
 
 
 def ranks_from_scores(pos: torch.Tensor, cand: torch.Tensor, mode: int, worst_rank_infty: bool) -> torch.Tensor:
@@ -1717,10 +1636,8 @@ def ranks_from_scores(pos: torch.Tensor, cand: torch.Tensor, mode: int, worst_ra
     if cand.dim() != 2 or cand.shape[0] != pos.numel():
         raise ValueError("`pos_score` and `candidate_score` need to have same size at dimension 0")
     out = torch.empty((pos.numel(),), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_ranks_from_scores(pos.data_ptr(), cand.data_ptr(), pos.numel(), cand.shape[1], cand.shape[1],
-                                           mode, int(worst_rank_infty), out.data_ptr(), _stream(dev))
-    _check(rc, "bess_ranks_from_scores")
+    _launch("bess_ranks_from_scores", dev, pos.data_ptr(), cand.data_ptr(), pos.numel(), cand.shape[1], cand.shape[1],
+            mode, int(worst_rank_infty), out.data_ptr())
     return out
 
 
@@ -1731,10 +1648,8 @@ def ranks_from_indices(truth: torch.Tensor, cand: torch.Tensor, worst_rank_infty
     if cand.dim() != 2 or cand.shape[0] != truth.numel():
         raise ValueError("`ground_truth` and `candidate_indices` need to have the same size for dimension 0")
     out = torch.empty((truth.numel(),), dtype=torch.float32, device=dev)
-    with _on(dev):
-        rc = load().bess_ranks_from_indices(truth.data_ptr(), cand.data_ptr(), truth.numel(), cand.shape[1],
-                                            int(worst_rank_infty), out.data_ptr(), _stream(dev))
-    _check(rc, "bess_ranks_from_indices")
+    _launch("bess_ranks_from_indices", dev, truth.data_ptr(), cand.data_ptr(), truth.numel(), cand.shape[1],
+            int(worst_rank_infty), out.data_ptr())
     return out
 
 
@@ -1764,24 +1679,18 @@ def topk_update(scores: torch.Tensor, best_score: torch.Tensor, best_id: torch.T
                 or not mask.is_contiguous():
             raise ValueError("topk_update: mask must be a contiguous bool [1 | rows, L] tensor")
         mp, mr = mask.data_ptr(), int(mask.shape[0])
+    ld = int(scores.stride(0)) if R > 1 else L
     if flags is not None:
         if ids is not None or mask is not None:
             raise ValueError("topk_update: flagged tiles take ids from id_base and no mask")
         if flags.dtype != torch.uint8 or flags.dim() != 2 or flags.shape[0] != R or not flags.is_contiguous() \
                 or flags.shape[1] % 4 or flags.shape[1] * 64 < L:
             raise ValueError("topk_update: flags must be a contiguous uint8 [rows, 4 * ceil(L / 256)] tensor")
-        with _on(dev), _Timed("bess_topk_update", dev):
-            ld = int(scores.stride(0)) if R > 1 else L
-            rc = load().bess_topk_update_flagged(scores.data_ptr(), R, L, max(ld, L), flags.data_ptr(),
-                                                 int(flags.shape[1]), int(id_base), best_score.data_ptr(),
-                                                 best_id.data_ptr(), kk, _stream(dev))
-        _check(rc, "bess_topk_update_flagged")
+        _launch("bess_topk_update_flagged", dev, scores.data_ptr(), R, L, max(ld, L), flags.data_ptr(),
+                int(flags.shape[1]), int(id_base), best_score.data_ptr(), best_id.data_ptr(), kk)
         return
-    with _on(dev), _Timed("bess_topk_update", dev):
-        ld = int(scores.stride(0)) if R > 1 else L
-        rc = load().bess_topk_update(scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr,
-                                     best_score.data_ptr(), best_id.data_ptr(), kk, _stream(dev))
-    _check(rc, "bess_topk_update")
+    _launch("bess_topk_update", dev, scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr,
+            best_score.data_ptr(), best_id.data_ptr(), kk)
 
 
 # --------------------------------------------------------------------------- #
@@ -1814,10 +1723,8 @@ def sample_negatives(gen: Pcg64State, jump_table: torch.Tensor, n_step: int, n_s
     tcp = _int_tensor(type_counts, "type_counts", torch.int32)
     top = _int_tensor(type_offsets, "type_offsets", torch.int32)
     out = torch.empty((n_step, src_count, n_shard, B, K), dtype=torch.int32, device=dev)
-    with _Timed("bess_sample_negatives", dev):
-        _check(load().bess_sample_negatives(ctypes.byref(gen), tp, n_step, n_shard, src_begin, src_count, B, K, cp,
-                                            wp, tcp, top, n_type, int(local_sampling), out.data_ptr(),
-                                            _stream(dev)), "sample_negatives")
+    _launch("bess_sample_negatives", dev, ctypes.byref(gen), tp, n_step, n_shard, src_begin, src_count, B, K, cp, wp, tcp,
+            top, n_type, int(local_sampling), out.data_ptr())
     return out
 
 
@@ -1833,8 +1740,8 @@ def sample_bucket_indices(gen: Pcg64State, jump_table: torch.Tensor, shape: Sequ
     cp = _int_tensor(counts, "counts", torch.int64, n_bucket)
     op = _int_tensor(offsets, "offsets", torch.int64, n_bucket)
     out = torch.empty(tuple(int(s) for s in shape), dtype=torch.int64, device=dev)
-    _check(load().bess_sample_bucket_indices(ctypes.byref(gen), tp, out.numel(), int(shape[-1]), n_bucket, cp, op,
-                                             out.data_ptr(), _stream(dev)), "sample_bucket_indices")
+    _launch("bess_sample_bucket_indices", dev, ctypes.byref(gen), tp, out.numel(), int(shape[-1]), n_bucket, cp, op,
+            out.data_ptr())
     return out
 
 
@@ -1862,9 +1769,8 @@ def lookup_triples(triples: torch.Tensor, sample_idx: torch.Tensor, swap_tail: b
             shape = (n_step, n2, n1, ppp)
         out[k] = torch.empty(shape, dtype=torch.int32, device=dev)
     ptr = lambda k: out[k].data_ptr() if k in out else 0  # noqa: E731
-    _check(load().bess_lookup_triples(triples.data_ptr(), triples.shape[0], sample_idx.data_ptr(), n_step, n1, n2,
-                                      ppp, int(swap_tail), ptr("head"), ptr("relation"), ptr("tail"),
-                                      _stream(dev)), "lookup_triples")
+    _launch("bess_lookup_triples", dev, triples.data_ptr(), triples.shape[0], sample_idx.data_ptr(), n_step, n1, n2, ppp,
+            int(swap_tail), ptr("head"), ptr("relation"), ptr("tail"))
     return out
 
 
@@ -1894,13 +1800,10 @@ def gather_candidate_lists(table_h: torch.Tensor, mask_h: Optional[torch.Tensor]
     if want_mask and mask_h is not None:
         shape = (n_step, n_neg_shard, n_shard, T, L) if mask_gather_layout else (n_step, n_shard, T, n_neg_shard, L)
         msk = torch.empty(shape, dtype=torch.bool, device=dev)
-    with _on(dev), _Timed("bess_gather_candidate_lists", dev):
-        rc = load().bess_gather_candidate_lists(
-            table_h.data_ptr(), table_t.data_ptr() if table_t is not None else None,
+    _launch("bess_gather_candidate_lists", dev, table_h.data_ptr(), table_t.data_ptr() if table_t is not None else None,
             mask_h.data_ptr() if mask_h is not None else None, mask_t.data_ptr() if mask_t is not None else None,
             n_list, lookup.data_ptr(), n_step, n_shard, T, int(per_part), int(half), n_neg_shard, L,
-            int(bool(mask_gather_layout)), ent.data_ptr(), msk.data_ptr() if msk is not None else None, _stream(dev))
-    _check(rc, "bess_gather_candidate_lists")
+            int(bool(mask_gather_layout)), ent.data_ptr(), msk.data_ptr() if msk is not None else None)
     return ent, msk
 
 
@@ -2006,30 +1909,23 @@ class Communicator:
             raise ValueError("all_to_all: recv does not match send")
         per_peer = send[0].numel() * send.element_size()
         self._note_capture()
-        with _on(self.device), _Timed("bess_alltoall", self.device):
-            rc = load().bess_alltoall(self._h, self._buf(send, "send"), self._buf(recv, "recv"), per_peer,
-                                      _stream(self.device))
-        _check(rc, "bess_alltoall")
+        _launch("bess_alltoall", self.device, self._h, self._buf(send, "send"), self._buf(recv, "recv"), per_peer)
         return recv
 
     def all_gather(self, send: torch.Tensor) -> torch.Tensor:
         """recv [world, *send.shape] in rank order."""
         recv = torch.empty((self.world, *send.shape), dtype=send.dtype, device=send.device)
         self._note_capture()
-        with _on(self.device), _Timed("bess_allgather", self.device):
-            rc = load().bess_allgather(self._h, self._buf(send, "send"), self._buf(recv, "recv"),
-                                       send.numel() * send.element_size(), _stream(self.device))
-        _check(rc, "bess_allgather")
+        _launch("bess_allgather", self.device, self._h, self._buf(send, "send"), self._buf(recv, "recv"),
+                send.numel() * send.element_size())
         return recv
 
     def all_reduce_sum_(self, x: torch.Tensor) -> torch.Tensor:
         """In-place sum over ranks of a float32 tensor."""
         _f32(x, "x")
         self._note_capture()
-        with _on(self.device), _Timed("bess_allreduce_sum_f32", self.device):
-            p = self._buf(x, "x")
-            rc = load().bess_allreduce_sum_f32(self._h, p, p, x.numel(), _stream(self.device))
-        _check(rc, "bess_allreduce_sum_f32")
+        p = self._buf(x, "x")
+        _launch("bess_allreduce_sum_f32", self.device, self._h, p, p, x.numel())
         return x
 
     def pack_exchange(self, table: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -2042,11 +1938,8 @@ class Communicator:
         send = torch.empty((self.world, L, W), dtype=table.dtype, device=table.device)
         recv = torch.empty_like(send)
         self._note_capture()
-        with _on(self.device), _Timed("bess_pack_exchange", self.device):
-            rc = load().bess_pack_exchange(self._h, _dtype_code(table), W, self._buf(table, "table"),
-                                           self._buf(idx, "idx"), L, send.data_ptr(), recv.data_ptr(),
-                                           _stream(self.device))
-        _check(rc, "bess_pack_exchange")
+        _launch("bess_pack_exchange", self.device, self._h, _dtype_code(table), W, self._buf(table, "table"),
+                self._buf(idx, "idx"), L, send.data_ptr(), recv.data_ptr())
         return send, recv
 
 
@@ -2087,19 +1980,20 @@ class Plan:
         self.names: List[str] = []
 
     def __len__(self) -> int:
-        return int(_real_lib().bess_plan_length(self._h))
+        return int(load().bess_plan_length(self._h))
 
-    def _add(self, name: str, argtypes: Sequence[Any], args: Sequence[Any]) -> None:
-        n = len(args)
-        kinds = (ctypes.c_uint8 * max(1, n))()
-        values = (ctypes.c_uint64 * max(1, n))()
-        blobs = (_vp * max(1, n))()
-        sizes = (_i64 * max(1, n))()
+    def _add(self, name: str, args: Sequence[Any]) -> None:
+        """Note a call of entry point `name` (`_launch`): `args` are all its arguments but the trailing stream, which
+        a replay supplies."""
+        n = len(args) + 1
+        kinds = (ctypes.c_uint8 * n)()
+        values = (ctypes.c_uint64 * n)()
+        blobs = (_vp * n)()
+        sizes = (_i64 * n)()
         keep = []  # the ctypes objects whose bytes are copied must outlive the call
-        for k, (tp, a) in enumerate(zip(argtypes, args)):
-            if k == n - 1:
-                kinds[k] = PLAN_ARG_STREAM
-            elif tp in _INT_TYPES:
+        kinds[n - 1] = PLAN_ARG_STREAM
+        for k, (tp, a) in enumerate(zip(SIGNATURES[name], args)):
+            if tp in _INT_TYPES:
                 kinds[k], values[k] = PLAN_ARG_INT, int(a) & 0xFFFFFFFFFFFFFFFF
             elif tp is ctypes.c_float or tp is ctypes.c_double:
                 kinds[k] = PLAN_ARG_FLOAT
@@ -2117,23 +2011,23 @@ class Plan:
                     keep.append(obj)
                 else:
                     raise TypeError(f"record_plan: {name} argument {k}: cannot record a {type(a).__name__}")
-        _check(_real_lib().bess_plan_add_call(self._h, name.encode(), n, kinds, values, blobs, sizes), "bess_plan_add_call")
+        _check(load().bess_plan_add_call(self._h, name.encode(), n, kinds, values, blobs, sizes), "bess_plan_add_call")
         self.names.append(name)
 
     def run(self) -> None:
         with _on(self.device):
-            rc = _real_lib().bess_plan_run(self._h, _stream(self.device))
+            rc = load().bess_plan_run(self._h, _stream(self.device))
         _check(rc, "bess_plan_run")
 
     def run_on(self, stream: int) -> None:
         """`bess_plan_run` on a raw hipStream_t (worker threads of a multi-device process: the device must be the
         thread's current one)."""
-        _check(_real_lib().bess_plan_run(self._h, stream), "bess_plan_run")
+        _check(load().bess_plan_run(self._h, stream), "bess_plan_run")
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
             h, self._h = self._h, _vp()
-            _real_lib().bess_plan_destroy(h)
+            load().bess_plan_destroy(h)
 
     def __del__(self, _finalizing: Any = sys.is_finalizing) -> None:  # pragma: no cover
         if not _finalizing():
@@ -2143,50 +2037,17 @@ class Plan:
                 pass
 
 
-class _RecordingLib:
-    """Stands in for the library while a plan is recorded: every call goes through to it; the ones that enqueue
-    work are noted in the plan with their argument values."""
-
-    def __init__(self, lib: ctypes.CDLL, plan: Plan) -> None:
-        self._lib, self._plan = lib, plan
-        self._wrapped: dict = {}
-
-    def __getattr__(self, name: str) -> Any:
-        fn = getattr(self._lib, name)
-        if not name.startswith("bess_") or not self._lib.bess_plan_knows(name.encode()):
-            return fn
-        w = self._wrapped.get(name)
-        if w is None:
-            plan, argtypes = self._plan, fn.argtypes
-
-            def w(*args: Any, _fn: Any = fn, _name: str = name) -> int:
-                rc = _fn(*args)
-                if rc == 0:
-                    plan._add(_name, argtypes, args)
-                return rc
-
-            self._wrapped[name] = w
-        return w
-
-
-def _real_lib() -> ctypes.CDLL:
-    lib = load()
-    return lib._lib if isinstance(lib, _RecordingLib) else lib
-
-
 @contextlib.contextmanager
 def record_plan(device: torch.device):
-    """Run a step inside this context: it executes as usual, and every library call that enqueues work is noted in
-    the `Plan` the context yields (`plan.run()` issues them again).  The step must be made of library calls only -
-    work enqueued by anything else (a torch operator) is not part of the plan - and must not allocate device
-    memory outside a pool the caller keeps (see `Runner._call_with_plans`)."""
-    global _lib
-    real = load()
-    if isinstance(real, _RecordingLib):
+    """Run a step inside this context: it executes as usual, and every library call that the calling host thread
+    puts on a stream (`_launch`) is noted in the `Plan` the context yields (`plan.run()` issues them again).  Other
+    threads' calls are not, so threads that drive different devices record their plans at the same time.  The step
+    must be made of library calls only - work enqueued by anything else (a torch operator) is not part of the plan -
+    and must not allocate device memory outside a pool the caller keeps (see `Runner._call_with_plans`)."""
+    if _recording.plan is not None:
         raise RuntimeError("record_plan: already recording")
-    plan = Plan(device)
-    _lib = _RecordingLib(real, plan)  # type: ignore[assignment]
+    plan = _recording.plan = Plan(device)
     try:
         yield plan
     finally:
-        _lib = real
+        _recording.plan = None

@@ -6,9 +6,9 @@ finishing before the forward starts, which is not what an un-profiled step does)
     python3 profiles/step_timeline.py c2        # BASELINE configs[1] training step (SGD)
     python3 profiles/step_timeline.py c2adam
 
-Every library call that enqueues work is bracketed by a pair of events on the stream it is issued to (the calls are
-wrapped at the ctypes boundary, as `record_plan` does); offsets are relative to an event recorded on the main
-stream just before the step.  An event pair brackets a CALL: a call of several launches shows as one line."""
+Every library call that enqueues work is bracketed by a pair of events on the stream it is issued to (the library's
+kernel timing with every entry point timed: `_native.kernel_timing_log`); offsets are relative to an event recorded on
+the main stream just before the step.  An event pair brackets a CALL: a call of several launches shows as one line."""
 import os
 import sys
 
@@ -23,30 +23,6 @@ from besskge import runtime  # noqa: E402
 from besskge.collectives import SingleProcessGroup  # noqa: E402
 
 
-class EventLib:
-    """The loaded library with an event pair around every call whose last argument is a stream."""
-
-    def __init__(self, lib):
-        self._lib, self.rec, self.on = lib, [], False
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        sig = nat.SIGNATURES.get(name)
-        if not self.on or sig is None or not sig or sig[-1] is not nat._vp or not self._lib.bess_plan_knows(name.encode()):
-            return fn
-
-        def call(*args):
-            st = torch.cuda.current_stream()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(st)
-            rc = fn(*args)
-            b.record(st)
-            self.rec.append((name, st.cuda_stream, a, b))
-            return rc
-
-        return call
-
-
 def main(workload: str) -> None:
     dev = torch.device("cuda", 0)
     model, sharding, k_pair = bench.build_c2(bench.N_ENTITY_C2, 1, 0, dev, SingleProcessGroup(1), False)
@@ -55,23 +31,19 @@ def main(workload: str) -> None:
     for i in range(6):
         model.train_step_replicas([batches[i % 4]], opt)
     torch.cuda.synchronize()
-    proxy = EventLib(nat.load())
-    nat._lib = proxy
-    try:
-        best = None
-        for i in range(5):
-            proxy.rec, proxy.on = [], True
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            model.train_step_replicas([batches[i % 4]], opt)
-            e1.record()
-            torch.cuda.synchronize()
-            proxy.on = False
-            span = e0.elapsed_time(e1) * 1e3
-            if best is None or span < best[0]:
-                best = (span, e0, list(proxy.rec))
-    finally:
-        nat._lib = proxy._lib
+    best = None
+    for i in range(5):
+        nat.start_kernel_timing(nat.SIGNATURES)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        model.train_step_replicas([batches[i % 4]], opt)
+        e1.record()
+        torch.cuda.synchronize()
+        rec = nat.kernel_timing_log()
+        nat.stop_kernel_timing()
+        span = e0.elapsed_time(e1) * 1e3
+        if best is None or span < best[0]:
+            best = (span, e0, rec)
     span, e0, rec = best
     main_stream = torch.cuda.current_stream().cuda_stream
     rows = sorted(((e0.elapsed_time(a) * 1e3, a.elapsed_time(b) * 1e3, st, name) for name, st, a, b in rec))

@@ -165,6 +165,59 @@ def test_a_step_with_work_outside_the_library_is_refused(dev):
     assert torch.equal(model.score_fn.entity_embedding.detach(), before)  # the failed recording left the tables alone
 
 
+def test_threads_record_their_own_plans_at_the_same_time(dev):
+    """A recording belongs to the host thread that opened it (what `MultiDeviceRunner` needs: one thread per device):
+    two threads recording at the same time each get exactly their own calls, and each replay reproduces its own
+    thread's outputs."""
+    import threading
+
+    from besskge import _native as nat
+
+    torch.manual_seed(0)
+    table = torch.randn(1000, 64, device=dev)
+    barrier = threading.Barrier(2, timeout=120)
+    got, errors = {}, []
+
+    def record(r):
+        try:
+            torch.cuda.set_device(dev)
+            n = 96 + 64 * r
+            idx = torch.randint(0, 1000, (n,), dtype=torch.int32, device=dev)
+            out = torch.empty((n, 64), device=dev)
+            dst = torch.zeros((1000, 64), device=dev)
+            torch.cuda.synchronize()
+            with nat.record_plan(dev) as plan:
+                barrier.wait()  # both recordings are open from here on
+                for _ in range(r + 1):
+                    nat.gather_rows(table, idx, out)
+                barrier.wait()
+                nat.scatter_add_rows(dst, idx, out, 0.5)
+                barrier.wait()
+            torch.cuda.synchronize()
+            want = (out.clone(), dst.clone())
+            out.zero_()
+            dst.zero_()
+            plan.run()
+            torch.cuda.synchronize()
+            got[r] = (list(plan.names), len(plan), want, (out.clone(), dst.clone()))
+        except BaseException as e:  # (re-raised by the test below)
+            errors.append(e)
+            barrier.abort()
+
+    threads = [threading.Thread(target=record, args=(r,)) for r in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for r in range(2):
+        names, length, want, replayed = got[r]
+        assert names == ["bess_gather_rows"] * (r + 1) + ["bess_scatter_add_rows"], (r, names)
+        assert length == len(names)
+        assert torch.equal(replayed[0], want[0])
+        torch.testing.assert_close(replayed[1], want[1], rtol=1e-6, atol=1e-6)
+
+
 _NATIVE_PLAN = r"""
 import sys, torch
 sys.path[:0] = [sys.argv[1], sys.argv[2], sys.argv[3]]
