@@ -180,6 +180,7 @@ SIGNATURES = {
     "bess_coalesced_update_axpy": [ctypes.POINTER(OptDesc), _i32, _i32, _vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(_i64),
                                    _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp],
     "bess_neg_pertriple_items": [_MD, _i64, _i64, ctypes.POINTER(ctypes.c_int32)],
+    "bess_neg_pertriple_sweep": [_MD, _i64, _i64, ctypes.POINTER(ctypes.c_int32)],
     "bess_neg_score_pertriple_fwd_dq": [_MD, _LD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
     "bess_neg_score_pertriple_fwd_dq_masked": [_MD, _LD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp,
                                                _vp, _vp, _vp],
@@ -443,6 +444,25 @@ def copy_desc(d: ModelDesc) -> ModelDesc:
     return c
 
 
+def with_row_count(d: ModelDesc, base: torch.Tensor) -> ModelDesc:
+    """TransE / RotatE / DistMult / ComplEx: a copy of `d` with desc.reserved[1] = the rows of `base` (the table the
+    negative ids index), which lets bess_neg_score_pertriple_fwd score tables whose rows recur in row order
+    (bess_neg_pertriple_sweep).  Other scorers use reserved[1] for their own settings: `d` as it is."""
+    if d.scorer > COMPLEX:
+        return d
+    c = copy_desc(d)
+    rows = int(base.shape[0])
+    c.reserved[1] = rows if rows < (1 << 31) else 0
+    return c
+
+
+def pertriple_sweep(d: ModelDesc, n_query: int, n_neg: int) -> bool:
+    """Whether bess_neg_score_pertriple_fwd takes the row-ordered kernel for these sizes (host arithmetic)."""
+    out = ctypes.c_int32(0)
+    _check(load().bess_neg_pertriple_sweep(ctypes.byref(d), n_query, n_neg, ctypes.byref(out)), "bess_neg_pertriple_sweep")
+    return bool(out.value)
+
+
 def make_desc(scorer: int, norm_p: int, table: torch.Tensor, rel_width: int) -> ModelDesc:
     d = ModelDesc()
     d.scorer = scorer
@@ -648,6 +668,7 @@ def neg_score_pertriple_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, n
     if tuple(out.shape) != (nq, n_neg):
         raise ValueError("neg_score_pertriple_fwd: bad `out` shape")
     ip, keep = _neg_idx_ptr(neg, dev)
+    d = with_row_count(d, neg.base)
     _launch("bess_neg_score_pertriple_fwd", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), ip, n_neg,
             out.data_ptr(), n_neg)
     del keep

@@ -39,6 +39,7 @@ struct NegPtArgs {
     int accum = 0;  // forward: add to the scores already there (a later column window of a wide row)
     float p = 2.f;  // the norm of the RED_L2 kernels (any p != 1)
     int dn_by_row = 0;  // backward: d_neg row of reference k is neg_idx[k] (BESS_FLAG_DNEG_BY_ROW), not q * n_neg + k
+    int sweep_shift = -1;  // plain forward: >= 0 takes k_neg_pertriple_fwd_sweep, row buckets of 1 << sweep_shift rows
 };
 
 // Fused training forward (FUSE): besides the scores, accumulate the loss gradient wrt the query,
@@ -193,6 +194,243 @@ __global__ __launch_bounds__(256) void k_neg_pertriple_fwd(NegPtArgs a, float* _
                 x += __shfl_xor(x, 32, 64);
                 if (sub == 0 && c < a.nch) ap[c * VEC + v] = x;
             }
+        }
+    }
+}
+
+// ---- K5s: the plain forward in row order, for tables whose rows are each scored many times --------------------
+//
+// k_neg_pertriple_fwd reads n_query * n_neg random rows; with more pairs than table rows (C2: 1 M pairs over 93,773
+// rows, each row ~11 times) nearly every read still comes from the Infinity Cache: a row's uses arrive from waves on
+// all eight XCDs at random times, and one XCD's 4 MiB L2 holds 2 % of a 192 MB table.  This kernel scores the same
+// pairs in an order that keeps a row's uses on one XCD and close together in time:
+//
+// - a query block (up to 32 queries x a chunk of their negatives, <= SW_PMAX pairs) is served by eight workgroups, labels
+//   l = blockIdx.x % 8 (blocks b and b + 8 share an XCD under the observed round-robin placement: a speed hint only);
+// - each of the eight reads the block's indices, builds the same histogram over coarse row buckets in LDS and takes
+//   the l-th eighth of the block's pairs in (bucket, position) order - identical data, identical split, no
+//   communication: every pair is scored exactly once wherever the blocks run, and with skewed indices (one hot row)
+//   every label still gets 1/8 of the pairs.  Only the (at most two) buckets cut by the share's ends need the
+//   position order (ballot ranks); the pairs of the other buckets take slots by LDS atomics;
+// - the share (<= SW_PMAX / 8 pairs, bucket-sorted in LDS) is dealt to the 16-lane groups front to back in runs of
+//   4 * UNROLL per wave: the workgroup walks its row range in order, and all workgroups of an XCD walk about the same
+//   range in step (no inter-workgroup synchronisation);
+// - the block's queries are staged in LDS in the chunk layout of the registers of k_neg_pertriple_fwd (16 lanes read
+//   256 contiguous bytes per ds_read_b128: conflict-free without padding); a group's pairs belong to any query.
+//
+// Per pair the arithmetic is that of k_neg_pertriple_fwd in the same order (chunks g + 16 it, the same fmaf / fabsf /
+// lp_term sequence, row16_allreduce_sum, lp_root, sign): the scores are bitwise equal.  Plain forward only (no fused
+// loss, one column window, no accumulation); run() takes it when the caller gives the table's row count.
+constexpr int SW_NB = 1024;                 // row buckets of the histogram
+constexpr int SW_PMAX = 8192;               // pairs of one block chunk: qb queries x up to SW_PMAX / qb negatives
+constexpr int SW_PPT = SW_PMAX / 256;       // pairs per thread while sorting
+constexpr int SW_SHARE = SW_PMAX / 8;       // entries of one label's share
+constexpr int SW_QFLOATS = 16384;           // LDS for the staged queries (64 KiB): qb = min(32, this / row stride)
+constexpr int64_t SW_REUSE_MIN = 4;         // pairs per table row from which run() takes the sweep
+
+struct SweepArgs {
+    int qb;        // queries per block
+    int kc;        // negatives per block chunk
+    int n_kchunks;
+    int shift;     // bucket of row r: min(r >> shift, SW_NB - 1)
+    int qstride;   // floats per staged query (IT * 16 * VEC)
+};
+
+template <typename T, int VEC, int IT, int RED, int UNROLL>
+__global__ __launch_bounds__(256) void k_neg_pertriple_fwd_sweep(NegPtArgs a, SweepArgs s, float* __restrict__ out,
+                                                                 int64_t ld_out) {
+    // (static arrays of whole 16-B units: the dynamic region after them stays 16-B aligned)
+    extern __shared__ __attribute__((aligned(16))) float qs[];  // [qb][IT * 16 chunks][VEC]
+    __shared__ int hist[SW_NB + 4];  // counts, then bucket starts (hist[SW_NB] = P), then slot cursors
+    __shared__ int2 ent[SW_SHARE];  // (row, qi << 16 | k - kc0)
+    __shared__ int rk[2][SW_PPT * 4];
+    __shared__ int wsum[4];
+    __shared__ int cut[4];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int label = blockIdx.x & 7;
+    const int bc = blockIdx.x >> 3;
+    const int qblk = bc / s.n_kchunks;
+    const int kch = bc - qblk * s.n_kchunks;
+    const int64_t q0 = static_cast<int64_t>(qblk) * s.qb;
+    const int nqb = static_cast<int>(min(static_cast<int64_t>(s.qb), a.n_query - q0));
+    const int kc0 = kch * s.kc;
+    const int kcn = min(s.kc, a.n_neg - kc0);
+    const int P = nqb * kcn;
+    const int lo = static_cast<int>((static_cast<int64_t>(label) * P) >> 3);
+    const int hi = static_cast<int>((static_cast<int64_t>(label + 1) * P) >> 3);
+
+    // queries -> LDS (zeros past the row's end, as load_chunk gives the registers of k_neg_pertriple_fwd)
+    for (int i = tid; i < nqb * IT * 16; i += 256) {
+        const int qi = i / (IT * 16);
+        const int c = i - qi * (IT * 16);
+        float v[VEC];
+        load_chunk<float, VEC>(a.query + (q0 + qi) * a.W, c, a.nch, v);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) qs[qi * s.qstride + c * VEC + j] = v[j];
+    }
+    for (int b = tid; b < SW_NB; b += 256) hist[b] = 0;
+    if (tid < 2) cut[tid] = -1;
+    // the block's row ids: pair p = qi * kcn + kk, thread tid holds p = tid + 256 j
+    int rr[SW_PPT];
+#pragma unroll
+    for (int j = 0; j < SW_PPT; ++j) {
+        const int p = tid + 256 * j;
+        rr[j] = 0;
+        if (p < P) {
+            const int qi = p / kcn;
+            rr[j] = a.idx[(q0 + qi) * a.n_neg + kc0 + (p - qi * kcn)];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < SW_PPT; ++j)
+        if (tid + 256 * j < P) atomicAdd(&hist[min(static_cast<unsigned>(rr[j]) >> s.shift, SW_NB - 1u)], 1);
+    __syncthreads();
+
+    // exclusive scan of the counts (4 buckets per thread); note the buckets that the share's ends cut
+    {
+        int c[4], sum = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            c[i] = hist[4 * tid + i];
+            sum += c[i];
+        }
+        int incl = sum;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int y = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += y;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        int run = incl - sum;
+        for (int w = 0; w < wave; ++w) run += wsum[w];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b = 4 * tid + i;
+            hist[b] = run;
+            if (run < lo && lo < run + c[i]) cut[0] = b;
+            if (run < hi && hi < run + c[i]) cut[1] = b;
+            run += c[i];
+        }
+        if (tid == 255) hist[SW_NB] = run;
+    }
+    __syncthreads();
+
+    // ranks in position order inside the cut buckets: per (j, wave) counts, scanned by wave 0
+    const int cut0 = cut[0], cut1 = cut[1];
+    const uint64_t lt = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < SW_PPT; ++j) {
+        const bool live = tid + 256 * j < P;
+        const unsigned b = min(static_cast<unsigned>(rr[j]) >> s.shift, SW_NB - 1u);
+        const uint64_t m0 = __ballot(live && static_cast<int>(b) == cut0);
+        const uint64_t m1 = __ballot(live && static_cast<int>(b) == cut1);
+        if (lane == 0) {
+            rk[0][j * 4 + wave] = __popcll(m0);
+            rk[1][j * 4 + wave] = __popcll(m1);
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int x0 = rk[h][2 * lane], x1 = rk[h][2 * lane + 1];
+            int incl = x0 + x1;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int y = __shfl_up(incl, off, 64);
+                if (lane >= off) incl += y;
+            }
+            rk[h][2 * lane] = incl - x0 - x1;
+            rk[h][2 * lane + 1] = incl - x1;
+        }
+    }
+    __syncthreads();
+
+    // slot of each pair in the share: >= 0 fixed (cut buckets), -2 by atomic (whole bucket inside), -1 not ours
+    int slot[SW_PPT];
+#pragma unroll
+    for (int j = 0; j < SW_PPT; ++j) {
+        const bool live = tid + 256 * j < P;
+        const unsigned b = min(static_cast<unsigned>(rr[j]) >> s.shift, SW_NB - 1u);
+        const bool in0 = live && static_cast<int>(b) == cut0;
+        const bool in1 = live && static_cast<int>(b) == cut1 && !in0;
+        const uint64_t m0 = __ballot(in0);
+        const uint64_t m1 = __ballot(in1);
+        const int b0 = live ? hist[b] : 0, b1 = live ? hist[b + 1] : 0;
+        slot[j] = -1;
+        if (live) {
+            if (in0 || in1) {
+                const int r = in0 ? rk[0][j * 4 + wave] + __popcll(m0 & lt) : rk[1][j * 4 + wave] + __popcll(m1 & lt);
+                const int pos = b0 + r;
+                if (pos >= lo && pos < hi) slot[j] = pos - lo;
+            } else if (b0 >= lo && b1 <= hi) {
+                slot[j] = -2;
+            }
+        }
+    }
+    __syncthreads();  // hist[] is now the slot cursor of the buckets inside the share
+#pragma unroll
+    for (int j = 0; j < SW_PPT; ++j) {
+        const int p = tid + 256 * j;
+        if (slot[j] == -1) continue;
+        const unsigned b = min(static_cast<unsigned>(rr[j]) >> s.shift, SW_NB - 1u);
+        const int e = slot[j] >= 0 ? slot[j] : atomicAdd(&hist[b], 1) - lo;
+        const int qi = p / kcn;
+        ent[e] = make_int2(rr[j], (qi << 16) | (p - qi * kcn));
+    }
+    __syncthreads();
+
+    // the sweep: 16-lane group `sub` of wave `wave` scores entries it * 16 * UNROLL + wave * 4 * UNROLL + sub + 4 u
+    const int n = hi - lo;
+    const int g = lane & 15;
+    const int sub = lane >> 4;
+    const T* base = static_cast<const T*>(a.base);
+    int2 nx[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) nx[u] = ent[max(0, min(wave * 4 * UNROLL + sub + 4 * u, n - 1))];
+    for (int e0 = wave * 4 * UNROLL; e0 < n; e0 += 16 * UNROLL) {  // wave-uniform
+        float ev[UNROLL][IT][VEC];
+        int2 cur[UNROLL];
+        bool valid[UNROLL];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int e = e0 + sub + 4 * u;
+            valid[u] = e < n;
+            cur[u] = nx[u];
+            const T* rp = base + static_cast<int64_t>(cur[u].x) * a.W;  // clamped entry: keeps the wave converged
+            nx[u] = ent[min(e + 16 * UNROLL, n - 1)];
+#pragma unroll
+            for (int it = 0; it < IT; ++it) load_chunk<T, VEC>(rp, g + 16 * it, a.nch, ev[u][it]);
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int qi = cur[u].y >> 16;
+            const int kk = cur[u].y & 0xffff;
+            const float* qp = qs + qi * s.qstride;
+            float acc = 0.f;
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                float qv[VEC];
+                VecLoad<float, VEC>::load(qp + (g + 16 * it) * VEC, qv);
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    if (RED == RED_DOT) {
+                        acc = fmaf(qv[v], ev[u][it][v], acc);
+                    } else if (RED == RED_L1) {
+                        acc += fabsf(qv[v] - ev[u][it][v]);
+                    } else {
+                        acc += lp_term(qv[v] - ev[u][it][v], a.p);
+                    }
+                }
+            }
+            acc = row16_allreduce_sum(acc);
+            if (RED == RED_L2) acc = lp_root(acc, a.p);
+            if (g == 0 && valid[u]) out[(q0 + qi) * ld_out + kc0 + kk] = a.sign * acc;
         }
     }
 }
@@ -357,7 +595,18 @@ static void launch_fwd(const NegPtArgs& a, float* out, int64_t ld, const FuseArg
     const int64_t items = a.n_query * a.items_per_query;
     constexpr int EPL = IT * VEC;  // scalars per lane per row
     constexpr int UNROLL = EPL <= 16 ? 4 : (EPL <= 32 ? 2 : 1);
-    if (fuse) {
+    if (!fuse && a.sweep_shift >= 0) {
+        SweepArgs s;
+        s.qstride = IT * 16 * VEC;
+        s.qb = SW_QFLOATS / s.qstride < 32 ? SW_QFLOATS / s.qstride : 32;
+        s.kc = a.n_neg < SW_PMAX / s.qb ? a.n_neg : SW_PMAX / s.qb;
+        s.n_kchunks = static_cast<int>(ceil_div(a.n_neg, s.kc));
+        s.shift = a.sweep_shift;
+        const int64_t blocks = ceil_div(a.n_query, s.qb) * s.n_kchunks * 8;
+        const int lds = s.qb * s.qstride * static_cast<int>(sizeof(float));  // <= 64 KiB (+ 13 KiB static)
+        k_neg_pertriple_fwd_sweep<T, VEC, IT, RED, UNROLL>
+            <<<static_cast<unsigned>(blocks), 256, lds, st>>>(a, s, out, ld);
+    } else if (fuse) {
         constexpr int FU = EPL <= 16 ? 2 : 1;  // the running d_query sum takes EPL more registers
         k_neg_pertriple_fwd<T, VEC, IT, RED, FU, true><<<ceil_div(items, 4), 256, 0, st>>>(a, out, ld, *fuse);
     } else {
@@ -413,6 +662,27 @@ static int negatives_per_item(int64_t n_query, int64_t n_neg, int64_t row_bytes)
     return nb;
 }
 
+// scalars per lane load: the widest vector that divides the row (f32 {4,1}, f16 {8,2,1})
+static int vec_of(const bess_model_desc* d) {
+    const int maxvec = d->dtype == BESS_F32 ? 4 : 8;
+    if (d->width % maxvec == 0) return maxvec;
+    return (d->dtype == BESS_F16 && d->width % 2 == 0) ? 2 : 1;
+}
+
+// Row-ordered plain forward (k_neg_pertriple_fwd_sweep)?  Only where the caller gave the table's row count
+// (desc.reserved[1]; 0 = unknown) and each row is scored at least SW_REUSE_MIN times on average: a list that names
+// each row about once (a receive buffer, a table far larger than the pairs) gains nothing from the order.  One column
+// window only.  Returns the bucket shift (row buckets of 1 << shift rows, at most SW_NB of them), or -1.
+static int sweep_shift_for(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
+    if (d->scorer > BESS_COMPLEX || d->width > 16 * 16 * vec_of(d)) return -1;
+    const int64_t rows = d->reserved[1];
+    if (rows <= 0 || n_query <= 0 || n_neg <= 0 || n_query * n_neg < SW_REUSE_MIN * rows) return -1;
+    if (ceil_div(n_query, 8) * ceil_div(n_neg, 256) * 8 >= (1ll << 31)) return -1;  // grid: >= 8 queries x 256 per block
+    int shift = 0;
+    while (((rows - 1) >> shift) >= SW_NB) ++shift;
+    return shift;
+}
+
 static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n_query,
                const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* out,
                const float* d_out, int64_t ld, float* dq, float* dn, void* stream,
@@ -430,10 +700,7 @@ static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n
         return affine_pertriple(d, fwd, query, n_query, neg_base, neg_idx, n_neg, out, d_out, ld, dq, dn,
                                 as_stream(stream));
     const int W = d->width;
-    const int maxvec = d->dtype == BESS_F32 ? 4 : 8;
-    // widest vector that divides the row: f32 {4,1}, f16 {8,2,1} scalars per lane load
-    int vec = maxvec;
-    if (W % vec) vec = (d->dtype == BESS_F16 && W % 2 == 0) ? 2 : 1;
+    const int vec = vec_of(d);
     NegPtArgs a;
     a.query = query;
     a.base = neg_base;
@@ -449,6 +716,7 @@ static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n
     a.sign = is_distance(d->scorer) ? -1.f : 1.f;
     a.p = static_cast<float>(d->norm_p);
     a.dn_by_row = (!fwd && (d->reserved[0] & BESS_FLAG_DNEG_BY_ROW)) ? 1 : 0;
+    if (fwd && !fuse) a.sweep_shift = sweep_shift_for(d, n_query, n_neg);
     const int red = reduce_of(d);
     hipStream_t st = as_stream(stream);
     if (!fwd && a.items_per_query > 1 && dq) {
@@ -515,6 +783,13 @@ extern "C" int bess_neg_score_pertriple_bwd(const bess_model_desc* d, const floa
     // ComplEx then never read the candidate rows)
     return bess::run(d, false, query, n_query, neg_base, neg_idx, n_neg, nullptr, d_out, ld_dout,
                      d_query, d_neg, stream);
+}
+
+extern "C" int bess_neg_pertriple_sweep(const bess_model_desc* d, int64_t n_query, int64_t n_neg, int32_t* sweep) {
+    if (int e = bess::check_desc(d)) return e;
+    if (!sweep || n_query < 0 || n_neg < 0) return bess::fail(BESS_EINVAL, "neg_pertriple_sweep: bad argument");
+    *sweep = bess::sweep_shift_for(d, n_query, n_neg) >= 0 ? 1 : 0;
+    return BESS_OK;
 }
 
 static int64_t row_bytes_of(const bess_model_desc* d) {

@@ -100,6 +100,8 @@ extern "C" {
 #define BESS_FLAG_FP32_MATH 1 /* shared negatives with the plain fp32 kernels only: no packed-fp16 L1 forward
                                  (TransE / RotatE on f16 tables), no split-fp16 matrix-core products (DistMult /
                                  ComplEx) */
+/* bess_model_desc.reserved[1] of TransE / RotatE / DistMult / ComplEx: the row count of the table that
+ * bess_neg_score_pertriple_fwd's neg_base / neg_idx name (0 = unknown), see bess_neg_pertriple_sweep */
 
 typedef struct bess_model_desc {
     int32_t scorer;    /* BESS_TRANSE ...                                  */
@@ -224,6 +226,12 @@ int bess_neg_score_pertriple_fwd(const bess_model_desc* d, const float* query,
                                  int64_t n_query, const void* neg_base,
                                  const int32_t* neg_idx, int64_t n_neg, float* out,
                                  int64_t ld_out, void* stream);
+/* Host arithmetic, no GPU: *sweep = 1 when bess_neg_score_pertriple_fwd scores n_query x n_neg pairs with its
+ * row-ordered kernel (csrc/neg_pertriple.hip, K5s: a query block's pairs are split over eight workgroups by row and
+ * swept in row order, so that a row's repeated reads hit one XCD's L2), else 0.  It does when desc.reserved[1]
+ * holds the row count of neg_base (0 = unknown) and n_query * n_neg >= 4 x that count, for rows of one column
+ * window.  The scores are the same, bit for bit, either way. */
+int bess_neg_pertriple_sweep(const bess_model_desc* d, int64_t n_query, int64_t n_neg, int32_t* sweep);
 
 /* backward of K5.  d_out read with ld_dout.  d_query [n_query, W] f32 is
  * overwritten; d_neg [n_query*n_neg, W] f32 (gradient w.r.t. every gathered
