@@ -34,7 +34,8 @@ _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _RETURNS_I64 = ("bess_neg_score_shared_workspace", "bess_neg_score_shared_bwd_workspace",
-                "bess_neg_score_shared_fwd_counts_workspace", "bess_neg_score_shared_fwd_pairs_workspace")  # every other entry returns an int status
+                "bess_neg_score_shared_fwd_counts_workspace", "bess_neg_score_shared_fwd_pairs_workspace",
+                "bess_neg_score_table_fwd_counts_workspace", "bess_neg_score_table_fwd_pairs_workspace")  # every other entry returns an int status
 _i32 = ctypes.c_int32
 _f32 = ctypes.c_float
 
@@ -145,6 +146,10 @@ SIGNATURES = {
     "bess_neg_score_shared_fwd_counts": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
     "bess_neg_score_shared_fwd_pairs_workspace": [_MD, _i64, _i64],
     "bess_neg_score_shared_fwd_pairs": [_MD, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
+    "bess_neg_score_table_fwd_counts_workspace": [_MD, _i64, _i64],
+    "bess_neg_score_table_fwd_counts": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
+    "bess_neg_score_table_fwd_pairs_workspace": [_MD, _i64, _i64],
+    "bess_neg_score_table_fwd_pairs": [_MD, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
     "bess_topk_update_flagged": [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
     "bess_neg_score_shared_fwd_masked": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(KillDesc), _vp, _i64, _vp],
     "bess_neg_score_shared_bwd": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
@@ -224,6 +229,7 @@ SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
 }
 COMM_ID_BYTES = 128
+AFFINE_COUNT_CHUNK_BYTES = 32 << 20  # BESS_AFFINE_COUNT_CHUNK_BYTES
 TICKET_INTS = 544  # BESS_TICKET_INTS
 ECOMM_BASE = 10000
 
@@ -857,6 +863,14 @@ def normalize_rows_bwd(hat: torch.Tensor, inv: torch.Tensor, d_hat: torch.Tensor
     return out
 
 
+def affine_count_chunk_rows(d: ModelDesc) -> int:
+    """Candidate rows per launch of the affine scorers' counting pass (`bess_neg_score_table_fwd_counts`):
+    `AFFINE_COUNT_CHUNK_BYTES` of table rows, in whole 64-row tiles, at least one.  Its workspace is the inverse part
+    norms of one chunk: at most this many rows x n_part floats, whatever the number of queries."""
+    row_bytes = int(d.width) * (4 if d.dtype == F32 else 2)
+    return max(64, AFFINE_COUNT_CHUNK_BYTES // row_bytes // 64 * 64)
+
+
 def _affine_candidates(d: ModelDesc, neg: RowSource) -> Tuple[RowSource, torch.Tensor, torch.Tensor]:
     """The shared kernels of the affine scorers work on dense, normalised f32 candidates."""
     hat, inv = normalize_rows(neg, int(d.reserved[0]), bool(d.reserved[1] & 1))
@@ -931,8 +945,8 @@ def neg_score_shared_fwd_pruned(d: ModelDesc, query: torch.Tensor, neg: RowSourc
 def neg_score_shared_pairs(d: ModelDesc, query: torch.Tensor, neg: RowSource, like_n_query: int,
                            like_n_neg: int) -> torch.Tensor:
     """out[i] = score(query[i], candidate i of `neg`) in the arithmetic of the all-entity pass over a
-    (like_n_query x like_n_neg) problem (`bess_neg_score_shared_fwd_pairs`): what `neg_score_shared_counts` compares
-    against, to the last bit."""
+    (like_n_query x like_n_neg) problem (`bess_neg_score_table_fwd_pairs`: `neg` names rows of the entity table for
+    every scorer): what `neg_score_shared_counts` compares against, to the last bit."""
     n = int(query.shape[0])
     if len(neg) != n or neg.idx is None:
         raise ValueError("neg_score_shared_pairs: one indexed candidate per query")
@@ -941,17 +955,19 @@ def neg_score_shared_pairs(d: ModelDesc, query: torch.Tensor, neg: RowSource, li
     if n == 0:
         return out
     lib = load()
-    ws_bytes = int(lib.bess_neg_score_shared_fwd_pairs_workspace(ctypes.byref(d), int(like_n_query), int(like_n_neg)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    _launch("bess_neg_score_shared_fwd_pairs", dev, ctypes.byref(d), query.data_ptr(), neg.base.data_ptr(),
-            _idx(neg.idx, "negative idx"), n, int(like_n_query), int(like_n_neg), out.data_ptr(), ws.data_ptr(), ws_bytes)
+    ws_bytes = int(lib.bess_neg_score_table_fwd_pairs_workspace(ctypes.byref(d), int(like_n_query), int(like_n_neg)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    _launch("bess_neg_score_table_fwd_pairs", dev, ctypes.byref(d), query.data_ptr(), neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n, int(like_n_query), int(like_n_neg), out.data_ptr(),
+            ws.data_ptr() if ws is not None else None, ws_bytes)
     return out
 
 
 def neg_score_shared_counts(d: ModelDesc, query: torch.Tensor, neg: RowSource, thr: torch.Tensor,
                             excl: torch.Tensor, counts: Optional[torch.Tensor] = None,
                             round_f16: bool = False) -> torch.Tensor:
-    """Ranks without the score matrix (`bess_neg_score_shared_fwd_counts`): adds to `counts` [nq, 2] int32 (made
+    """Ranks without the score matrix (`bess_neg_score_table_fwd_counts`; `neg`: rows of the entity table for every
+    scorer - the affine family's are normalised as the kernel stages them): adds to `counts` [nq, 2] int32 (made
     and cleared when None) the number of candidates scoring above / exactly `thr[q]` (f32 [nq]: the score of the
     row's true completion), leaving out candidate `excl[q]` (int32 [nq]: its position in `neg`, -1: not among
     them).  `round_f16`: scores are rounded to fp16 before they are compared (the ranking of a half-precision
@@ -969,12 +985,10 @@ def neg_score_shared_counts(d: ModelDesc, query: torch.Tensor, neg: RowSource, t
         counts = torch.zeros((nq, 2), dtype=torch.int32, device=dev)
     elif tuple(counts.shape) != (nq, 2) or counts.dtype != torch.int32 or not counts.is_contiguous():
         raise ValueError("neg_score_shared_counts: counts must be a contiguous [nq, 2] int32 tensor")
-    if d.scorer == AFFINE:
-        neg, _, _ = _affine_candidates(d, neg)
     lib = load()
-    ws_bytes = int(lib.bess_neg_score_shared_fwd_counts_workspace(ctypes.byref(d), nq, n_neg))
+    ws_bytes = int(lib.bess_neg_score_table_fwd_counts_workspace(ctypes.byref(d), nq, n_neg))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
-    _launch("bess_neg_score_shared_fwd_counts", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+    _launch("bess_neg_score_table_fwd_counts", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
             _idx(neg.idx, "negative idx"), n_neg, thr.data_ptr(), excl.data_ptr(), counts.data_ptr(),
             int(bool(round_f16)), ws.data_ptr() if ws is not None else None, ws_bytes)
     return counts

@@ -27,9 +27,10 @@ from besskge.utils import get_entity_filter
 
 
 def _counting_scorer(score_fn: BaseScoreFunction) -> bool:
-    """TransE / RotatE / DistMult / ComplEx: the scorers whose all-entity kernels can count ranks."""
+    """Every scorer with a kernel descriptor: their all-entity kernels count ranks in their epilogues (TransE /
+    RotatE / DistMult / ComplEx - ConvE rides DistMult's -, the affine family's tile kernel, BoxE's)."""
     try:
-        return int(score_fn.kernel_desc().scorer) <= nat.COMPLEX
+        return nat.TRANSE <= int(score_fn.kernel_desc().scorer) <= nat.BOXE
     except (AttributeError, NotImplementedError, ValueError):
         return False
 
@@ -130,7 +131,9 @@ class AllScoresPipeline(torch.nn.Module):
             and the filtered completions' scores are taken in that kernel's arithmetic too:
             `bess_neg_score_shared_fwd_pairs`); where `window_size` makes the matrix path take another
             kernel (the split-fp16 product needs 256 output tiles) ranks may differ by one at scores that
-            agree to a rounding error.
+            agree to a rounding error.  Every scorer of `besskge.scoring` takes this path (PairRE / TripleRE /
+            InterHT / TranS and BoxE run one per-element arithmetic whatever the window: the same ranks for
+            any `window_size`); `fused_ranks=False` forces the matrix path.
         """
         super().__init__()
         if not (evaluation or return_scores):

@@ -19,7 +19,9 @@
 //     the norm of each part is one more DPP reduction over registers.
 //   shared (VALU bound): 64 x 64 LDS tile kernel over *dense fp32, already
 //     normalised* candidates (bess_normalize_rows gathers + converts + normalises the
-//     N candidate rows first; its backward maps the gradient back).
+//     N candidate rows first; its backward maps the gradient back).  Rank counting and single pairs run the
+//     same tile kernel on the raw table rows, scaled by their inverse norms as they are staged, with a
+//     counting epilogue / on the diagonal tiles (affine_table_fwd): no score and no normalised copy is stored.
 #include <algorithm>
 #include <string.h>
 
@@ -31,7 +33,9 @@ constexpr float NORM_EPS = 1e-12f;  // torch.nn.functional.normalize default
 
 // ---------------------------------------------------------------------------
 // normalise rows: out[i, p*d + w] = e[i, p*d + w] / max(||e[i, p*d : (p+1)*d]||, eps)
-// one wave per row
+// one wave per row.  out == NULL: the inverse norms only - the tile kernel on raw table rows (k_aff_shared_fwd,
+// RAW) multiplies by them while it stages; s comes from this code in both forms, so its to_f32(x) * s is the
+// `hat` stored here, bit for bit.
 template <typename T>
 __global__ __launch_bounds__(256) void k_normalize_rows(const T* __restrict__ base, const int32_t* __restrict__ idx,
                                                         int64_t n, int d, int n_part, int normalize,
@@ -53,7 +57,8 @@ __global__ __launch_bounds__(256) void k_normalize_rows(const T* __restrict__ ba
             ss = wave_allreduce_sum(ss);
             s = 1.f / fmaxf(sqrtf(ss), NORM_EPS);
         }
-        for (int w = lane; w < d; w += 64) op[p * d + w] = to_f32(rp[p * d + w]) * s;
+        if (out)
+            for (int w = lane; w < d; w += 64) op[p * d + w] = to_f32(rp[p * d + w]) * s;
         if (inv && lane == 0) inv[i * n_part + p] = s;
     }
 }
@@ -826,28 +831,82 @@ __device__ __forceinline__ void aff_stage_store(float (*tile)[AKT][ALDP], const 
         for (int i = 0; i < 4; ++i) tile[p][kc + i][m] = v[p][i];
 }
 
-template <int NPART, int P>
-__global__ __launch_bounds__(256) void k_aff_shared_fwd(const float* __restrict__ Q, int64_t S, const float* __restrict__ C,
-                                                        int64_t N, int d, float* __restrict__ out, int64_t ld_out, float pf) {
+// The same stage from raw table rows (element type TC, gathered through idx): this thread's row pointer `rp`
+// (at its first column kc) and the row's per-part inverse norms s are fixed for the whole K loop.
+template <typename TC, int NV>
+__device__ __forceinline__ void aff_stage_fetch_raw(const TC* __restrict__ rp, const float (&s)[NV], int d, int k0, bool vec,
+                                                    float (&v)[NV][4]) {
+    const int kc = (threadIdx.x & 3) * 4;
+    const bool vec_ok = vec && k0 + kc + 3 < d;
+#pragma unroll
+    for (int p = 0; p < NV; ++p) {
+        if (vec_ok) {
+            VecLoad<TC, 4>::load(rp + p * d + k0, v[p]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[p][i] = (k0 + kc + i < d) ? to_f32(rp[p * d + k0 + i]) : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[p][i] = v[p][i] * s[p];  // = k_normalize_rows' hat
+    }
+}
+
+// candidates of the tile kernel: dense, already normalised f32 rows (RAW == false: idx, inv unused) or rows of the
+// entity table in TC, gathered through idx (NULL: rows 0 .. N-1) and scaled by inv [N, NPART] (NULL: 1) as staged
+template <typename TC>
+struct AffCand {
+    const TC* base;
+    const int32_t* idx;
+    const float* inv;
+    int vec;  // RAW: rows may be read as 4-element vectors (d % 4 == 0, aligned base)
+};
+
+// RAW: see AffCand.  COUNT: the counting epilogue of common.h's CountArgs - a workgroup walks over `tiles`
+// consecutive column tiles and keeps its rows' two counters in registers, so it issues at most one atomic pair per
+// row; out may be NULL.  DIAG: S == N, the workgroup of row tile y computes column tile y only, out [S, 64].
+// <NPART, P, float, false, false, false> is the kernel of the dense forward: the K loop is the same code for all.
+template <int NPART, int P, typename TC, bool RAW, bool COUNT, bool DIAG>
+__global__ __launch_bounds__(256) void k_aff_shared_fwd(const float* __restrict__ Q, int64_t S, AffCand<TC> cand,
+                                                        int64_t N, int d, float* __restrict__ out, int64_t ld_out, float pf,
+                                                        const float* __restrict__ thr, CountArgs cnt, int tiles) {
     __shared__ __attribute__((aligned(16))) float Qs[NPART + 1][AKT][ALDP];
     __shared__ __attribute__((aligned(16))) float Cs[NPART][AKT][ALDP];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int64_t q0 = static_cast<int64_t>(blockIdx.y) * 64, j0 = static_cast<int64_t>(blockIdx.x) * 64;
+    const int64_t q0 = static_cast<int64_t>(blockIdx.y) * 64;
+    int cg[4] = {0, 0, 0, 0}, ce[4] = {0, 0, 0, 0};
+    const int n_tile = COUNT ? tiles : 1;
+    for (int tile = 0; tile < n_tile; ++tile) {
+    const int64_t j0 = DIAG ? q0 : (static_cast<int64_t>(blockIdx.x) * n_tile + tile) * 64;
+    if (COUNT && j0 >= N) break;  // (the same for the whole workgroup)
     float acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
     float qv[NPART + 1][4], cv[NPART][4];
+    // RAW: the row this thread stages and its inverse norms
+    const TC* crow = nullptr;
+    float cs[NPART];
+    if constexpr (RAW) {
+        const int64_t ci = min(j0 + (threadIdx.x >> 2), N - 1);
+        const int64_t r = cand.idx ? static_cast<int64_t>(cand.idx[ci]) : ci;
+        crow = cand.base + r * NPART * d + (threadIdx.x & 3) * 4;
+#pragma unroll
+        for (int p = 0; p < NPART; ++p) cs[p] = cand.inv ? cand.inv[ci * NPART + p] : 1.f;
+    }
+    auto fetch_c = [&](int k0) {
+        if constexpr (RAW) aff_stage_fetch_raw<TC, NPART>(crow, cs, d, k0, cand.vec != 0, cv);
+        else aff_stage_fetch<NPART>(cand.base, N, static_cast<int64_t>(NPART) * d, j0, d, k0, cv);
+    };
     aff_stage_fetch<NPART + 1>(Q, S, static_cast<int64_t>(NPART + 1) * d, q0, d, 0, qv);
-    aff_stage_fetch<NPART>(C, N, static_cast<int64_t>(NPART) * d, j0, d, 0, cv);
+    fetch_c(0);
     for (int k0 = 0; k0 < d; k0 += AKT) {
         aff_stage_store<NPART + 1>(Qs, qv);
         aff_stage_store<NPART>(Cs, cv);
         __syncthreads();
         if (k0 + AKT < d) {
             aff_stage_fetch<NPART + 1>(Q, S, static_cast<int64_t>(NPART + 1) * d, q0, d, k0 + AKT, qv);
-            aff_stage_fetch<NPART>(C, N, static_cast<int64_t>(NPART) * d, j0, d, k0 + AKT, cv);
+            fetch_c(k0 + AKT);
         }
 #pragma unroll
         for (int k = 0; k < AKT; ++k) {
@@ -878,11 +937,42 @@ __global__ __launch_bounds__(256) void k_aff_shared_fwd(const float* __restrict_
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int64_t q = q0 + ty * 4 + i;
-        if (q >= S) continue;
+        if constexpr (COUNT) {
+            // (rows past the end count against the last row's threshold and are dropped at the atomics)
+            const int64_t qc = min(q, S - 1);
+            const float th = thr[qc];
+            const int64_t ex = static_cast<int64_t>(cnt.excl[qc]) - cnt.col0;  // position in this launch's columns
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t jj = j0 + tx * 4 + j;
-            if (jj < N) out[q * ld_out + jj] = -(P == 2 ? lp_root(acc[i][j], pf) : acc[i][j]);
+            for (int j = 0; j < 4; ++j) {
+                const int64_t jj = j0 + tx * 4 + j;
+                const float sc = -(P == 2 ? lp_root(acc[i][j], pf) : acc[i][j]);
+                const float v = count_value(sc, cnt.round16);
+                const bool in = jj < N && jj != ex;
+                cg[i] += (in && v > th) ? 1 : 0;
+                ce[i] += (in && v == th) ? 1 : 0;
+                if (out && q < S && jj < N) out[q * ld_out + jj] = sc;
+            }
+        } else {
+            if (q >= S) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t jj = j0 + tx * 4 + j;
+                if (jj < N) out[q * ld_out + (DIAG ? tx * 4 + j : jj)] = -(P == 2 ? lp_root(acc[i][j], pf) : acc[i][j]);
+            }
+        }
+    }
+    }
+    if constexpr (COUNT) {
+        // the 16 threads that share a ty are the 16 lanes of one DPP row (at most 64 * tiles per counter: exact in f32)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int g = static_cast<int>(row16_allreduce_sum(static_cast<float>(cg[i])));
+            const int e = static_cast<int>(row16_allreduce_sum(static_cast<float>(ce[i])));
+            const int64_t q = q0 + ty * 4 + i;
+            if (tx == 0 && q < S) {
+                if (g) atomicAdd(cnt.counts + 2 * q, g);
+                if (e) atomicAdd(cnt.counts + 2 * q + 1, e);
+            }
         }
     }
 }
@@ -1042,14 +1132,79 @@ int affine_shared_fwd(const bess_model_desc* d, const float* query, int64_t S, c
     const int dd = d->width / n_part;
     const float pf = static_cast<float>(d->norm_p);
     const dim3 grid(static_cast<unsigned>(ceil_div(N, 64)), static_cast<unsigned>(ceil_div(S, 64)));
+    const AffCand<float> C{cand, nullptr, nullptr, 0};
+    const CountArgs none{nullptr, nullptr, 0, 0};
+#define BESS_AFF_FWD(NP, PP) \
+    k_aff_shared_fwd<NP, PP, float, false, false, false><<<grid, 256, 0, st>>>(query, S, C, N, dd, out, ld, pf, nullptr, none, 1)
     if (n_part == 1) {
-        if (d->norm_p == 1) k_aff_shared_fwd<1, 1><<<grid, 256, 0, st>>>(query, S, cand, N, dd, out, ld, pf);
-        else k_aff_shared_fwd<1, 2><<<grid, 256, 0, st>>>(query, S, cand, N, dd, out, ld, pf);
+        if (d->norm_p == 1) BESS_AFF_FWD(1, 1);
+        else BESS_AFF_FWD(1, 2);
     } else {
-        if (d->norm_p == 1) k_aff_shared_fwd<2, 1><<<grid, 256, 0, st>>>(query, S, cand, N, dd, out, ld, pf);
-        else k_aff_shared_fwd<2, 2><<<grid, 256, 0, st>>>(query, S, cand, N, dd, out, ld, pf);
+        if (d->norm_p == 1) BESS_AFF_FWD(2, 1);
+        else BESS_AFF_FWD(2, 2);
     }
+#undef BESS_AFF_FWD
     return check_launch("neg_score_shared_fwd (affine)");
+}
+
+// inverse part norms of n table rows (k_normalize_rows without its output): inv [n, n_part]
+int affine_inv_norms(const bess_model_desc* d, const void* base, const int32_t* idx, int64_t n, float* inv, hipStream_t st) {
+    const int n_part = d->reserved[0];
+    const int dd = d->width / n_part;
+    const unsigned blocks = static_cast<unsigned>(ceil_div(n, 4));
+    if (d->dtype == BESS_F32)
+        k_normalize_rows<float><<<blocks, 256, 0, st>>>(static_cast<const float*>(base), idx, n, dd, n_part, 1, nullptr, inv);
+    else
+        k_normalize_rows<half_t><<<blocks, 256, 0, st>>>(static_cast<const half_t*>(base), idx, n, dd, n_part, 1, nullptr, inv);
+    return check_launch("inverse norms (affine)");
+}
+
+template <int NPART, int P, typename TC>
+static void aff_table_launch(const float* query, int64_t S, const AffCand<TC>& C, int64_t N, int dd, float* out, int64_t ld,
+                             float pf, const float* thr, const CountArgs* cnt, hipStream_t st) {
+    if (cnt) {
+        // column tiles per workgroup: as many as leave the chip ~8 workgroups per CU (one atomic pair per row each)
+        const int64_t col_tiles = ceil_div(N, 64), row_tiles = ceil_div(S, 64);
+        int tiles = 1;
+        while (tiles < 8 && row_tiles * ceil_div(col_tiles, tiles * 2) >= 256 * 8) tiles *= 2;
+        const dim3 grid(static_cast<unsigned>(ceil_div(col_tiles, tiles)), static_cast<unsigned>(row_tiles));
+        k_aff_shared_fwd<NPART, P, TC, true, true, false><<<grid, 256, 0, st>>>(query, S, C, N, dd, out, ld, pf, thr, *cnt, tiles);
+    } else {
+        const dim3 grid(1, static_cast<unsigned>(ceil_div(S, 64)));
+        const CountArgs none{nullptr, nullptr, 0, 0};
+        k_aff_shared_fwd<NPART, P, TC, true, false, true><<<grid, 256, 0, st>>>(query, S, C, N, dd, out, 64, pf, nullptr, none, 1);
+    }
+}
+
+// The tile kernel on rows of the entity table (d->dtype, gathered through idx, scaled by inv [N, n_part] or not
+// at all when inv == NULL).  cnt != NULL: counts only (out may be NULL).  cnt == NULL: the diagonal form - S == N,
+// out [S, 64] receives the diagonal 64 x 64 tiles.
+int affine_table_fwd(const bess_model_desc* d, const float* query, int64_t S, const void* base, const int32_t* idx,
+                     const float* inv, int64_t N, float* out, int64_t ld, const float* thr, const CountArgs* cnt,
+                     hipStream_t st) {
+    const int n_part = d->reserved[0];
+    const int dd = d->width / n_part;
+    const float pf = static_cast<float>(d->norm_p);
+    BESS_REQUIRE(ceil_div(S, 64) < 65536, "affine scorers: more than 4 M queries in one call");
+    const int vec = dd % 4 == 0 && reinterpret_cast<uintptr_t>(base) % 16 == 0;
+#define BESS_AFF_TAB(NP, PP)                                                                                     \
+    do {                                                                                                         \
+        if (d->dtype == BESS_F32)                                                                                \
+            aff_table_launch<NP, PP, float>(query, S, AffCand<float>{static_cast<const float*>(base), idx, inv, vec}, N, dd, \
+                                            out, ld, pf, thr, cnt, st);                                          \
+        else                                                                                                     \
+            aff_table_launch<NP, PP, half_t>(query, S, AffCand<half_t>{static_cast<const half_t*>(base), idx, inv, vec}, N, \
+                                             dd, out, ld, pf, thr, cnt, st);                                     \
+    } while (0)
+    if (n_part == 1) {
+        if (d->norm_p == 1) BESS_AFF_TAB(1, 1);
+        else BESS_AFF_TAB(1, 2);
+    } else {
+        if (d->norm_p == 1) BESS_AFF_TAB(2, 1);
+        else BESS_AFF_TAB(2, 2);
+    }
+#undef BESS_AFF_TAB
+    return check_launch(cnt ? "neg_score_table_fwd_counts (affine)" : "neg_score_table_fwd_pairs (affine)");
 }
 
 int affine_shared_bwd(const bess_model_desc* d, const float* query, int64_t S, const float* cand, int64_t N,

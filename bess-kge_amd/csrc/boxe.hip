@@ -85,20 +85,34 @@ __device__ __forceinline__ float box_final(float dist, float h, bool inside) {
     return inside ? dist * A : dist * B - h * (B - A);
 }
 
-template <typename T, int VEC, int IT, int P, bool TANH, bool PERDIM>
-__global__ __launch_bounds__(256) void k_box_fwd(BoxArgs a, float* __restrict__ out, int64_t ld_out) {
+// COUNT: the counting variant (CountArgs of common.h; shared candidates only) - no score is stored; every 16-lane
+// group counts its candidates against thr[q], the wave adds the four groups up and lane 0 issues at most one
+// atomic pair.  Work items run candidate block first, query second: the waves in flight share a block of
+// candidate rows (L2) and stream the queries, where the storing form streams the whole candidate list per query.
+// The per-element and row16 arithmetic is the storing form's.  (Single (query, candidate) scores in this
+// arithmetic need no kernel of their own: the storing form with n_neg = 1 and one index per query.)
+template <typename T, int VEC, int IT, int P, bool TANH, bool PERDIM, bool COUNT>
+__global__ __launch_bounds__(256) void k_box_fwd(BoxArgs a, float* __restrict__ out, int64_t ld_out,
+                                                 const float* __restrict__ thr, CountArgs cnt) {
     const int lane = threadIdx.x & 63;
     const int g = lane & 15, sub = lane >> 4;
     const int64_t item = blockIdx.x * 4ll + (threadIdx.x >> 6);
     if (item >= a.n_query * a.items_per_query) return;
-    const int64_t q = item / a.items_per_query;
-    const int k0 = static_cast<int>(item - q * a.items_per_query) * a.nb;
+    const int64_t q = COUNT ? item % a.n_query : item / a.items_per_query;
+    const int k0 = static_cast<int>(COUNT ? item / a.n_query : item - q * a.items_per_query) * a.nb;
     const int k1 = min(k0 + a.nb, a.n_neg);
+    float th = 0.f;
+    int64_t ex = -1;
+    int cg = 0, ce = 0;
+    if constexpr (COUNT) {
+        th = thr[q];
+        ex = static_cast<int64_t>(cnt.excl[q]) - cnt.col0;
+    }
     BoxQuery<VEC, IT> qv;
     qv.load(a.query + q * 6 * a.d, g, a.d, a.nch);
     const T* base = static_cast<const T*>(a.base);
     const int32_t* idx = box_idx(a, q);
-    float* orow = out + q * ld_out;
+    float* orow = COUNT ? nullptr : out + q * ld_out;
     for (int kb = k0; kb < k1; kb += 4) {
         const int k = kb + sub;
         const bool valid = k < k1;
@@ -139,7 +153,24 @@ __global__ __launch_bounds__(256) void k_box_fwd(BoxArgs a, float* __restrict__ 
             acc = row16_allreduce_sum(acc);
             total += (P == 2) ? lp_root(acc, a.p) : acc;
         }
-        if (g == 0 && valid) orow[k] = -total;
+        if constexpr (COUNT) {
+            const float v = count_value(-total, cnt.round16);
+            const bool in = valid && k != ex;
+            cg += (in && v > th) ? 1 : 0;
+            ce += (in && v == th) ? 1 : 0;
+        } else {
+            if (g == 0 && valid) orow[k] = -total;
+        }
+    }
+    if constexpr (COUNT) {  // (the 16 lanes of a group hold the same counts)
+        cg += __shfl_xor(cg, 16, 64);
+        cg += __shfl_xor(cg, 32, 64);
+        ce += __shfl_xor(ce, 16, 64);
+        ce += __shfl_xor(ce, 32, 64);
+        if (lane == 0) {
+            if (cg) atomicAdd(cnt.counts + 2 * q, cg);
+            if (ce) atomicAdd(cnt.counts + 2 * q + 1, ce);
+        }
     }
 }
 
@@ -264,12 +295,14 @@ __global__ __launch_bounds__(256) void k_box_bwd(BoxArgs a, const float* __restr
 
 template <typename T, int VEC, int IT, int P>
 static void box_launch(int flags, bool fwd, const BoxArgs& a, float* out, const float* d_out, int64_t ld, float* dq,
-                       float* dn, int dn_atomic, hipStream_t st) {
+                       float* dn, int dn_atomic, hipStream_t st, const float* thr, const CountArgs* cnt) {
     const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_query * a.items_per_query, 4));
     const bool th = flags & 1, pd = flags & 2;
+    const CountArgs none{nullptr, nullptr, 0, 0};
 #define BESS_BOX(TH, PD)                                                                                   \
-    (fwd ? k_box_fwd<T, VEC, IT, P, TH, PD><<<blocks, 256, 0, st>>>(a, out, ld)                            \
-         : k_box_bwd<T, VEC, IT, P, TH, PD><<<blocks, 256, 0, st>>>(a, d_out, ld, dq, dn, dn_atomic))
+    (cnt ? k_box_fwd<T, VEC, IT, P, TH, PD, true><<<blocks, 256, 0, st>>>(a, nullptr, 0, thr, *cnt)        \
+     : fwd ? k_box_fwd<T, VEC, IT, P, TH, PD, false><<<blocks, 256, 0, st>>>(a, out, ld, nullptr, none)    \
+           : k_box_bwd<T, VEC, IT, P, TH, PD><<<blocks, 256, 0, st>>>(a, d_out, ld, dq, dn, dn_atomic))
     if (th && pd) BESS_BOX(true, true);
     else if (th) BESS_BOX(true, false);
     else if (pd) BESS_BOX(false, true);
@@ -279,10 +312,10 @@ static void box_launch(int flags, bool fwd, const BoxArgs& a, float* out, const 
 
 template <typename T, int VEC>
 static int box_by_it(int it, int p, int flags, bool fwd, const BoxArgs& a, float* out, const float* d_out, int64_t ld,
-                     float* dq, float* dn, int dn_atomic, hipStream_t st) {
-#define BESS_BOXP(ITV)                                                                        \
-    (p == 1 ? box_launch<T, VEC, ITV, 1>(flags, fwd, a, out, d_out, ld, dq, dn, dn_atomic, st) \
-            : box_launch<T, VEC, ITV, 2>(flags, fwd, a, out, d_out, ld, dq, dn, dn_atomic, st))
+                     float* dq, float* dn, int dn_atomic, hipStream_t st, const float* thr, const CountArgs* cnt) {
+#define BESS_BOXP(ITV)                                                                                  \
+    (p == 1 ? box_launch<T, VEC, ITV, 1>(flags, fwd, a, out, d_out, ld, dq, dn, dn_atomic, st, thr, cnt) \
+            : box_launch<T, VEC, ITV, 2>(flags, fwd, a, out, d_out, ld, dq, dn, dn_atomic, st, thr, cnt))
     if (it <= 1) BESS_BOXP(1);
     else if (it <= 2) BESS_BOXP(2);
     else if (it <= 4) BESS_BOXP(4);
@@ -295,7 +328,8 @@ static int box_by_it(int it, int p, int flags, bool fwd, const BoxArgs& a, float
 // shared == true: idx is one list of n_neg rows for every query (or NULL = rows 0..n_neg-1), d_neg is [n_neg, 2d]
 int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float* query, int64_t n_query,
                    const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* out, const float* d_out,
-                   int64_t ld, float* dq, float* dn, hipStream_t st) {
+                   int64_t ld, float* dq, float* dn, hipStream_t st, const float* thr, const CountArgs* count) {
+    BESS_REQUIRE(!count || (fwd && shared && thr), "BoxE: counting is a forward over shared candidates");
     const int dd = d->width / 2;
     const int vec = (dd % 4 == 0) ? 4 : 1;
     BoxArgs a;
@@ -307,10 +341,11 @@ int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float*
     a.n_neg = static_cast<int>(n_neg);
     a.d = dd;
     a.nch = dd / vec;
-    int nb = 64;
+    int nb = count ? 256 : 64;  // (counting: a wave's candidates end in one atomic pair)
     while (nb > 8 && n_query * ceil_div(n_neg, nb) < 256 * 16 * 2) nb >>= 1;
     a.nb = nb;
     a.items_per_query = static_cast<int>(ceil_div(n_neg, nb));
+    BESS_REQUIRE(!count || ceil_div(n_query * a.items_per_query, 4) < (1ll << 31), "BoxE: problem too large for one launch");
     a.p = static_cast<float>(d->norm_p);
     const int it = static_cast<int>(ceil_div(a.nch, 16));
     if (!fwd) {
@@ -322,11 +357,11 @@ int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float*
     int rc;
     const int flags = d->reserved[0];
     if (d->dtype == BESS_F32)
-        rc = vec == 4 ? box_by_it<float, 4>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st)
-                      : box_by_it<float, 1>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st);
+        rc = vec == 4 ? box_by_it<float, 4>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count)
+                      : box_by_it<float, 1>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count);
     else
-        rc = vec == 4 ? box_by_it<half_t, 4>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st)
-                      : box_by_it<half_t, 1>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st);
+        rc = vec == 4 ? box_by_it<half_t, 4>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count)
+                      : box_by_it<half_t, 1>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count);
     if (rc) return rc;
     return check_launch(fwd ? "neg_score fwd (BoxE)" : "neg_score bwd (BoxE)");
 }

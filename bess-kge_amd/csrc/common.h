@@ -103,11 +103,19 @@ int affine_shared_fwd(const bess_model_desc* d, const float* query, int64_t S, c
 int affine_shared_bwd(const bess_model_desc* d, const float* query, int64_t S, const float* cand, int64_t N,
                       const float* out, int64_t ld_out, const float* d_out, int64_t ld_dout, float* d_query,
                       float* d_cand, hipStream_t st);
+// the forward tile kernel on rows of the entity table, with the counting epilogue (cnt) or in its diagonal form
+// (cnt == NULL: S == N, out [S, 64]); inv [N, n_part]: affine_inv_norms of the same rows, NULL = not normalised
+int affine_inv_norms(const bess_model_desc* d, const void* base, const int32_t* idx, int64_t n, float* inv, hipStream_t st);
+int affine_table_fwd(const bess_model_desc* d, const float* query, int64_t S, const void* base, const int32_t* idx,
+                     const float* inv, int64_t N, float* out, int64_t ld, const float* thr, const CountArgs* cnt,
+                     hipStream_t st);
 
 // BoxE (boxe.hip): one kernel family for per-triple and shared negatives
+// (thr / count, forward with shared candidates only: the counting variant - no score is stored, out unused)
 int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float* query, int64_t n_query,
                    const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* out, const float* d_out,
-                   int64_t ld, float* dq, float* dn, hipStream_t st);
+                   int64_t ld, float* dq, float* dn, hipStream_t st, const float* thr = nullptr,
+                   const CountArgs* count = nullptr);
 
 // ---- device side ------------------------------------------------------------
 typedef _Float16 half_t;

@@ -839,6 +839,22 @@ static bool use_l1_pk(const bess_model_desc* d, const void* query, const void* n
            reinterpret_cast<uintptr_t>(query) % 16 == 0 && reinterpret_cast<uintptr_t>(neg_base) % 16 == 0;
 }
 
+// scalars per row of the query matrix (besskge/_native.py: query_width)
+static int64_t query_width(const bess_model_desc* d) {
+    if (d->scorer == BESS_AFFINE) return static_cast<int64_t>(d->reserved[0] + 1) * (d->width / d->reserved[0]);
+    if (d->scorer == BESS_BOXE) return 3ll * d->width;
+    return d->width;
+}
+
+// Candidate rows per launch of the affine counting pass: BESS_AFFINE_COUNT_CHUNK_BYTES of table rows (whole 64-row
+// tiles) - a chunk and its inverse norms stay in the Infinity Cache while the query tiles pass over them, as the
+// 65,536 fp16 rows of the packed L1 pass do.
+static int64_t affine_chunk_rows(const bess_model_desc* d) {
+    const int64_t row_bytes = static_cast<int64_t>(d->width) * (d->dtype == BESS_F32 ? 4 : 2);
+    const int64_t rows = BESS_AFFINE_COUNT_CHUNK_BYTES / row_bytes / 64 * 64;
+    return rows < 64 ? 64 : rows;
+}
+
 }  // namespace bess
 
 using namespace bess;
@@ -1018,6 +1034,7 @@ static bool counts_in_epilogue(const bess_model_desc* d, const float* query, con
 extern "C" int64_t bess_neg_score_shared_fwd_counts_workspace(const bess_model_desc* d, int64_t n_query,
                                                               int64_t n_neg) {
     if (!d || check_desc(d) || n_query <= 0 || n_neg <= 0) return 0;
+    if (d->scorer == BESS_BOXE) return 0;  // counts in its own kernel (k_box_fwd, COUNT)
     int64_t want = 0;
     if (counts_in_epilogue(d, nullptr, nullptr, n_query, n_neg, &want) && want > 0) return want;
     // (the packed L1 kernel needs none, but whether it applies depends on the pointers' alignment: the tile is
@@ -1037,6 +1054,9 @@ extern "C" int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const 
     BESS_REQUIRE(n_neg < (1ll << 31), "neg_score_shared_fwd_counts: candidate ids are int32");
     hipStream_t st = as_stream(stream);
     const CountArgs cnt{excl, counts, 0, round_f16 ? 1 : 0};
+    if (d->scorer == BESS_BOXE)
+        return boxe_negatives(d, true, true, query, n_query, neg_base, neg_idx, n_neg, nullptr, nullptr, 0, nullptr,
+                              nullptr, st, thr, &cnt);
     int64_t want = 0;
     if (counts_in_epilogue(d, query, neg_base, n_query, n_neg, &want)) {
         if (reduce_of(d) == RED_DOT) {
@@ -1096,6 +1116,7 @@ __global__ void k_take_diagonal(const float* __restrict__ tile, int64_t ld, int6
 extern "C" int64_t bess_neg_score_shared_fwd_pairs_workspace(const bess_model_desc* d, int64_t like_n_query,
                                                              int64_t like_n_neg) {
     if (!d || check_desc(d) || like_n_query <= 0 || like_n_neg <= 0) return 0;
+    if (d->scorer == BESS_BOXE) return 0;
     int64_t want = 0;
     if (counts_in_epilogue(d, nullptr, nullptr, like_n_query, like_n_neg, &want) && want > 0)
         return PAIR_DIAG_CHUNK * 128 * 4 + gemm_split_workspace_any(PAIR_DIAG_CHUNK, PAIR_DIAG_CHUNK, d->width);
@@ -1111,7 +1132,13 @@ extern "C" int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const f
     BESS_REQUIRE(n_pair >= 0 && like_n_query > 0 && like_n_neg > 0, "neg_score_shared_fwd_pairs: bad sizes");
     if (n_pair == 0) return BESS_OK;
     BESS_REQUIRE(query && neg_base && neg_idx && out, "neg_score_shared_fwd_pairs: NULL pointer");
-    BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "neg_score_shared_fwd_pairs: TransE / RotatE / DistMult / ComplEx only");
+    BESS_REQUIRE(d->scorer != BESS_AFFINE, "neg_score_shared_fwd_pairs: the affine scorers' pairs are scored from the "
+                                           "entity table (bess_neg_score_table_fwd_pairs)");
+    // BoxE: the kernel of the all-entity pass with one candidate per query - its per-triple form, n_neg = 1 (the
+    // per-element and row16 arithmetic does not know how many candidates a query has)
+    if (d->scorer == BESS_BOXE)
+        return boxe_negatives(d, true, false, query, n_pair, neg_base, neg_idx, 1, out, nullptr, 1, nullptr, nullptr,
+                              as_stream(stream));
     BESS_REQUIRE(workspace && workspace_bytes >= bess_neg_score_shared_fwd_pairs_workspace(d, like_n_query, like_n_neg) &&
                      reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
                  "neg_score_shared_fwd_pairs: workspace too small (bess_neg_score_shared_fwd_pairs_workspace) or misaligned");
@@ -1120,7 +1147,7 @@ extern "C" int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const f
     int64_t want = 0;
     const bool epi = counts_in_epilogue(d, query, neg_base, like_n_query, like_n_neg, &want);
     const bool gemm = epi && reduce_of(d) == RED_DOT;
-    const int64_t qw = d->width;  // (the four native scorers: query rows as wide as entity rows)
+    const int64_t qw = query_width(d);
     const int64_t chunk = epi ? PAIR_DIAG_CHUNK : PAIR_CHUNK;
     const int64_t block = gemm ? 128 : (epi ? 64 : PAIR_CHUNK);  // columns of `tile`
     void* gws = static_cast<char*>(workspace) + PAIR_DIAG_CHUNK * 128 * 4;
@@ -1138,6 +1165,91 @@ extern "C" int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const f
             rc = bess_neg_score_shared_fwd_ws(d, q, np, neg_base, neg_idx + p0, np, tile, PAIR_CHUNK, nullptr, 0, stream);
         if (rc) return rc;
         k_take_diagonal<<<static_cast<unsigned>(ceil_div(np, 256)), 256, 0, st>>>(tile, block, np, block, out + p0);
+        if (int e = check_launch("take_diagonal")) return e;
+    }
+    return BESS_OK;
+}
+
+// ---- the same two calls on the entity table --------------------------------------------------------------------
+// neg_base is always the table in desc.dtype (optional neg_idx).  That is what the shared calls take for every
+// scorer but the affine family, whose shared kernels are defined on dense normalised f32 rows: for them the tile
+// kernel stages the raw rows and scales them by inverse norms computed per chunk (affine.hip).
+static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+extern "C" int64_t bess_neg_score_table_fwd_counts_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
+    if (!d || check_desc(d) || n_query <= 0 || n_neg <= 0) return 0;
+    if (d->scorer != BESS_AFFINE) return bess_neg_score_shared_fwd_counts_workspace(d, n_query, n_neg);
+    if (!(d->reserved[1] & 1)) return 0;  // not normalised: no inverse norms
+    const int64_t chunk = affine_chunk_rows(d);
+    return align256((n_neg < chunk ? n_neg : chunk) * d->reserved[0] * 4);
+}
+
+extern "C" int bess_neg_score_table_fwd_counts(const bess_model_desc* d, const float* query, int64_t n_query,
+                                               const void* neg_base, const int32_t* neg_idx, int64_t n_neg,
+                                               const float* thr, const int32_t* excl, int32_t* counts,
+                                               int32_t round_f16, void* workspace, int64_t workspace_bytes,
+                                               void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->scorer != BESS_AFFINE)
+        return bess_neg_score_shared_fwd_counts(d, query, n_query, neg_base, neg_idx, n_neg, thr, excl, counts, round_f16,
+                                                workspace, workspace_bytes, stream);
+    BESS_REQUIRE(n_query >= 0 && n_neg >= 0, "neg_score_table_fwd_counts: bad sizes");
+    if (n_query == 0 || n_neg == 0) return BESS_OK;
+    BESS_REQUIRE(query && neg_base && thr && excl && counts, "neg_score_table_fwd_counts: NULL pointer");
+    BESS_REQUIRE(n_neg < (1ll << 31), "neg_score_table_fwd_counts: candidate ids are int32");
+    const bool normalize = d->reserved[1] & 1;
+    BESS_REQUIRE(!normalize || (workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0 &&
+                                workspace_bytes >= bess_neg_score_table_fwd_counts_workspace(d, n_query, n_neg)),
+                 "neg_score_table_fwd_counts: workspace too small (bess_neg_score_table_fwd_counts_workspace) or misaligned");
+    hipStream_t st = as_stream(stream);
+    float* inv = normalize ? static_cast<float*>(workspace) : nullptr;
+    const int64_t chunk = affine_chunk_rows(d);
+    const int64_t row_bytes = static_cast<int64_t>(d->width) * (d->dtype == BESS_F32 ? 4 : 2);
+    for (int64_t j0 = 0; j0 < n_neg; j0 += chunk) {
+        const int64_t nc = n_neg - j0 < chunk ? n_neg - j0 : chunk;
+        const void* base = neg_idx ? neg_base : static_cast<const char*>(neg_base) + j0 * row_bytes;
+        const int32_t* idx = neg_idx ? neg_idx + j0 : nullptr;
+        if (normalize)
+            if (int e = affine_inv_norms(d, base, idx, nc, inv, st)) return e;
+        const CountArgs cj{excl, counts, j0, round_f16 ? 1 : 0};
+        if (int e = affine_table_fwd(d, query, n_query, base, idx, inv, nc, nullptr, 0, thr, &cj, st)) return e;
+    }
+    return BESS_OK;
+}
+
+extern "C" int64_t bess_neg_score_table_fwd_pairs_workspace(const bess_model_desc* d, int64_t like_n_query,
+                                                            int64_t like_n_neg) {
+    if (!d || check_desc(d) || like_n_query <= 0 || like_n_neg <= 0) return 0;
+    if (d->scorer != BESS_AFFINE) return bess_neg_score_shared_fwd_pairs_workspace(d, like_n_query, like_n_neg);
+    return PAIR_DIAG_CHUNK * 64 * 4 + PAIR_DIAG_CHUNK * d->reserved[0] * 4;  // diagonal tiles + inverse norms
+}
+
+extern "C" int bess_neg_score_table_fwd_pairs(const bess_model_desc* d, const float* query, const void* neg_base,
+                                              const int32_t* neg_idx, int64_t n_pair, int64_t like_n_query,
+                                              int64_t like_n_neg, float* out, void* workspace, int64_t workspace_bytes,
+                                              void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->scorer != BESS_AFFINE)
+        return bess_neg_score_shared_fwd_pairs(d, query, neg_base, neg_idx, n_pair, like_n_query, like_n_neg, out,
+                                               workspace, workspace_bytes, stream);
+    BESS_REQUIRE(n_pair >= 0 && like_n_query > 0 && like_n_neg > 0, "neg_score_table_fwd_pairs: bad sizes");
+    if (n_pair == 0) return BESS_OK;
+    BESS_REQUIRE(query && neg_base && neg_idx && out, "neg_score_table_fwd_pairs: NULL pointer");
+    BESS_REQUIRE(workspace && workspace_bytes >= bess_neg_score_table_fwd_pairs_workspace(d, like_n_query, like_n_neg) &&
+                     reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+                 "neg_score_table_fwd_pairs: workspace too small (bess_neg_score_table_fwd_pairs_workspace) or misaligned");
+    hipStream_t st = as_stream(stream);
+    float* tile = static_cast<float*>(workspace);
+    float* inv = (d->reserved[1] & 1) ? tile + PAIR_DIAG_CHUNK * 64 : nullptr;
+    const int64_t qw = query_width(d);
+    // the counting pass's kernel on the diagonal 64 x 64 tiles of the (pairs x pairs) problem
+    for (int64_t p0 = 0; p0 < n_pair; p0 += PAIR_DIAG_CHUNK) {
+        const int64_t np = n_pair - p0 < PAIR_DIAG_CHUNK ? n_pair - p0 : PAIR_DIAG_CHUNK;
+        if (inv)
+            if (int e = affine_inv_norms(d, neg_base, neg_idx + p0, np, inv, st)) return e;
+        if (int e = affine_table_fwd(d, query + p0 * qw, np, neg_base, neg_idx + p0, inv, np, tile, 64, nullptr, nullptr, st))
+            return e;
+        k_take_diagonal<<<static_cast<unsigned>(ceil_div(np, 256)), 256, 0, st>>>(tile, 64, np, 64, out + p0);
         if (int e = check_launch("take_diagonal")) return e;
     }
     return BESS_OK;

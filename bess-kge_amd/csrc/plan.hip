@@ -84,6 +84,8 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_neg_score_shared_fwd_pruned),
     BESS_PLAN_FN(bess_neg_score_shared_fwd_counts),
     BESS_PLAN_FN(bess_neg_score_shared_fwd_pairs),
+    BESS_PLAN_FN(bess_neg_score_table_fwd_counts),
+    BESS_PLAN_FN(bess_neg_score_table_fwd_pairs),
     BESS_PLAN_FN(bess_neg_score_shared_bwd),
     BESS_PLAN_FN(bess_neg_score_shared_bwd_ws),
     BESS_PLAN_FN(bess_neg_score_shared_bwd_parts),

@@ -336,8 +336,10 @@ int bess_neg_score_shared_fwd_pruned(const bess_model_desc* d, const float* quer
  * in the candidate list (0 .. n_neg - 1), or -1 when it is not among these candidates (another shard's entity);
  * counts [n_query, 2] int32 is accumulated into (clear it before the first shard / window).  The counting is the
  * epilogue of the split-fp16 matrix-core product (DistMult / ComplEx) and of the packed-fp16 L1 kernel (TransE /
- * RotatE p = 1 on f16 tables): no score is written.  Other scorers / shapes score tiles of at most 64 MiB into the
- * workspace and count them there.  workspace: bess_neg_score_shared_fwd_counts_workspace bytes, 16-B aligned.
+ * RotatE p = 1 on f16 tables) and of BoxE's kernel (workspace 0): no score is written.  Other scorers / shapes score
+ * tiles of at most 64 MiB into the workspace and count them there (BESS_AFFINE: on dense normalised f32 candidates,
+ * as in bess_neg_score_shared_fwd_ws - bess_neg_score_table_fwd_counts below counts straight from the entity table).
+ * workspace: bess_neg_score_shared_fwd_counts_workspace bytes, 16-B aligned.
  * round_f16 != 0: every score is rounded to fp16 before it is compared (thr is taken as given) - the ranking a
  * reference whose model is in half precision makes of its fp16 scores, ties included.
  * If an operand of the matrix-core product is outside the fp16 range every count of the call is set to INT32_MIN
@@ -355,12 +357,35 @@ int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const float* quer
  * (split-fp16 product, packed L1 kernel) or on 1024 x 1024 blocks whose diagonal is kept (the other kernels); the
  * kernels' per-element arithmetic does not depend on the element's place in the matrix.  For the positive scores
  * and the filtered completions that a rank count is corrected with (pipeline.py:233-271): a per-triple kernel
- * would round differently and move ranks by one at near-ties.  TransE / RotatE / DistMult / ComplEx.
+ * would round differently and move ranks by one at near-ties.  TransE / RotatE / DistMult / ComplEx, and BoxE
+ * (whose one kernel family scores a pair as a query with a single candidate; workspace 0).  query rows are as wide
+ * as the scorer's query matrix (BoxE: 3 * width).  BESS_AFFINE: bess_neg_score_table_fwd_pairs.
  * workspace: bess_neg_score_shared_fwd_pairs_workspace bytes, 16-B aligned. */
 int64_t bess_neg_score_shared_fwd_pairs_workspace(const bess_model_desc* d, int64_t like_n_query, int64_t like_n_neg);
 int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const float* query, const void* neg_base,
                                     const int32_t* neg_idx, int64_t n_pair, int64_t like_n_query, int64_t like_n_neg,
                                     float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The two calls above on the ENTITY TABLE: neg_base is always the table in desc.dtype, neg_idx optional for the
+ * counts.  For every scorer but BESS_AFFINE that is what their shared namesakes take, and these forward to them.
+ * BESS_AFFINE (whose shared calls take dense f32 rows that bess_normalize_rows has normalised): the 64 x 64 tile
+ * kernel stages the raw rows and multiplies them by the rows' inverse part norms as it does - to_f32(x) * s with
+ * the s of bess_normalize_rows, i.e. bit for bit the operand, and the score, of bess_neg_score_shared_fwd_ws on
+ * normalised rows - with the counting epilogue, or on the diagonal tiles for the pairs.  No score, no score tile
+ * and no normalised copy is written: candidates go through in chunks of BESS_AFFINE_COUNT_CHUNK_BYTES of table rows
+ * (whole 64-row tiles, at least one) that stay in the Infinity Cache while the query tiles pass over them, and the
+ * workspace holds the inverse norms of one chunk (n_part floats per row; 0 bytes when entities are not
+ * normalised) - it does not depend on n_query.  query rows: (n_part + 1) * d scalars [U | V | R]. */
+#define BESS_AFFINE_COUNT_CHUNK_BYTES (32ll << 20)
+int64_t bess_neg_score_table_fwd_counts_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg);
+int bess_neg_score_table_fwd_counts(const bess_model_desc* d, const float* query, int64_t n_query,
+                                    const void* neg_base, const int32_t* neg_idx, int64_t n_neg, const float* thr,
+                                    const int32_t* excl, int32_t* counts, int32_t round_f16, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+int64_t bess_neg_score_table_fwd_pairs_workspace(const bess_model_desc* d, int64_t like_n_query, int64_t like_n_neg);
+int bess_neg_score_table_fwd_pairs(const bess_model_desc* d, const float* query, const void* neg_base,
+                                   const int32_t* neg_idx, int64_t n_pair, int64_t like_n_query, int64_t like_n_neg,
+                                   float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 int64_t bess_neg_score_shared_bwd_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg);
 int bess_neg_score_shared_bwd_ws(const bess_model_desc* d, const float* query,
