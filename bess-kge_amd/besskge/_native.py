@@ -173,6 +173,8 @@ SIGNATURES = {
     "bess_apply_segments_sgd": [_i32, _i32, _vp, _vp, _vp, _i64, _vp, _f32, _vp],
     "bess_segment_sum_rows": [_i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "bess_topk_update": [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _vp],
+    "bess_topk_update_excl": [_vp, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
+    "bess_topk_update_flagged_excl": [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
     "bess_ranks_from_scores": [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp],
     "bess_ranks_from_indices": [_vp, _vp, _i64, _i64, _i32, _vp, _vp],
     "bess_apply_segments_opt": [ctypes.POINTER(OptDesc), _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
@@ -251,6 +253,8 @@ TIMING_LABELS = {
     "bess_sparse_sgd_lists_axpy": "bess_sparse_sgd_lists",
     "bess_coalesced_update_axpy": "bess_coalesced_update",
     "bess_topk_update_flagged": "bess_topk_update",
+    "bess_topk_update_excl": "bess_topk_update",
+    "bess_topk_update_flagged_excl": "bess_topk_update",
 }
 
 
@@ -877,12 +881,22 @@ def _affine_candidates(d: ModelDesc, neg: RowSource) -> Tuple[RowSource, torch.T
     return RowSource(hat), hat, inv
 
 
+def _range_flag(ws: Optional[torch.Tensor], range_flags: Optional[list]) -> None:
+    """Note the range flag of a split-fp16 product in `range_flags`: the int32 at the tail of its scratch, non-zero
+    after the call when an operand was outside the fp16 range and the fp32 kernels computed the scores instead."""
+    if range_flags is not None and ws is not None:
+        off = (ws.numel() - 256) // 16 * 16
+        range_flags.append(ws[off: off + 4].view(torch.int32))
+
+
 def neg_score_shared_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, pad_ld: bool = False,
-                         kill: Optional[Tuple[int, bool, int, Optional[torch.Tensor]]] = None) -> torch.Tensor:
+                         kill: Optional[Tuple[int, bool, int, Optional[torch.Tensor]]] = None,
+                         range_flags: Optional[list] = None) -> torch.Tensor:
     """Scores [nq, n_neg].  `pad_ld`: rows of the result are 16-B aligned (leading dimension rounded
     up to 4 floats; the result is then a column slice of the buffer) - what `topk_update` streams fastest.
     `kill` = (diag_step, ht, ppp, mask [rows, cols] bool | None): K7 applied with the scores
-    (`mask_scores` semantics; in the scoring kernel's epilogue where it has one)."""
+    (`mask_scores` semantics; in the scoring kernel's epilogue where it has one).  `range_flags`: a list that
+    receives the call's range flag when the split-fp16 product ran (`_range_flag`)."""
     nq, n_neg = int(query.shape[0]), len(neg)
     dev = _neg_operands(d, query, neg, n_neg)
     if d.scorer == AFFINE:
@@ -911,16 +925,17 @@ def neg_score_shared_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, pad_
     else:
         _launch("bess_neg_score_shared_fwd_masked", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
                 _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, ctypes.byref(kd), wp, ws_bytes)
+    _range_flag(ws, range_flags)
     return out if ld == n_neg else out[:, :n_neg]
 
 
-def neg_score_shared_fwd_pruned(d: ModelDesc, query: torch.Tensor, neg: RowSource, thr: torch.Tensor
-                                ) -> Tuple[torch.Tensor, torch.Tensor]:
+def neg_score_shared_fwd_pruned(d: ModelDesc, query: torch.Tensor, neg: RowSource, thr: torch.Tensor,
+                                range_flags: Optional[list] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(scores [nq, n_neg] with 16-B aligned rows, flags [nq, n_blocks] uint8) for the top-k passes: a row's block
     of 64 consecutive candidates is written only when one of its scores is above `thr[row]` (f32 [nq]: the row's
     current k-th best), `flags` marks the blocks that were - the rest of `scores` is uninitialised memory, which
     `topk_update(..., flags=flags)` never reads.  (`bess_neg_score_shared_fwd_pruned`: kernels without a pruning
-    epilogue write and flag everything.)"""
+    epilogue write and flag everything.)  `range_flags`: see `_range_flag`."""
     nq, n_neg = int(query.shape[0]), len(neg)
     dev = _neg_operands(d, query, neg, n_neg)
     _same_device([("query", query), ("thr", thr)])
@@ -939,6 +954,7 @@ def neg_score_shared_fwd_pruned(d: ModelDesc, query: torch.Tensor, neg: RowSourc
     _launch("bess_neg_score_shared_fwd_pruned", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
             _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, thr.data_ptr(), flags.data_ptr(), ldf,
             ws.data_ptr() if ws is not None else None, ws_bytes)
+    _range_flag(ws, range_flags)
     return (out if ld == n_neg else out[:, :n_neg]), flags
 
 
@@ -1726,6 +1742,68 @@ def topk_update(scores: torch.Tensor, best_score: torch.Tensor, best_id: torch.T
         return
     _launch("bess_topk_update", dev, scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr,
             best_score.data_ptr(), best_id.data_ptr(), kk)
+
+
+#: id of an empty entry of the ordered lists (`topk_update_excl`): nothing sorts after (-inf, TOPK_ID_NONE)
+TOPK_ID_NONE = 2**31 - 1
+
+
+def topk_update_excl(scores: torch.Tensor, best_score: torch.Tensor, best_id: torch.Tensor,
+                     ids: Optional[torch.Tensor] = None, id_base: int = 0, mask: Optional[torch.Tensor] = None,
+                     flags: Optional[torch.Tensor] = None, excl_ptr: Optional[torch.Tensor] = None,
+                     excl_ids: Optional[torch.Tensor] = None, round_f16: bool = False) -> None:
+    """`topk_update` under the total order (score descending, id ascending), leaving out the candidates named by
+    the rows' exclusion lists (`bess_topk_update_excl` / `bess_topk_update_flagged_excl`): the result does not
+    depend on the order of columns, tiles or shards.  Lists start out as (-inf, TOPK_ID_NONE).
+
+    `excl_ptr` [rows + 1], `excl_ids` (int32, CSR; ids ascending within a row, in the id space of the candidates).
+    `round_f16`: scores are rounded to fp16 before they are compared and stored.  With `flags`, `ids` is one row
+    [1, L] shared by all rows (or None: `id_base` + column) and there is no mask; the thresholds the tile was
+    pruned with must be strictly below the rows' kk-th scores."""
+    dev = _same_device([("scores", scores), ("best_score", best_score), ("best_id", best_id), ("ids", ids),
+                        ("mask", mask), ("flags", flags), ("excl_ptr", excl_ptr), ("excl_ids", excl_ids)])
+    if scores.dtype != torch.float32 or scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError("topk_update_excl: scores must be float32 [rows, L] with contiguous rows")
+    _f32(best_score, "best_score")
+    if best_score.dim() != 2 or best_score.shape[0] != scores.shape[0] \
+            or best_id.shape != best_score.shape or best_id.dtype != torch.int32 or not best_id.is_contiguous():
+        raise ValueError("topk_update_excl: best lists must be [rows, kk] (f32 scores, int32 ids)")
+    R, L, kk = int(scores.shape[0]), int(scores.shape[1]), int(best_score.shape[1])
+    if (excl_ptr is None) != (excl_ids is None):
+        raise ValueError("topk_update_excl: excl_ptr and excl_ids go together")
+    ep = ei = n_excl = 0
+    if excl_ptr is not None:
+        for t in (excl_ptr, excl_ids):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("topk_update_excl: excl_ptr / excl_ids must be contiguous 1-D int32 tensors")
+        if excl_ptr.numel() != R + 1:
+            raise ValueError(f"topk_update_excl: excl_ptr has {excl_ptr.numel()} entries, expected rows + 1 = {R + 1}")
+        ep, ei, n_excl = excl_ptr.data_ptr(), excl_ids.data_ptr(), int(excl_ids.numel())
+    ip = ir = 0
+    if ids is not None:
+        if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[1] != L or ids.shape[0] not in (1, R) \
+                or not ids.is_contiguous():
+            raise ValueError("topk_update_excl: ids must be a contiguous int32 [1 | rows, L] tensor")
+        ip, ir = ids.data_ptr(), int(ids.shape[0])
+    mp = mr = 0
+    if mask is not None:
+        if mask.dtype != torch.bool or mask.dim() != 2 or mask.shape[1] != L or mask.shape[0] not in (1, R) \
+                or not mask.is_contiguous():
+            raise ValueError("topk_update_excl: mask must be a contiguous bool [1 | rows, L] tensor")
+        mp, mr = mask.data_ptr(), int(mask.shape[0])
+    ld = int(scores.stride(0)) if R > 1 else L
+    if flags is not None:
+        if mask is not None or (ids is not None and ids.shape[0] != 1):
+            raise ValueError("topk_update_excl: flagged tiles take one shared row of ids (or id_base) and no mask")
+        if flags.dtype != torch.uint8 or flags.dim() != 2 or flags.shape[0] != R or not flags.is_contiguous() \
+                or flags.shape[1] % 4 or flags.shape[1] * 64 < L:
+            raise ValueError("topk_update_excl: flags must be a contiguous uint8 [rows, 4 * ceil(L / 256)] tensor")
+        _launch("bess_topk_update_flagged_excl", dev, scores.data_ptr(), R, L, max(ld, L), flags.data_ptr(),
+                int(flags.shape[1]), ip, int(id_base), ep, ei, n_excl, int(bool(round_f16)), best_score.data_ptr(),
+                best_id.data_ptr(), kk)
+        return
+    _launch("bess_topk_update_excl", dev, scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr, ep, ei,
+            n_excl, int(bool(round_f16)), best_score.data_ptr(), best_id.data_ptr(), kk)
 
 
 # --------------------------------------------------------------------------- #

@@ -21,7 +21,7 @@ from besskge import runtime
 from besskge.batch_sampler import ShardedBatchSampler
 from besskge.collectives import ReplicaGroup
 from besskge.negative_sampler import PlaceholderNegativeSampler
-from besskge.query import AllScoresBESS, topk_merge
+from besskge.query import KERNEL_LIST_MAX, AllScoresBESS, topk_merge
 from besskge.scoring import BaseScoreFunction
 from besskge.utils import get_entity_filter
 
@@ -35,13 +35,16 @@ def _counting_scorer(score_fn: BaseScoreFunction) -> bool:
         return False
 
 
-def rank_filter_pairs(flt: torch.Tensor, keep: torch.Tensor, truth: torch.Tensor, rows: int, shard_bs: int,
+def rank_filter_pairs(flt: torch.Tensor, keep: torch.Tensor, truth: Optional[torch.Tensor], rows: int, shard_bs: int,
                       candidate: Optional[torch.Tensor] = None) -> "tuple[torch.Tensor, torch.Tensor]":
-    """The `rank_filter` input of `AllScoresBESS.rank_counts_replicas` for one sampler batch.
+    """The `rank_filter` input of `AllScoresBESS.rank_counts_replicas` / `topk_replicas` for one sampler batch:
+    the (query, entity) pairs to leave out, from `get_entity_filter` output.  Pure torch on the host.
 
     :param flt: (z, 2) rows (i, e) of `get_entity_filter`: entity e is filtered for the i-th KEPT triple.
     :param keep: flat [rows * shard_bs] triple mask (rows = micro-batches x shards).
-    :param truth: flat [rows * shard_bs] global id of every slot's true completion.
+    :param truth: flat [rows * shard_bs] global id of every slot's true completion - pairs naming it are dropped:
+        the counts leave the truth out by themselves, and a top-k list keeps it even when `filter_triples` holds
+        the test triple (reference pipeline.py:277-278).  None (queries without a ground truth): nothing is dropped.
     :param candidate: bool [n_entity], with `candidate_ents`: pairs naming an entity outside the subset are
         dropped - the counting pass never sees those entities (the reference sets them to -inf anyway,
         pipeline.py:247-250), so there is nothing to subtract for them.
@@ -50,7 +53,8 @@ def rank_filter_pairs(flt: torch.Tensor, keep: torch.Tensor, truth: torch.Tensor
     """
     slot = keep.nonzero().reshape(-1)[flt[:, 0]]  # position in the flat [rows * shard_bs] batch
     pairs = torch.stack([slot, flt[:, 1].to(slot.dtype)], dim=1)
-    pairs = pairs[pairs[:, 1] != truth[pairs[:, 0]].to(pairs.dtype)]  # (the truth is left out anyway)
+    if truth is not None:
+        pairs = pairs[pairs[:, 1] != truth[pairs[:, 0]].to(pairs.dtype)]  # (the truth is left out anyway)
     if candidate is not None:
         pairs = pairs[candidate[pairs[:, 1]]]
     pairs = torch.unique(pairs, dim=0)  # sorted by slot
@@ -110,6 +114,7 @@ class AllScoresPipeline(torch.nn.Module):
         group: Optional[ReplicaGroup] = None,
         device: Optional[torch.device] = None,
         fused_ranks: bool = True,
+        fused_topk: bool = True,
     ) -> None:
         """
         :param batch_sampler: sampler over "h_shard" / "t_shard" partitioned queries.
@@ -124,7 +129,7 @@ class AllScoresPipeline(torch.nn.Module):
         :param use_ipu_model: accepted for call compatibility, ignored.
         :param group / device: replica group and HIP device (default: all shards
             in this process on the current device).
-        :param fused_ranks: when only metrics / ranks are asked for (no scores, no top-k) count the entities that beat the true completion in the scoring kernel's
+        :param fused_ranks: when no scores are asked for count the entities that beat the true completion in the scoring kernel's
             epilogue instead of assembling the `[queries, n_entity]` score matrix
             (`AllScoresBESS.rank_counts_replicas`).  The same ranks to the last bit as the matrix path
             whenever that scores its windows with the same kernel as the all-entity pass (the positives'
@@ -134,6 +139,13 @@ class AllScoresPipeline(torch.nn.Module):
             agree to a rounding error.  Every scorer of `besskge.scoring` takes this path (PairRE / TripleRE /
             InterHT / TranS and BoxE run one per-element arithmetic whatever the window: the same ranks for
             any `window_size`); `fused_ranks=False` forces the matrix path.
+        :param fused_topk: with `return_topk` and without `return_scores` keep the k best entities per query in the
+            streaming top-k kernels while the shards are scored (`AllScoresBESS.topk_replicas`) instead of
+            assembling the `[queries, n_entity]` matrix: filtered completions are exclusion lists of the kernel,
+            `candidate_ents` restricts the pass, equal scores are ordered by ascending entity id - the matrix
+            path's order, whose columns are entity ids.  The same `topk_global_id` as the matrix path under the
+            condition given for `fused_ranks`; scorers with a kernel descriptor and k <= 128.
+            `fused_topk=False` forces the matrix path.
         """
         super().__init__()
         if not (evaluation or return_scores):
@@ -171,9 +183,13 @@ class AllScoresPipeline(torch.nn.Module):
             self.triples = torch.from_numpy(glob)
             self.filter_triples = torch.concat(
                 [t if isinstance(t, torch.Tensor) else torch.from_numpy(t) for t in filter_triples], dim=0)
-        self.fused_ranks = bool(fused_ranks and evaluation and not return_scores and not return_topk
-                                and _counting_scorer(score_fn))
-        if self.fused_ranks:
+        # (ranks asked for but not counted come from the matrix: then the top-k does too)
+        self.fused_topk = bool(fused_topk and return_topk and not return_scores and 1 <= k <= KERNEL_LIST_MAX
+                               and _counting_scorer(score_fn) and (fused_ranks or not evaluation))
+        # (with a top-k wanted through the matrix, the ranks come from that matrix as before)
+        self.fused_ranks = bool(fused_ranks and evaluation and not return_scores and _counting_scorer(score_fn)
+                                and (self.fused_topk or not return_topk))
+        if self.fused_ranks or self.fused_topk:
             self.bess_module.set_rank_candidates(candidate_ents)
         self.candidate_mask: Optional[torch.Tensor] = None
         self._is_candidate: Optional[torch.Tensor] = None
@@ -189,24 +205,33 @@ class AllScoresPipeline(torch.nn.Module):
             cols.append(sharding.shard_and_idx_to_entity[:, ent_slice].flatten())
         self._first = torch.from_numpy(np.unique(np.concatenate(cols), return_index=True)[1])
 
+    def _filter_pairs(self, ground_truth: Optional[torch.Tensor], triple_mask: torch.Tensor,
+                      triple_id: Optional[torch.Tensor]) -> "Optional[tuple[torch.Tensor, torch.Tensor]]":
+        """(`rank_filter` input, filtered completions per kept triple) of one sampler batch; None without a filter."""
+        if self.filter_triples is None:
+            return None
+        if triple_id is None:
+            raise ValueError("filtering needs a batch sampler with return_triple_idx=True")
+        rows, shard_bs = triple_mask.flatten(end_dim=1).shape  # [micro-batches * n_shard, shard_bs]
+        flt = get_entity_filter(self.triples[triple_id[triple_mask]], self.filter_triples,
+                                filter_mode=self.corruption_scheme)
+        truth = None if ground_truth is None else ground_truth.flatten()
+        return rank_filter_pairs(flt, triple_mask.flatten(), truth, rows, shard_bs, self._is_candidate)
+
     def _ranks_by_counting(self, inp: Dict[str, torch.Tensor], ground_truth: torch.Tensor,
-                           triple_mask: torch.Tensor, triple_id: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+                           triple_mask: torch.Tensor, triple_id: Optional[torch.Tensor],
+                           pairs: "Optional[tuple[torch.Tensor, torch.Tensor]]" = None) -> Optional[torch.Tensor]:
         """Ranks of one sampler batch from counts made in the scoring kernels' epilogues; None when the
-        matrix-core product met operands outside its fp16 range (the caller then takes the matrix path)."""
+        matrix-core product met operands outside its fp16 range (the caller then takes the matrix path).
+        `pairs`: the batch's `_filter_pairs`, when the caller has made them already."""
         ev = self.evaluation
         sharding = self.bess_module.sharding
-        n = sharding.n_shard
         rows, shard_bs = ground_truth.flatten(end_dim=1).shape  # [micro-batches * n_shard, shard_bs]
         keep = triple_mask.flatten()
-        truth = ground_truth.flatten()
         extra = dict(rank_truth=ground_truth.flatten(end_dim=1).to(torch.int32))
         n_masked = torch.ones(int(keep.sum()), dtype=torch.int64)  # entries the reference sets to -inf, per kept row
         if self.filter_triples is not None:
-            if triple_id is None:
-                raise ValueError("filtering needs a batch sampler with return_triple_idx=True")
-            flt = get_entity_filter(self.triples[triple_id[triple_mask]], self.filter_triples,
-                                    filter_mode=self.corruption_scheme)
-            filt, per_kept = rank_filter_pairs(flt, keep, truth, rows, shard_bs, self._is_candidate)
+            filt, per_kept = pairs if pairs is not None else self._filter_pairs(ground_truth, triple_mask, triple_id)
             n_masked += per_kept
             extra["rank_filter"] = filt
         if self._is_candidate is not None:
@@ -221,6 +246,21 @@ class AllScoresPipeline(torch.nn.Module):
             return None  # some shard's matrix-core product met operands outside the fp16 range: matrix path
         pos = out["pos_score"].reshape(-1)[keep.to(dev)]
         return ranks_from_counts(counts, pos, n_masked.to(dev), sharding.n_entity, ev.mode, ev.worst_rank_infty)
+
+    def _topk_by_lists(self, inp: Dict[str, torch.Tensor], triple_mask: torch.Tensor,
+                       pairs: "Optional[tuple[torch.Tensor, torch.Tensor]]") -> Optional[torch.Tensor]:
+        """`topk_global_id` of one sampler batch from lists kept while the shards are scored
+        (`AllScoresBESS.topk_replicas`): no score matrix; None when a split-fp16 product met operands outside its
+        range (the caller then takes the matrix path, as for the counts)."""
+        rows = triple_mask.flatten(end_dim=1).shape[0]
+        extra = dict(topk_k=torch.full((rows, 1), self.k, dtype=torch.int32))
+        if pairs is not None:
+            extra["rank_filter"] = pairs[0]
+        out = self.runner(step=torch.zeros((rows, 1), dtype=torch.int32), **inp, **extra)
+        if bool(out["out_of_range"].any()):
+            return None
+        dev = out["topk_global_id"].device
+        return out["topk_global_id"].reshape(-1, self.k)[triple_mask.flatten().to(dev)]
 
     def forward(self) -> Dict[str, Any]:
         """Run over the whole sampler."""
@@ -239,13 +279,22 @@ class AllScoresPipeline(torch.nn.Module):
                 ids.append(triple_id[triple_mask])
             n_triple += int(triple_mask.sum())
             inp = {k: v.flatten(end_dim=1) for k, v in batch.items()}
-            if self.fused_ranks:
-                assert ground_truth is not None, "Evaluation requires providing ground truth entities"
-                r = self._ranks_by_counting(inp, ground_truth, triple_mask, triple_id)
-                if r is not None:
-                    metrics.append({m: v.cpu() for m, v in ev.dict_metrics_from_ranks(r).items()})
-                    if ev.return_ranks:
-                        ranks.append(r.cpu())
+            if self.fused_ranks or self.fused_topk:
+                # nothing of this batch needs the score matrix - unless a product leaves the fp16 range
+                pairs = self._filter_pairs(ground_truth, triple_mask, triple_id)
+                r = t = None
+                if self.fused_ranks:
+                    assert ground_truth is not None, "Evaluation requires providing ground truth entities"
+                    r = self._ranks_by_counting(inp, ground_truth, triple_mask, triple_id, pairs=pairs)
+                if self.fused_topk and (r is not None or not self.fused_ranks):
+                    t = self._topk_by_lists(inp, triple_mask, pairs)
+                if (r is not None or not self.fused_ranks) and (t is not None or not self.fused_topk):
+                    if r is not None:
+                        metrics.append({m: v.cpu() for m, v in ev.dict_metrics_from_ranks(r).items()})
+                        if ev.return_ranks:
+                            ranks.append(r.cpu())
+                    if t is not None:
+                        topk.append(t.cpu().long())
                     continue
             parts = []
             for i in range(self.bess_module.n_step):

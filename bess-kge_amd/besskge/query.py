@@ -73,6 +73,25 @@ def topk_merge(scores: torch.Tensor, best_s: torch.Tensor, best_i: torch.Tensor,
         best_s.copy_(top_s)
 
 
+def threshold_below(tau: torch.Tensor, half: bool) -> torch.Tensor:
+    """Thresholds for a pruned scoring pass that feeds the ORDERED top-k kernels (`nat.topk_update_excl`): the
+    pass flags a block when a score is > thr, and under the order (score descending, id ascending) a score EQUAL to
+    the k-th may still enter - so thr is the next float below the k-th score `tau`; `half`: the next fp16 value
+    below it (scores are ranked after rounding to fp16, and a score that rounds up to `tau` lies above that value).
+    -inf stays -inf; +inf gives the largest finite value."""
+    ninf = torch.full_like(tau, -torch.inf)
+    if not half:
+        return torch.nextafter(tau, ninf).contiguous()
+    # fp16 spacing at |tau| = m * 2^e, m in [0.5, 1): 2^(e - 11), from 2^-24 (subnormals) up; just below a positive
+    # power of two the spacing is half of that
+    m, e = torch.frexp(tau.abs().clamp(max=65504.0))
+    ulp = torch.ldexp(torch.ones_like(tau), (e - 11).clamp(min=-24))
+    ulp = torch.where(tau == 0, torch.full_like(tau, 2.0 ** -24), ulp)
+    step = torch.where((tau > 0) & (m == 0.5) & (e - 11 > -24), 0.5 * ulp, ulp)
+    thr = torch.where(torch.isinf(tau), torch.where(tau > 0, torch.full_like(tau, 65504.0), ninf), tau - step)
+    return thr.contiguous()
+
+
 class _QueryModule(torch.nn.Module):
     """Shared plumbing: replica group, shard placement, query gathering."""
 
@@ -328,10 +347,12 @@ class AllScoresBESS(_QueryModule):
 
     def forward(self, step: torch.Tensor, relation: torch.Tensor, head: Optional[torch.Tensor] = None,
                 tail: Optional[torch.Tensor] = None, rank_truth: Optional[torch.Tensor] = None,
-                rank_filter: Optional[torch.Tensor] = None) -> torch.Tensor:
+                rank_filter: Optional[torch.Tensor] = None, topk_k: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Scores (shard_bs, n_shard * window_size) of window `step` (one replica); with `rank_truth` the
-        rank counts over all entities instead (`rank_counts_replicas`; `step` is not used then)."""
-        b = dict(step=step, relation=relation, head=head, tail=tail, rank_truth=rank_truth, rank_filter=rank_filter)
+        rank counts over all entities instead (`rank_counts_replicas`), with `topk_k` the k best entities
+        (`topk_replicas`) - `step` is not used then."""
+        b = dict(step=step, relation=relation, head=head, tail=tail, rank_truth=rank_truth, rank_filter=rank_filter,
+                 topk_k=topk_k)
         if len(self._group().local_shards) != 1:
             raise RuntimeError("forward() steps a single replica; use forward_replicas()")
         return self.forward_replicas([{k: v for k, v in b.items() if v is not None}])[0]
@@ -346,9 +367,10 @@ class AllScoresBESS(_QueryModule):
         return cache[dev]
 
     def set_rank_candidates(self, candidate_ents: Optional[Any]) -> None:
-        """Restrict the rank-counting mode to these entities (global ids; None: all) - `candidate_ents` of
-        `AllScoresPipeline` (pipeline.py:101-111): every other entity counts as scoring -inf."""
+        """Restrict the rank-counting and top-k modes to these entities (global ids; None: all) - `candidate_ents`
+        of `AllScoresPipeline` (pipeline.py:101-111): every other entity counts as scoring -inf."""
         self.__dict__.pop("_rank_cand_cache", None)
+        self.__dict__.pop("_topk_id_cache", None)
         self.rank_candidates = None if candidate_ents is None else np.unique(np.asarray(candidate_ents).reshape(-1))
 
     def _rank_candidates_on(self, shard: int, dev: torch.device):
@@ -473,7 +495,128 @@ class AllScoresBESS(_QueryModule):
                             out_of_range=flagged, pos_score=thr[shard].contiguous()))
         return res
 
+    #: bytes of the fp32 score tile [n_query, tile] of the top-k mode - a budget of its own: `window_size`, the
+    #: matrix path's knob, plays no part in it
+    topk_tile_bytes = 256 << 20
+    #: candidates of the first (unpruned) tile of the top-k mode; the next ones double up to the tile size
+    topk_first_tile = 8192
+    #: prune the score tiles of the top-k mode against the running k-th best scores
+    topk_prune = True
+
+    def _topk_ids_on(self, shard: int, dev: torch.device):
+        """(candidate rows of the shard or None: rows 0 .. n - 1, their global entity ids [n] int32): what the top-k
+        pass of this shard runs over - its entities (never its padding rows), or its candidate entities."""
+        cache = self.__dict__.setdefault("_topk_id_cache", {})
+        if (shard, dev) not in cache:
+            sh = self.sharding
+            gid = torch.from_numpy(np.ascontiguousarray(sh.shard_and_idx_to_entity[shard]).astype(np.int32)).to(dev)
+            if getattr(self, "rank_candidates", None) is not None:
+                rows, _ = self._rank_candidates_on(shard, dev)
+                cache[(shard, dev)] = (rows, gid[rows.long()].contiguous())
+            else:
+                cache[(shard, dev)] = (None, gid[: int(sh.shard_counts[shard])].contiguous())
+        return cache[(shard, dev)]
+
+    def topk_replicas(self, batches: List[_Batch]) -> List[Dict[str, torch.Tensor]]:
+        """Top-k mode (`topk_k` in the batch): for every query of the hosted replicas the k best entities over all
+        shards under the order (score descending, global id ascending), with a sparse set of (query, entity) pairs
+        left out - what the reference gets from the window loop, the -inf writes into the `[queries, n_entity]`
+        matrix and one top-k over it (`pipeline.py:233-285`), without that matrix.
+
+        Every shard runs the all-entity pass of `TopKQueryBessKGE`: a first dense score tile, then tiles pruned
+        against the rows' k-th scores (`bess_neg_score_shared_fwd_pruned`) that grow geometrically up to
+        `topk_tile_bytes`; `bess_topk_update_excl` / `_flagged_excl` keep the lists.  Candidates carry global
+        entity ids, the exclusion lists are built on the device from the gathered pairs (the completions that live
+        on the shard; its padding rows are never scored), the shards' lists go back with the all-to-all and are
+        merged by the same ordered kernel: the result does not depend on the sharding or the tiling.
+
+        Inputs next to the query's known entity and relation: `topk_k` [1, 1] int32 (k <= 128); optional
+        `rank_filter` [1, P, 2] int32 pairs (query position in the replica's micro-batch, global id of an entity to
+        leave out; -1 padding) - a pair naming an entity is honoured as given, so a caller that wants the true
+        completion kept leaves it out of the pairs (`pipeline.rank_filter_pairs`); `set_rank_candidates` restricts
+        the pass to a subset.  A half-precision model ranks its scores rounded to fp16, ties included.
+
+        Returns per replica `topk_global_id` [shard_bs, k] int32 and `topk_scores` [shard_bs, k] f32 (slots beyond
+        a query's candidates: id 0, score -inf - as a top-k over the matrix leaves them) and `out_of_range`
+        [shard_bs] bool: some shard's split-fp16 product met operands outside the fp16 range and left its tile to
+        the fp32 kernels (use the score matrix for this batch, as for the counts)."""
+        group = self._group()
+        n = group.n_shard
+        fn = self.score_fn
+        desc = fn.kernel_desc()
+        k = int(batches[0]["topk_k"].reshape(-1)[0])
+        if not 1 <= k <= KERNEL_LIST_MAX:
+            raise ValueError(f"the top-k mode keeps lists of 1 .. {KERNEL_LIST_MAX} entries, got k = {k}")
+        half = fn.relation_embedding.dtype == torch.float16  # (scores leave AllScoresBESS in the model's dtype)
+        queries = self._gather_queries(batches)
+        devs = [self._local_table(s).device for s in group.local_shards]
+        with_filter = batches[0].get("rank_filter") is not None
+        if with_filter:
+            filt_all = group.all_gather([_i32(b["rank_filter"].squeeze(0).to(d)) for b, d in zip(batches, devs)])
+        filters = filt_all if with_filter else [None] * len(queries)
+        n_entity = int(self.sharding.n_entity)
+        best_s, best_i = [], []
+        for shard, q, f in zip(group.local_shards, queries, filters):
+            table = self._local_table(shard)
+            dev = table.device
+            nq = int(q.shape[0])
+            e2s, _, _ = self._entity_maps_on(dev)
+            cand_rows, gid = self._topk_ids_on(shard, dev)
+            n_count = int(gid.numel())
+            excl_ptr = excl_ids = None
+            if f is not None and int(f.shape[1]):  # [n, P, 2]: the pairs of every replica
+                # CSR lists of the filtered completions that live here: pairs sorted by (query, entity), the
+                # others (padding, other shards' entities) after them, where no row's offsets point
+                qi, ent = f[..., 0].long(), f[..., 1].long().reshape(-1)
+                g = (torch.arange(n, device=dev)[:, None] * (nq // n) + qi.clamp(min=0)).reshape(-1)
+                ok = (ent >= 0) & (qi.reshape(-1) >= 0) & (e2s[ent.clamp(min=0)] == shard)
+                key = torch.sort(torch.where(ok, g * n_entity + ent, torch.full_like(g, nq * n_entity))).values
+                excl_ids = (key % n_entity).to(torch.int32)
+                per_row = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+                per_row.index_add_(0, torch.where(ok, g, torch.full_like(g, nq)), torch.ones_like(g))
+                excl_ptr = torch.cat([per_row.new_zeros(1), torch.cumsum(per_row[:nq], 0)]).to(torch.int32)
+            bs = torch.full((nq, k), -torch.inf, dtype=torch.float32, device=dev)
+            bi = torch.full((nq, k), nat.TOPK_ID_NONE, dtype=torch.int32, device=dev)
+            tile = max(64, (self.topk_tile_bytes // 4) // max(1, nq) // 64 * 64)
+            range_flags: List[torch.Tensor] = []
+            w0, step = 0, min(tile, max(64, self.topk_first_tile))
+            while w0 < n_count:
+                w1 = min(n_count, w0 + step)
+                src = RowSource(table[w0:w1]) if cand_rows is None else RowSource(table, cand_rows[w0:w1])
+                ids = gid[w0:w1][None, :]
+                if w0 == 0 or not self.topk_prune:
+                    sc = nat.neg_score_shared_fwd(desc, q, src, pad_ld=True, range_flags=range_flags)
+                    nat.topk_update_excl(sc, bs, bi, ids=ids, excl_ptr=excl_ptr, excl_ids=excl_ids, round_f16=half)
+                else:
+                    # (an equal score may still enter: thresholds strictly below the k-th scores)
+                    thr = threshold_below(bs[:, k - 1], half)
+                    sc, flags = nat.neg_score_shared_fwd_pruned(desc, q, src, thr, range_flags=range_flags)
+                    nat.topk_update_excl(sc, bs, bi, ids=ids, flags=flags, excl_ptr=excl_ptr, excl_ids=excl_ids,
+                                         round_f16=half)
+                w0, step = w1, min(tile, 2 * step)
+            # the range flag of the shard's products travels next to the ids (as the counts' flag column does)
+            bad = torch.stack(range_flags).ne(0).any().to(torch.int32) if range_flags else bi.new_zeros(())
+            best_s.append(bs.reshape(n, -1, k))
+            best_i.append(torch.cat([bi, bad.expand(nq, 1)], dim=1).reshape(n, -1, k + 1))
+        back_s = group.all_to_all(best_s)  # per-query lists back to the query's replica
+        back_i = group.all_to_all(best_i)
+        res = []
+        for s, i in zip(back_s, back_i):
+            dev = s.device
+            shard_bs = int(s.shape[1])
+            flagged = i[..., k].sum(dim=0) > 0
+            flat_s = s.transpose(0, 1).reshape(shard_bs, n * k).contiguous()
+            flat_g = i[..., :k].transpose(0, 1).reshape(shard_bs, n * k).contiguous()
+            top_s = torch.full((shard_bs, k), -torch.inf, dtype=torch.float32, device=dev)
+            top_g = torch.full((shard_bs, k), nat.TOPK_ID_NONE, dtype=torch.int32, device=dev)
+            nat.topk_update_excl(flat_s, top_s, top_g, ids=flat_g)  # (rounded and filtered where they were made)
+            top_g = torch.where(top_s == -torch.inf, torch.zeros_like(top_g), top_g)
+            res.append(dict(topk_global_id=top_g, topk_scores=top_s, out_of_range=flagged))
+        return res
+
     def forward_replicas(self, batches: List[_Batch]) -> List[torch.Tensor]:
+        if batches and batches[0].get("topk_k") is not None:
+            return self.topk_replicas(batches)  # type: ignore[return-value]
         if batches and batches[0].get("rank_truth") is not None:
             return self.rank_counts_replicas(batches)  # type: ignore[return-value]
         group = self._group()

@@ -27,7 +27,7 @@ from besskge.collectives import DistributedGroup, MultiDeviceGroup, NativeGroup,
 _MULTI_PROCESS = (DistributedGroup, NativeGroup)
 
 _BATCH_KEYS = ("head", "relation", "tail", "negative", "triple_mask", "triple_weight", "negative_mask", "step",
-               "rank_truth", "rank_filter")  # (the last two: AllScoresBESS in rank-counting mode)
+               "rank_truth", "rank_filter", "topk_k")  # (the last three: AllScoresBESS counting ranks / keeping top-k lists)
 
 
 @dataclasses.dataclass

@@ -95,6 +95,8 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_loss_fwd_bwd_one_launch),
     BESS_PLAN_FN(bess_topk_update),
     BESS_PLAN_FN(bess_topk_update_flagged),
+    BESS_PLAN_FN(bess_topk_update_excl),
+    BESS_PLAN_FN(bess_topk_update_flagged_excl),
     BESS_PLAN_FN(bess_ranks_from_scores),
     BESS_PLAN_FN(bess_ranks_from_indices),
     BESS_PLAN_FN(bess_scatter_add_rows),

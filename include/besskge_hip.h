@@ -460,6 +460,34 @@ int bess_topk_update_flagged(const float* scores, int64_t n_row, int64_t n_col, 
                              const uint8_t* flags, int64_t ld_flags, int32_t id_base, float* best_score,
                              int32_t* best_id, int32_t kk, void* stream);
 
+/* The two updates above under a total order, with a sparse set of (row, id) pairs left out - the filtered top-k
+ * over all entities (reference pipeline.py:250-285) without the [queries, n_entity] score matrix:
+ *   - order: score descending, then id ascending.  A candidate enters if its score is above the kk-th score, or
+ *     equals it while its id is below the kk-th id, and is placed by the same rule, so the lists do not depend on the
+ *     order of columns, tiles or shards.  An empty entry is (-inf, INT32_MAX): fill the lists with it before the
+ *     first call.  A score of -inf enters only while a list still has such entries; NaN never enters.
+ *   - excl_ptr [n_row + 1], excl_ids [n_excl] (int32; both NULL: nothing is left out): row r leaves out the ids
+ *     excl_ids[excl_ptr[r] .. excl_ptr[r + 1]), ascending, in the id space of the candidates (ids / id_base +
+ *     column).  Only candidates that have passed the test against the kk-th entry are looked up (a binary search
+ *     each), so long lists cost nothing on the chunks that hold no such candidate.  Offsets are clamped to
+ *     [0, n_excl].
+ *   - round_f16 != 0: every score (after the mask's BAD_NEGATIVE_SCORE) is rounded to fp16 before it is compared
+ *     and stored - the ranking a half-precision model makes of its scores, ties included.
+ * bess_topk_update_flagged_excl also takes ids [n_col] (one row shared by all, or NULL: id_base + column).  A caller
+ * that prunes (bess_neg_score_shared_fwd_pruned flags a block when a score is > thr) passes a threshold strictly
+ * below the kk-th score - the next float (round_f16: the next fp16 value) towards -inf - since an equal score may
+ * still enter.  kk <= 128; every layout of the namesakes (four waves per row, two registers per lane) is built. */
+int bess_topk_update_excl(const float* scores, int64_t n_row, int64_t n_col, int64_t ld,
+                          const int32_t* ids, int64_t ids_rows, int32_t id_base,
+                          const uint8_t* mask, int64_t mask_rows, const int32_t* excl_ptr,
+                          const int32_t* excl_ids, int64_t n_excl, int32_t round_f16, float* best_score,
+                          int32_t* best_id, int32_t kk, void* stream);
+int bess_topk_update_flagged_excl(const float* scores, int64_t n_row, int64_t n_col, int64_t ld,
+                                  const uint8_t* flags, int64_t ld_flags, const int32_t* ids, int32_t id_base,
+                                  const int32_t* excl_ptr, const int32_t* excl_ids, int64_t n_excl,
+                                  int32_t round_f16, float* best_score, int32_t* best_id, int32_t kk,
+                                  void* stream);
+
 /* next-2 - prediction ranks (reference metric.py:129-217), fp32 ranks:
  * from scores: 1 + #{cand[s, j] better than pos[s]}, mode 0 optimistic ('>'),
  * 1 pessimistic ('>='), 2 average; from ordered int64 candidate ids: 1-based
