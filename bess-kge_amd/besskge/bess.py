@@ -118,8 +118,10 @@ class _ReplicaStep:
         self.n: int = 1
         self.ppp: int = 0
         self.neg_shape: Tuple[int, ...] = ()  # (n, B, K) of the negative index tensor
-        self.local_neg: torch.Tensor = None  # type: ignore
-        self.local_tail: torch.Tensor = None  # type: ignore
+        # the micro-batch's row ids as they came in, per block: [n | 1, B, K], [n, ppp] (and ScoreMoving's [n, ppp] heads)
+        self.local_neg: Optional[torch.Tensor] = None
+        self.local_tail: Optional[torch.Tensor] = None
+        self.sm_head: Optional[torch.Tensor] = None
         self.positive_score: torch.Tensor = None  # type: ignore
         self.negative_score: torch.Tensor = None  # type: ignore
         self.loss_norm: Optional[torch.Tensor] = None  # [S, 2] (m, L / C) of each triple's softmax (ScoreMoving, fused)
@@ -138,6 +140,31 @@ class _ReplicaStep:
         self.direct: Any = None
         self.direct_lists: List[torch.Tensor] = []
         self.jobs_ride = False  # the step's copy / fill jobs go with the query / positive-score launch
+
+
+class _StepContext:
+    """What one call has decided about the step it runs, handed down as an argument to everything that acts on it.
+    `train_step_replicas` makes one per micro-batch, the inference entry points the default one (a plain forward).
+    It lives as long as the call: nothing of a step stays on the module."""
+
+    __slots__ = ("batches", "training", "grad_scale", "fuse", "sm_fuse", "optimizer", "seg_ahead", "small_ahead", "d_rel")
+
+    def __init__(self, batches: Optional[List[_Batch]] = None, training: bool = False, grad_scale: float = 1.0) -> None:
+        # the caller's batches (masks, weights), one per hosted replica: K7 may then be applied by the scoring call
+        # itself.  None (`score_batch`): the scores come back unmasked, like the reference's
+        self.batches = batches
+        self.training = training  # (EmbeddingMoving: K8 may run behind the scoring call; ScoreMoving: no finished queries)
+        self.grad_scale = grad_scale  # gradients averaged over accumulated micro-batches: a scaled triple weight
+        self.fuse: Optional[List[Optional[Dict[str, Any]]]] = None  # per replica: `_training_context`
+        self.sm_fuse: Any = None  # ScoreMoving, fusable loss: loss.kernel_desc - the shards keep softmax partials
+        self.optimizer: Any = None  # what the step's prologue plans the update for
+        # {id(group): SegmentIndex of its per-triple negatives}, started on the side stream before the scoring kernel
+        # is queued.  None: not wanted (inference; accumulating - indexed when the sum is applied)
+        self.seg_ahead: Optional[Dict[int, Any]] = None
+        # {id(replica step): (row-id lists, their SegmentIndex)} of the small update lists, from the step's prologue
+        # launch or the side stream.  None: no prologue (inference, ScoreMoving, accumulating)
+        self.small_ahead: Optional[Dict[int, Any]] = None
+        self.d_rel: Optional[torch.Tensor] = None  # relation gradient, allocated and cleared by the prologue
 
 
 class _PendingUpdate:
@@ -273,10 +300,9 @@ class BessKGE(torch.nn.Module, ABC):
             torch.cuda.current_stream(device).synchronize()
         return cache[device]
 
-    def _triple_weight(self, batch: _Batch, device: torch.device) -> torch.Tensor:
-        """Weights of the micro-batch's triples in the loss ([1] or [S], fp32), times the step's
-        gradient scale (1 unless gradients are averaged over accumulated micro-batches / replicas)."""
-        scale = self.__dict__.get("_grad_scale", 1.0)
+    def _triple_weight(self, batch: _Batch, device: torch.device, scale: float = 1.0) -> torch.Tensor:
+        """Weights of the micro-batch's triples in the loss ([1] or [S], fp32), times the step's gradient
+        scale (`_StepContext.grad_scale`: 1 unless gradients are averaged over accumulated micro-batches)."""
         w = batch.get("triple_weight")
         if w is None:
             if scale == 1.0:
@@ -337,7 +363,7 @@ class BessKGE(torch.nn.Module, ABC):
 
     def forward_replicas(self, batches: List[_Batch]) -> List[Dict[str, Any]]:
         """Lock-step forward of all replicas hosted by this process."""
-        steps = self._score_replicas(batches)
+        steps = self._score_replicas(batches, _StepContext(batches))
         return [self._finish(st, b, want_grad=False)[0] for st, b in zip(steps, batches)]
 
     # Two-phase form of forward_replicas for software pipelining over micro-batches:
@@ -351,7 +377,7 @@ class BessKGE(torch.nn.Module, ABC):
     def forward_finish(self, ctx: Dict[str, Any]) -> List[Dict[str, Any]]:
         return self.forward_replicas(ctx["batches"])
 
-    def _score_replicas(self, batches: List[_Batch]) -> List[_ReplicaStep]:
+    def _score_replicas(self, batches: List[_Batch], ctx: _StepContext) -> List[_ReplicaStep]:
         group = self._group()
         if len(batches) != len(group.local_shards):
             raise ValueError(f"{len(batches)} batches for {len(group.local_shards)} local replicas")
@@ -360,12 +386,8 @@ class BessKGE(torch.nn.Module, ABC):
             for k in ("head", "relation", "tail", "negative"):
                 if b[k].shape[0] != 1:
                     raise ValueError(f"`{k}` must have a leading replica dim of 1, got {tuple(b[k].shape)}")
-            sq: Dict[str, Any] = {k: _i32(b[k].squeeze(0)) for k in ("head", "relation", "tail", "negative")}
-            # forward / training step: K7 may be applied by the scoring call itself (`score_batch` keeps
-            # returning the unmasked scores, like the reference's)
-            sq["_kill_from"] = b
-            squeezed.append(sq)
-        return self.score_batch_replicas(squeezed)
+            squeezed.append({k: _i32(b[k].squeeze(0)) for k in ("head", "relation", "tail", "negative")})
+        return self.score_batch_replicas(squeezed, ctx=ctx)
 
     def score_batch(
         self, head: torch.Tensor, relation: torch.Tensor, tail: torch.Tensor, negative: torch.Tensor
@@ -380,12 +402,12 @@ class BessKGE(torch.nn.Module, ABC):
         return st.positive_score, st.negative_score
 
     @abstractmethod
-    def score_batch_replicas(self, batches: List[_Batch]) -> List[_ReplicaStep]:
-        """Scores of every local replica's micro-batch (lock-step)."""
+    def score_batch_replicas(self, batches: List[_Batch], ctx: Optional[_StepContext] = None) -> List[_ReplicaStep]:
+        """Scores of every local replica's micro-batch (lock-step); `ctx` default: plain scores, unmasked."""
         raise NotImplementedError
 
     # -------------------------------------------------- mask / loss / metrics
-    def _finish(self, st: _ReplicaStep, batch: _Batch, want_grad: bool, want_norm: bool = False
+    def _finish(self, st: _ReplicaStep, batch: _Batch, want_grad: bool, want_norm: bool = False, scale: float = 1.0
                 ) -> Tuple[Dict[str, Any], Optional[torch.Tensor], Optional[torch.Tensor]]:
         pos, neg = st.positive_score, st.negative_score
         dev = pos.device
@@ -402,7 +424,7 @@ class BessKGE(torch.nn.Module, ABC):
         ret_neg = neg
         d_pos = d_neg = None
         if self.loss_fn:
-            w = self._triple_weight(batch, dev)
+            w = self._triple_weight(batch, dev, scale)
             ld = self.loss_fn.kernel_desc(int(neg.shape[1]))
             if st.loss_pre is not None and not want_norm:  # the scoring call has done K8 already
                 loss, d_pos, d_neg = st.loss_pre
@@ -410,7 +432,6 @@ class BessKGE(torch.nn.Module, ABC):
                 loss, d_pos, d_neg, st.loss_norm = nat.loss_fwd_bwd(ld, pos, neg, w, want_grad, want_norm=True)
             else:
                 loss, d_pos, d_neg = nat.loss_fwd_bwd(ld, pos, neg, w, want_grad)
-            scale = self.__dict__.get("_grad_scale", 1.0)
             # (gradients averaged over accumulated micro-batches / replicas travel as a scaled triple weight;
             # the value handed back stays the micro-batch's own loss)
             out["loss"] = loss if scale == 1.0 else loss / scale
@@ -457,6 +478,12 @@ class BessKGE(torch.nn.Module, ABC):
         return None
 
     # ------------------------------------------------------- optimiser step
+    @staticmethod
+    def _plain_lr(optimizer: Any) -> Tuple[bool, float]:
+        """(plain SGD?, learning rate) of a training step's `optimizer`: a bare learning rate or a `besskge.runtime` one."""
+        plain = not hasattr(optimizer, "kind") or optimizer.is_plain_sgd
+        return plain, float(optimizer.lr) if hasattr(optimizer, "lr") else float(optimizer)
+
     def _opt_state(self, table: torch.Tensor, n_state: int, state_rows: Optional[int] = None) -> Dict[str, Any]:
         """Lazily allocated per-row optimiser state of one table.  `state_rows` (the optimiser's
         `state_rows` option; only for tables with more rows than that): paged state - pools of that
@@ -586,7 +613,7 @@ class BessKGE(torch.nn.Module, ABC):
         reduced by the segmented K9 in a way that leaves the lists unknown until the backward has run).  A
         candidate list that the step's prologue concatenates is named by its parts: the index is built in the
         same launch, from the lists as the sampler handed them over."""
-        plain = not hasattr(optimizer, "kind") or optimizer.is_plain_sgd
+        plain, _ = self._plain_lr(optimizer)
         if plain and self.score_fn.entity_embedding.dtype == torch.float32:
             return None
         fn = self.score_fn
@@ -676,8 +703,7 @@ class BessKGE(torch.nn.Module, ABC):
         g = st.groups[0]
         if not g.shared or g.neg.base is not st.table or g.neg.idx is None or st.tail.base is not st.table:
             return False
-        plain = not hasattr(optimizer, "kind") or optimizer.is_plain_sgd
-        if plain and st.table.dtype == torch.float32:
+        if self._plain_lr(optimizer)[0] and st.table.dtype == torch.float32:
             return False
         if getattr(optimizer, "dense", False):
             return False  # (every row is stepped: `_apply_dense`)
@@ -771,10 +797,11 @@ class BessKGE(torch.nn.Module, ABC):
                     lists.append(nat.pad_segments(seg, gseg))
             for i in range(0, len(lists), nat.MAX_ROW_LISTS):
                 nat.sparse_sgd_lists(acc, lists[i: i + nat.MAX_ROW_LISTS], -1.0)  # acc += rows (fp32 atomics)
-            if hasattr(optimizer, "kind") and not optimizer.is_plain_sgd:
-                self._apply_optimizer_dense(optimizer, st.table, acc)
+            plain, lr = self._plain_lr(optimizer)
+            if plain:
+                nat.dense_sgd(st.table, acc, lr)
             else:
-                nat.dense_sgd(st.table, acc, float(optimizer.lr) if hasattr(optimizer, "lr") else float(optimizer))
+                self._apply_optimizer_dense(optimizer, st.table, acc)
             nat.step_prologue([(acc, None, 0)])  # back to zero for the next step
 
     def _apply_optimizer_dense(self, opt: Any, table: torch.Tensor, grad: torch.Tensor) -> None:
@@ -825,11 +852,11 @@ class BessKGE(torch.nn.Module, ABC):
             return nat.SegmentIndex(g.neg.idx, st.table.shape[0], width=st.table.shape[1],
                                     scratch=self.__dict__.setdefault("_seg_scratch", {}))
 
-    def _prefetch_segment_indices(self, steps: List[_ReplicaStep]) -> Dict[int, Any]:
+    def _prefetch_segment_indices(self, steps: List[_ReplicaStep], ctx: _StepContext) -> Dict[int, Any]:
         """The inverted indices of per-triple negatives only depend on the sampled indices: they are
         built on a side stream while the forward kernels run (`_run_groups_one` starts them before the
-        scoring kernel of their group is queued; groups scored elsewhere are started here)."""
-        seg_index: Dict[int, Any] = dict(getattr(self, "_seg_ahead", None) or {})
+        scoring kernel of their group is queued - `ctx.seg_ahead`; groups scored elsewhere are started here)."""
+        seg_index: Dict[int, Any] = dict(ctx.seg_ahead or {})
         for st in steps:
             for g in st.groups:
                 if self._wants_segments(g, st) and id(g) not in seg_index:
@@ -875,19 +902,28 @@ class BessKGE(torch.nn.Module, ABC):
                 idx = torch.cat([g.neg.idx.reshape(-1) for _, g, _ in items])
             seg_index[id(merged)] = nat.SegmentIndex(idx, table.shape[0], width=table.shape[1], scratch=scratch)
             deferred.append((table, merged, go))
-        self.__dict__["_small_ahead"] = None
-        self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, self.score_fn.kernel_desc(),
-                            first.d_rel)
+        self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, self.score_fn.kernel_desc(), first.d_rel)
         pending.clear()
+
+    def _relation_gradient(self, ctx: _StepContext, pending: Optional[List[_PendingUpdate]]) -> torch.Tensor:
+        """Where a micro-batch sums its relation gradient: the buffer of the first micro-batch of the update it
+        accumulates into, the one the step's prologue has cleared, or a fresh zero one."""
+        if pending:
+            return pending[0].d_rel
+        if ctx.d_rel is not None:
+            return ctx.d_rel
+        rel_table = self.score_fn.relation_embedding.data
+        return torch.zeros(rel_table.shape, dtype=torch.float32, device=rel_table.device)
 
     def _apply_updates(self, steps: List[_ReplicaStep], local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]],
                        deferred: List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]], seg_index: Dict[int, Any],
-                       optimizer: Any, desc: nat.ModelDesc, d_rel: torch.Tensor) -> None:
-        """K9 + K10 on every hosted shard and C9 + update of the relation table."""
+                       optimizer: Any, desc: nat.ModelDesc, d_rel: torch.Tensor,
+                       small_ahead: Optional[Dict[int, Any]] = None) -> None:
+        """K9 + K10 on every hosted shard and C9 + update of the relation table (`small_ahead`: the step's)."""
         group = self._group()
         rel_table = self.score_fn.relation_embedding.data
-        plain = not hasattr(optimizer, "kind") or optimizer.is_plain_sgd
-        lr = float(optimizer.lr) if hasattr(optimizer, "lr") else float(optimizer)
+        small_ahead = small_ahead or {}
+        plain, lr = self._plain_lr(optimizer)
         # f16 shards: a packed-f16 atomic add rounds the row once per contribution.  Plain SGD on them
         # therefore takes the coalescing path of the stateful optimisers: contributions summed per unique
         # row in fp32, one read-modify-write (one rounding) per touched row and step.
@@ -967,7 +1003,7 @@ class BessKGE(torch.nn.Module, ABC):
                 if native and len(mine) == 1:
                     table, g, go = mine[0]
                     self._apply_optimizer_fused(optimizer, desc, table, g, go, seg_index[id(g)], list(upd),
-                                                (getattr(self, "_small_ahead", None) or {}).get(id(st)))
+                                                small_ahead.get(id(st)))
                     continue
                 contrib = list(upd)
                 for table, g, go in deferred:
@@ -979,8 +1015,7 @@ class BessKGE(torch.nn.Module, ABC):
                         # count: no host sync, and the step can be recorded into a hipGraph)
                         contrib.append(nat.pad_segments(seg, gseg))
                 last = st is steps[-1]
-                self._apply_optimizer(optimizer, st.table, contrib,
-                                      (getattr(self, "_small_ahead", None) or {}).get(id(st)),
+                self._apply_optimizer(optimizer, st.table, contrib, small_ahead.get(id(st)),
                                       axpy=rel_axpy if last else None)
                 rel_done = rel_done or (last and rel_axpy is not None)
         if rel_done:
@@ -1007,21 +1042,20 @@ class BessKGE(torch.nn.Module, ABC):
 
 
     # ------------------------------------------------------ group execution
-    def _run_groups_one(self, g: _NegGroup, desc: nat.ModelDesc, st: Optional[_ReplicaStep] = None,
-                        fuse: Optional[Dict[str, Any]] = None, partials_loss: Any = None) -> torch.Tensor:
-        ahead = getattr(self, "_seg_ahead", None)
-        if ahead is not None and st is not None and self._wants_segments(g, st):
+    def _run_groups_one(self, g: _NegGroup, desc: nat.ModelDesc, ctx: _StepContext, st: Optional[_ReplicaStep] = None,
+                        fuse: Optional[Dict[str, Any]] = None, partials_loss: Any = None,
+                        loss_batch: Optional[_Batch] = None) -> torch.Tensor:
+        """`fuse`: the replica's entry of `ctx.fuse`, unless K7 has to follow the pass; `partials_loss`: ScoreMoving's
+        `ctx.sm_fuse(n)`; `loss_batch`: the replica's batch when K8 may run behind the scoring call (shared negatives)."""
+        if ctx.seg_ahead is not None and st is not None and self._wants_segments(g, st):
             # training: the inverted index of the negatives only needs their row ids - start it on the
             # side stream *before* the scoring kernel is queued, so that it runs under it
-            ahead[id(g)] = self._segment_index_on_side(g, st)
+            ctx.seg_ahead[id(g)] = self._segment_index_on_side(g, st)
         if g.query is None:
             g.query, g.query_ctx = self.score_fn.query_fwd(g.side, g.ent, g.rel_idx)
-        with_loss = getattr(self, "_train_loss_in_scoring", None)
-        if g.shared and with_loss is not None and st is not None and len(st.groups) == 1 and g.sel is None \
-                and (st.kill_applied or with_loss.get("no_kill")):
+        if g.shared and loss_batch is not None and st is not None and len(st.groups) == 1 and g.sel is None:
             # training: K4 + K7 + K8 behind one call (one launch for the packed L1 kernel at notebook sizes)
-            b = with_loss["batch"]
-            w = self._triple_weight(b, g.query.device)
+            w = self._triple_weight(loss_batch, g.query.device, ctx.grad_scale)
             g.out, loss, d_pos, d_neg = nat.neg_score_shared_fwd_loss(
                 desc, self.loss_fn.kernel_desc(len(g.neg)), g.query, g.neg, st.positive_score, w, kill=g.kill)
             st.loss_pre = (loss, d_pos, d_neg)
@@ -1039,7 +1073,7 @@ class BessKGE(torch.nn.Module, ABC):
                 w = w if w.numel() == 1 else w[g.sel].contiguous()
             # one group over all triples of the own shard, query + positive score out of one launch: everything
             # per triple that follows - d loss / d query from the pass's partials, K8, K3' + K6' - is ONE more launch
-            d_rel = self.__dict__.get("_step_d_rel")
+            d_rel = ctx.d_rel
             defer = (self.pertriple_tail and st.fused_qt and g.sel is None and g.neg.base is st.table and d_rel is not None
                      and not self.evaluation and nat.pertriple_tail_supported(desc, g.n_per_query))
             ldesc = fuse["loss"](g.n_per_query)
@@ -1059,22 +1093,43 @@ class BessKGE(torch.nn.Module, ABC):
             g.out = nat.neg_score_pertriple_fwd(desc, g.query, g.neg, g.n_per_query)
         return g.out
 
-    def _run_groups(self, st: _ReplicaStep, desc: nat.ModelDesc, fuse: Optional[Dict[str, Any]] = None
-                    ) -> List[torch.Tensor]:
-        return [self._run_groups_one(g, desc, st, fuse) for g in st.groups]
+    def _run_groups(self, st: _ReplicaStep, desc: nat.ModelDesc, ctx: _StepContext,
+                    fuse: Optional[Dict[str, Any]] = None, loss_batch: Optional[_Batch] = None) -> List[torch.Tensor]:
+        return [self._run_groups_one(g, desc, ctx, st, fuse, loss_batch=loss_batch) for g in st.groups]
 
     def _fusable(self, batch: _Batch) -> Optional[Dict[str, Any]]:
         """Can the training forward of this micro-batch also produce d loss / d query?  Needs a
-        loss taken over exactly the scores of one per-triple group, with nothing masked."""
+        loss taken over exactly the scores of one per-triple group, with nothing masked.  An override returns a dict
+        of its own per call or None: the step adds the triples' weights to it as `weight` (`_training_context`)."""
         if self.loss_fn is None or not self.score_fn.supports_fused_forward or self.augment_negative:
             return None
         if not hasattr(self.loss_fn, "kernel_desc") or not nat.row_fits_registers(self.score_fn.kernel_desc()):
             return None  # (rows wider than a group's registers are scored in column windows: two-pass path)
-        dev = self.score_fn.relation_embedding.device
-        w = self._triple_weight(batch, dev)
         # a negative_mask (the padding of triple-specific negatives) is applied inside the fused pass when it
-        # has one row or one per triple (`_run_groups_one`); other layouts take the two-pass path
-        return dict(weight=w, loss=self.loss_fn.kernel_desc, masked=batch.get("negative_mask") is not None)
+        # has one row or one per triple (`score_batch_replicas`); other layouts take the two-pass path
+        return dict(loss=self.loss_fn.kernel_desc, masked=batch.get("negative_mask") is not None)
+
+    # ---------------------------------------------------------------- training
+    def _training_context(self, batches: List[_Batch], optimizer: Any, pending: Optional[List[_PendingUpdate]],
+                          grad_scale: float) -> _StepContext:
+        """The context of one training micro-batch, as far as both schemes decide the same: `fuse` is `_fusable`
+        of every replica's batch plus the triples' weights in the loss (times the gradient scale)."""
+        if self.loss_fn is None:
+            raise RuntimeError("train_step needs a loss function")
+        ctx = _StepContext(batches, training=True, grad_scale=grad_scale)
+        ctx.optimizer = optimizer
+        ctx.fuse = [self._fusable(b) for b in batches]
+        dev = self.score_fn.relation_embedding.device
+        for f, b in zip(ctx.fuse, batches):
+            if f is not None:
+                f["weight"] = self._triple_weight(b, dev, grad_scale)
+        if pending is None:  # (accumulating: the references of all micro-batches are indexed together when applied)
+            ctx.seg_ahead = {}
+        return ctx
+
+    def train_step(self, optimizer: Any, **batch: torch.Tensor) -> Dict[str, Any]:
+        """Single-replica convenience wrapper of `train_step_replicas`."""
+        return self.train_step_replicas([batch], optimizer)[0]
 
 
 class EmbeddingMovingBessKGE(BessKGE):
@@ -1087,7 +1142,8 @@ class EmbeddingMovingBessKGE(BessKGE):
     (reference `bess.py:308-468`).
     """
 
-    def score_batch_replicas(self, batches: List[_Batch]) -> List[_ReplicaStep]:
+    def score_batch_replicas(self, batches: List[_Batch], ctx: Optional[_StepContext] = None) -> List[_ReplicaStep]:
+        ctx = ctx or _StepContext()
         group = self._group()
         n = group.n_shard
         ns = self.negative_sampler
@@ -1099,10 +1155,10 @@ class EmbeddingMovingBessKGE(BessKGE):
         # NativeGroup: gather into the send buffer + all-to-all behind one entry point (bess_pack_exchange)
         packed_exchange = (hasattr(group, "pack_exchange")
                            and (W * self.score_fn.entity_embedding.element_size()) % 16 == 0)
-        prologue = self.__dict__.get("_small_early") is not None  # a training step that applies its own update
+        early = ctx.small_ahead  # not None: a training step that applies its own update
         for shard, b in zip(group.local_shards, batches):
             st = _ReplicaStep()
-            if prologue:
+            if early is not None:
                 st.jobs = []
             st.table = self._local_table(shard)
             dev = st.table.device
@@ -1121,8 +1177,7 @@ class EmbeddingMovingBessKGE(BessKGE):
                     sends.append(group.pack_exchange(st.table, st.send_idx))  # K1 + C1, one native call
                 else:
                     sends.append(nat.gather_rows(st.table, st.send_idx.reshape(-1)).reshape(n, -1, W))
-            st.local_neg = neg  # type: ignore
-            st.local_tail = tail  # type: ignore
+            st.local_neg, st.local_tail = neg, tail
             steps.append(st)
         if n > 1:
             recvs = sends if packed_exchange else group.all_to_all(sends)  # C1
@@ -1132,26 +1187,24 @@ class EmbeddingMovingBessKGE(BessKGE):
 
         desc = fn.kernel_desc()
         rel_table = fn.relation_embedding.data
-        done: List[_ReplicaStep] = []
-        fuse = getattr(self, "_train_fuse", None)
-        for st, b in zip(steps, batches):
+        k8_in_scoring = (ctx.training and self.loss_fn is not None and hasattr(self.loss_fn, "kernel_desc")
+                         and not self.evaluation)
+        for i, st in enumerate(steps):
             self._build_groups(st, exchange_negatives)
-            src = b.get("_kill_from")
+            src = ctx.batches[i] if ctx.batches is not None else None  # the caller's batch: masks, weights
             if src is not None and len(st.groups) == 1 and st.groups[0].shared:
                 st.groups[0].kill = self._kill_spec(src, st.n, st.ppp, st.n * st.ppp, st.table.device)
                 st.kill_applied = st.groups[0].kill is not None
             g0 = st.groups[0]
             st.fused_qt = (len(st.groups) == 1 and g0.sel is None and fn.supports_fused_query_triple
                            and st.tail.base.dtype == st.table.dtype)
-            early = getattr(self, "_small_early", None)
             if early is not None:
                 # training: what the step's kernels need prepared - the concatenated candidate list, cleared
                 # gradient targets, the index of the small update lists (it needs only row ids) - in ONE launch
                 d_rel = None
-                if not done:  # the relation gradient is shared by the replicas hosted here
-                    d_rel = self.__dict__["_step_d_rel"] = torch.empty(rel_table.shape, dtype=torch.float32,
-                                                                       device=rel_table.device)
-                ahead = self._launch_prologue(st, self._ahead_optimizer, d_rel)
+                if i == 0:  # the relation gradient is shared by the replicas hosted here
+                    d_rel = ctx.d_rel = torch.empty(rel_table.shape, dtype=torch.float32, device=rel_table.device)
+                ahead = self._launch_prologue(st, ctx.optimizer, d_rel)
                 if ahead is not None:
                     early[id(st)] = ahead
             if st.fused_qt:
@@ -1165,13 +1218,11 @@ class EmbeddingMovingBessKGE(BessKGE):
                     RowSource(st.table, st.head_idx), st.tail, st.rel_idx)
             if early is not None and id(st) not in early:
                 # longer lists: indexed on the side stream, started before the scoring kernels are queued
-                early.update(self._small_index_ahead([st], self._ahead_optimizer))
-            fz = fuse[len(done)] if fuse else None
+                early.update(self._small_index_ahead([st], ctx.optimizer))
+            fz = ctx.fuse[i] if ctx.fuse else None
             if fz is not None and fz.get("masked"):
                 # K7 inside the fused pass: one per-triple group over all triples, a mask of 1 or S rows, no 'ht' halves
-                kill = self._kill_spec(b["_kill_from"], st.n, st.ppp, st.n * st.ppp, st.table.device) \
-                    if b.get("_kill_from") is not None else None
-                g0 = st.groups[0]
+                kill = self._kill_spec(src, st.n, st.ppp, st.n * st.ppp, st.table.device) if src is not None else None
                 ok = (kill is not None and kill[0] == 0 and not kill[1] and kill[3] is not None
                       and kill[3].shape[0] in (1, st.n * st.ppp) and len(st.groups) == 1 and g0.sel is None
                       and not g0.shared and g0.neg.base is st.table and kill[3].shape[1] <= g0.n_per_query)
@@ -1180,18 +1231,10 @@ class EmbeddingMovingBessKGE(BessKGE):
                     st.kill_applied = True
                 else:
                     fz = None  # two-pass path: scores, K7, loss, backward
-            in_scoring = self.__dict__.get("_train_loss_in_scoring_on")
-            if in_scoring and self.loss_fn is not None and hasattr(self.loss_fn, "kernel_desc") and not self.evaluation:
-                src_b = b.get("_kill_from")
-                if src_b is not None:
-                    no_kill = (not st.kill_applied
-                               and self._kill_spec(src_b, st.n, st.ppp, st.n * st.ppp, st.table.device) is None)
-                    self.__dict__["_train_loss_in_scoring"] = dict(batch=src_b, no_kill=no_kill)
-            try:
-                outs = self._run_groups(st, desc, fz)
-            finally:
-                self.__dict__["_train_loss_in_scoring"] = None
-            done.append(st)
+            # K8 behind the scoring call: when K7 went with the scores, or there is nothing to kill
+            k8_here = k8_in_scoring and src is not None and (
+                st.kill_applied or self._kill_spec(src, st.n, st.ppp, st.n * st.ppp, st.table.device) is None)
+            outs = self._run_groups(st, desc, ctx, fz, src if k8_here else None)
             if len(outs) == 1:
                 st.negative_score = outs[0]
             else:
@@ -1216,9 +1259,9 @@ class EmbeddingMovingBessKGE(BessKGE):
 
         # --- where do tails and negatives live?
         if n == 1:
-            tail_src = RowSource(st.table, st.local_tail.reshape(-1))  # type: ignore
+            tail_src = RowSource(st.table, st.local_tail.reshape(-1))
             neg_base = st.table
-            neg_idx2d = st.local_neg[0]  # type: ignore  # [B, K]
+            neg_idx2d = st.local_neg[0]  # [B, K]
         else:
             L = ppp + (B * K if exchange_negatives else 0)
             tail_map = self._static_map(
@@ -1235,7 +1278,7 @@ class EmbeddingMovingBessKGE(BessKGE):
                              ).reshape(B, n * K), dev)
             else:
                 neg_base = st.table
-                neg_idx2d = st.local_neg.transpose(0, 1).reshape(B, n * K).contiguous()  # type: ignore
+                neg_idx2d = st.local_neg.transpose(0, 1).reshape(B, n * K).contiguous()
         st.tail = tail_src
         head_src = RowSource(st.table, st.head_idx)
         nK = int(neg_idx2d.shape[1])
@@ -1324,63 +1367,42 @@ class EmbeddingMovingBessKGE(BessKGE):
             raise ValueError(f"corruption scheme {scheme!r} not supported")
 
     # ---------------------------------------------------------------- training
-    def train_step_replicas(self, batches: List[_Batch], optimizer: Any,
-                            pending: Optional[List[_PendingUpdate]] = None) -> List[Dict[str, Any]]:
+    def train_step_replicas(self, batches: List[_Batch], optimizer: Any, pending: Optional[List[_PendingUpdate]] = None,
+                            grad_scale: float = 1.0) -> List[Dict[str, Any]]:
         """Forward + backward + sparse optimiser update of every local replica.
 
         `optimizer`: a learning rate (plain SGD) or one of
         `besskge.runtime.{SGD, Adagrad, Adam}`.  `pending` (gradient accumulation): a list the
         micro-batch's gradients are appended to instead of being applied; `apply_accumulated`
-        applies the sum of what it holds in one optimiser step.
+        applies the sum of what it holds in one optimiser step.  `grad_scale`: factor on the micro-batch's
+        gradients (1 / k for the mean over k accumulated micro-batches); the loss handed back is not scaled.
 
         Backward of the reference's autograd graph (`bess.py:322-468`) written
         out: K8' -> K4'/K5' -> K6' -> K3' give the gradient of every gathered
         row; rows received through the all-to-all are returned to their owner
         by a second all-to-all (C8); K9+K10 apply them to the shard sparsely.
         """
-        if self.loss_fn is None:
-            raise RuntimeError("train_step needs a loss function")
-        plain = not hasattr(optimizer, "kind") or optimizer.is_plain_sgd
-        lr = float(optimizer.lr) if hasattr(optimizer, "lr") else float(optimizer)
+        ctx = self._training_context(batches, optimizer, pending, grad_scale)
+        if pending is None:  # a step that applies its own update: the prologue launch prepares it
+            ctx.small_ahead = {}
         group = self._group()
         fn = self.score_fn
         n = group.n_shard
         W = self.entity_embedding_size
-        # (per-step scratch goes straight into the instance dict: nn.Module.__setattr__ costs ~2.5 us a piece)
-        accumulating = pending is not None
-        self.__dict__["_train_fuse"] = [self._fusable(b) for b in batches]
-        # (accumulating: the references of all micro-batches are indexed together when they are applied)
-        self.__dict__["_seg_ahead"] = None if accumulating else {}
-        self.__dict__["_small_early"] = None if accumulating else {}
-        self.__dict__["_ahead_optimizer"] = optimizer
-        self.__dict__["_train_loss_in_scoring_on"] = True
-        try:
-            steps = self._score_replicas(batches)
-            seg_index = {} if accumulating else self._prefetch_segment_indices(steps)
-            self.__dict__["_small_ahead"] = dict(self._small_early or {})
-        finally:
-            self.__dict__["_train_fuse"] = None
-            self.__dict__["_seg_ahead"] = None
-            self.__dict__["_small_early"] = None
-            self.__dict__["_ahead_optimizer"] = None
-            self.__dict__["_train_loss_in_scoring_on"] = False
-        if not accumulating:
-            self._small_ahead.update(self._small_index_ahead([st for st in steps if id(st) not in self._small_ahead],
-                                                             optimizer))
+        steps = self._score_replicas(batches, ctx)
+        seg_index = {} if pending is not None else self._prefetch_segment_indices(steps, ctx)
+        if pending is None:
+            ctx.small_ahead.update(self._small_index_ahead([st for st in steps if id(st) not in ctx.small_ahead],
+                                                           optimizer))
         desc = fn.kernel_desc()
-        rel_table = fn.relation_embedding.data
         results = []
         # (the relation gradient of accumulated micro-batches is summed in the first one's buffer)
-        d_rel = self.__dict__.pop("_step_d_rel", None)  # allocated and cleared by the step's prologue launch
-        if pending:
-            d_rel = pending[0].d_rel
-        elif d_rel is None:
-            d_rel = torch.zeros(rel_table.shape, dtype=torch.float32, device=rel_table.device)
+        d_rel = self._relation_gradient(ctx, pending)
         back: List[torch.Tensor] = []
         deferred: List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]] = []
         local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]] = []
         for st, b in zip(steps, batches):
-            out, d_pos, d_neg = self._finish(st, b, want_grad=True)
+            out, d_pos, d_neg = self._finish(st, b, want_grad=True, scale=grad_scale)
             results.append(out)
             dev = st.table.device
             upd: List[Tuple[torch.Tensor, torch.Tensor]] = []  # (rows of my shard, gradient rows)
@@ -1481,19 +1503,11 @@ class EmbeddingMovingBessKGE(BessKGE):
             returned = group.all_to_all(back)  # C8
             for st, upd, g in zip(steps, local_updates, returned):
                 upd.append((st.send_idx.reshape(-1), g.reshape(-1, W)))
-        if accumulating:
-            self.__dict__["_small_ahead"] = None
+        if pending is not None:
             pending.append(_PendingUpdate(steps, local_updates, deferred, d_rel))
-            return results
-        try:
-            self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, desc, d_rel)
-        finally:
-            self.__dict__["_small_ahead"] = None
+        else:
+            self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, desc, d_rel, ctx.small_ahead)
         return results
-
-    def train_step(self, optimizer: Any, **batch: torch.Tensor) -> Dict[str, Any]:
-        """Single-replica convenience wrapper of :meth:`train_step_replicas`."""
-        return self.train_step_replicas([batch], optimizer)[0]
 
 
 class ScoreMovingBessKGE(BessKGE):
@@ -1504,23 +1518,24 @@ class ScoreMovingBessKGE(BessKGE):
     negatives documented for :class:`EmbeddingMovingBessKGE`.
     """
 
-    def score_batch_replicas(self, batches: List[_Batch]) -> List[_ReplicaStep]:
-        return self._score_finish(self._score_begin(batches))
+    def score_batch_replicas(self, batches: List[_Batch], ctx: Optional[_StepContext] = None) -> List[_ReplicaStep]:
+        ctx = ctx or _StepContext()
+        return self._score_finish(self._score_begin(batches, ctx), ctx)
 
     def forward_begin(self, batches: List[_Batch]) -> Dict[str, Any]:
         group = self._group()
         if len(batches) != len(group.local_shards):
             raise ValueError(f"{len(batches)} batches for {len(group.local_shards)} local replicas")
         squeezed = [{k: _i32(b[k].squeeze(0)) for k in ("head", "relation", "tail", "negative")} for b in batches]
-        ctx = self._score_begin(squeezed)
-        ctx["batches"] = batches
-        return ctx
+        begun = self._score_begin(squeezed, _StepContext())
+        begun["batches"] = batches
+        return begun
 
     def forward_finish(self, ctx: Dict[str, Any]) -> List[Dict[str, Any]]:
-        steps = self._score_finish(ctx)
+        steps = self._score_finish(ctx, _StepContext())
         return [self._finish(st, b, want_grad=False)[0] for st, b in zip(steps, ctx["batches"])]
 
-    def _score_begin(self, batches: List[_Batch]) -> Dict[str, Any]:
+    def _score_begin(self, batches: List[_Batch], ctx: _StepContext) -> Dict[str, Any]:
         """K1 gathers and the all-gathers C2 / C3 (reference bess.py:502-518)."""
         group = self._group()
         n = group.n_shard
@@ -1533,7 +1548,7 @@ class ScoreMovingBessKGE(BessKGE):
         # head rows + relation ids - one all-gather less, and no shard re-derives n * S queries.
         # (Heads are corrupted with queries built from tails that live on other shards than their
         # relation ids: those still travel as the reference's embeddings + ids.)
-        send_queries = (scheme == "t" and not getattr(self, "_training_pass", False) and fn.supports_fused_forward
+        send_queries = (scheme == "t" and not ctx.training and fn.supports_fused_forward
                         and fn.entity_embedding.dtype == torch.float32)
         steps: List[_ReplicaStep] = []
         tails_out, heads_q, tails_q, rels = [], [], [], []
@@ -1547,9 +1562,7 @@ class ScoreMovingBessKGE(BessKGE):
             st.head_idx, st.rel_idx = head.reshape(-1), rel.reshape(-1)
             if isinstance(ns, TripleBasedShardedNegativeSampler) and ns.flat_negative_format:
                 neg = neg[0:1]  # replicated along dim 0; one copy is enough (bess.py:511-517)
-            st.local_neg = neg  # type: ignore
-            st.local_tail = tail
-            st.sm_head = head  # type: ignore[attr-defined]
+            st.local_neg, st.local_tail, st.sm_head = neg, tail, head
             # rows of my shard that other replicas need
             tail_rows = nat.gather_rows(st.table, tail.reshape(-1)).reshape(n, st.ppp, W)
             tails_out.append(tail_rows)
@@ -1571,8 +1584,8 @@ class ScoreMovingBessKGE(BessKGE):
         return dict(steps=steps, tails_out=tails_out, rel_all=rel_all, tq_all=tq_all, hq_all=hq_all,
                     queries_sent=send_queries)
 
-    def _score_finish(self, ctx: Dict[str, Any]) -> List[_ReplicaStep]:
-        """Local scoring of the gathered queries, score all-to-all C4 + C5, positive scores."""
+    def _score_finish(self, begun: Dict[str, Any], ctx: _StepContext) -> List[_ReplicaStep]:
+        """Local scoring of the queries `_score_begin` gathered, score all-to-all C4 + C5, positive scores."""
         group = self._group()
         n = group.n_shard
         ns = self.negative_sampler
@@ -1581,9 +1594,9 @@ class ScoreMovingBessKGE(BessKGE):
         desc = fn.kernel_desc()
         sharing = bool(fn.negative_sample_sharing)
         scheme = ns.corruption_scheme
-        steps, tails_out = ctx["steps"], ctx["tails_out"]
-        rel_all, tq_all, hq_all = ctx["rel_all"], ctx["tq_all"], ctx["hq_all"]
-        sm_fuse = getattr(self, "_sm_fuse", None)  # training, fusable loss: loss.kernel_desc (see train_step_replicas)
+        steps, tails_out = begun["steps"], begun["tails_out"]
+        rel_all, tq_all, hq_all = begun["rel_all"], begun["tq_all"], begun["hq_all"]
+        sm_fuse = ctx.sm_fuse  # training, fusable loss: loss.kernel_desc (see train_step_replicas)
 
         scores_out = []
         for r, st in enumerate(steps):
@@ -1591,7 +1604,7 @@ class ScoreMovingBessKGE(BessKGE):
             ppp, cut = st.ppp, st.ppp // 2
             neg = st.local_neg  # [n | 1, B, K]
             nB, B, K = (int(x) for x in neg.shape)
-            queries_sent = bool(ctx.get("queries_sent"))
+            queries_sent = bool(begun.get("queries_sent"))
             relr = None if queries_sent else rel_all[r]
 
             def problem(side: int, ent_all: torch.Tensor, transpose: bool, rel_sel: torch.Tensor,
@@ -1620,7 +1633,7 @@ class ScoreMovingBessKGE(BessKGE):
                 pl = None
                 if sm_fuse is not None and not g.shared:
                     pl = sm_fuse(n * g.n_per_query)  # the loss sees the negatives of all shards
-                return self._run_groups_one(g, desc, st=st, partials_loss=pl)  # st: the index of the negatives starts now
+                return self._run_groups_one(g, desc, ctx, st=st, partials_loss=pl)  # (st: the negatives' index starts now)
 
             if scheme == "h":
                 sc = problem(nat.CORRUPT_HEAD, tq_all[r], True, relr, neg.reshape(nB * B, K))
@@ -1667,9 +1680,9 @@ class ScoreMovingBessKGE(BessKGE):
         return xo, yo
 
     # ---------------------------------------------------------------- training
-    def train_step_replicas(self, batches: List[_Batch], optimizer: Any,
-                            pending: Optional[List[_PendingUpdate]] = None) -> List[Dict[str, Any]]:
-        """Forward + backward + sparse optimiser update (ScoreMoving; `pending`: see EmbeddingMoving).
+    def train_step_replicas(self, batches: List[_Batch], optimizer: Any, pending: Optional[List[_PendingUpdate]] = None,
+                            grad_scale: float = 1.0) -> List[Dict[str, Any]]:
+        """Forward + backward + sparse optimiser update (ScoreMoving; `pending`, `grad_scale`: see EmbeddingMoving).
 
         Backward of the reference graph `bess.py:490-603`: score gradients travel
         back to the shards that produced them (all-to-all, transpose of C4); each
@@ -1678,40 +1691,28 @@ class ScoreMovingBessKGE(BessKGE):
         over shards and returned to the owner (reduce-scatter = transpose of the
         all-gather C3); positive tails return through an all-to-all (C5').
         """
-        if self.loss_fn is None:
-            raise RuntimeError("train_step needs a loss function")
+        ctx = self._training_context(batches, optimizer, pending, grad_scale)
         group = self._group()
         n = group.n_shard
         fn = self.score_fn
         W = self.entity_embedding_size
         scheme = self.negative_sampler.corruption_scheme
-        accumulating = pending is not None
-        self.__dict__["_training_pass"] = True  # the backward needs the gathered embeddings, not finished queries
-        self.__dict__["_seg_ahead"] = None if accumulating else {}
         # Fused training forward (per-triple negatives, nothing masked, a loss whose negative weights do not need
         # the positive score): every shard keeps the online-softmax partials of the queries it scored; the second
         # pass over the negative rows (`neg_score_pertriple_bwd`) is replaced by a rescaling of those partials
-        fuse = [self._fusable(b) for b in batches]
         kind = getattr(self.loss_fn, "_kind", -1)
-        fused = (all(f is not None and not f.get("masked") for f in fuse)
+        fused = (all(f is not None and not f.get("masked") for f in ctx.fuse)
                  and kind in (nat.LOSS_LOGSIGMOID, nat.LOSS_SSCE) and fn.supports_fused_segments)
-        self.__dict__["_sm_fuse"] = self.loss_fn.kernel_desc if fused else None
-        try:
-            steps = self._score_replicas(batches)
-            seg_index = {} if accumulating else self._prefetch_segment_indices(steps)
-        finally:
-            self.__dict__["_training_pass"] = False
-            self.__dict__["_seg_ahead"] = None
-            self.__dict__["_sm_fuse"] = None
+        ctx.sm_fuse = self.loss_fn.kernel_desc if fused else None
+        steps = self._score_replicas(batches, ctx)
+        seg_index = {} if pending is not None else self._prefetch_segment_indices(steps, ctx)
         desc = fn.kernel_desc()
-        rel_table = fn.relation_embedding.data
-        d_rel = pending[0].d_rel if pending else torch.zeros(rel_table.shape, dtype=torch.float32,
-                                                             device=rel_table.device)
+        d_rel = self._relation_gradient(ctx, pending)
         results, d_scores, d_tails = [], [], []
         local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]] = []
         for st, b in zip(steps, batches):
             with_norm = fused and any(g.partials is not None for g in st.groups)
-            out, d_pos, d_neg = self._finish(st, b, want_grad=True, want_norm=with_norm)
+            out, d_pos, d_neg = self._finish(st, b, want_grad=True, want_norm=with_norm, scale=grad_scale)
             results.append(out)
             S = d_neg.shape[0]
             d_sc = d_neg.reshape(S, n, -1).transpose(0, 1)  # [n(shard), S, Nl]
@@ -1768,7 +1769,7 @@ class ScoreMovingBessKGE(BessKGE):
         back_tq, back_hq = to_owner(d_tq), to_owner(d_hq)
         for i, (st, upd) in enumerate(zip(steps, local_updates)):
             cut = st.ppp // 2
-            head2d, tail2d = st.sm_head, st.local_tail  # type: ignore[attr-defined]
+            head2d, tail2d = st.sm_head, st.local_tail
             if scheme == "h":
                 upd.append((tail2d.reshape(-1), back_tq[i].reshape(-1, W)))
             elif scheme == "t":
@@ -1776,15 +1777,11 @@ class ScoreMovingBessKGE(BessKGE):
             else:
                 upd.append((tail2d[:, :cut].reshape(-1).contiguous(), back_tq[i].reshape(-1, W)))
                 upd.append((head2d[:, cut:].reshape(-1).contiguous(), back_hq[i].reshape(-1, W)))
-        if accumulating:
+        if pending is not None:
             pending.append(_PendingUpdate(steps, local_updates, deferred, d_rel))
-            return results
-        self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, desc, d_rel)
+        else:
+            self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, desc, d_rel, ctx.small_ahead)
         return results
-
-    def train_step(self, optimizer: Any, **batch: torch.Tensor) -> Dict[str, Any]:
-        """Single-replica convenience wrapper of :meth:`train_step_replicas`."""
-        return self.train_step_replicas([batch], optimizer)[0]
 
 
 from besskge.query import AllScoresBESS, TopKQueryBessKGE  # noqa: E402,F401

@@ -285,17 +285,12 @@ class Runner:
         k = self._accum
         if k == 1:
             return [self._step(self._split(batch, it))]
-        mean = self.reduction == "mean"
+        scale = 1.0 / k if self.reduction == "mean" else 1.0
         pending: List[Any] = []
         outs = []
-        if mean:
-            self.model.__dict__["_grad_scale"] = 1.0 / k
-        try:
-            for j in range(k):
-                outs.append(self.model.train_step_replicas(self._split(batch, it * k + j), self.optimizer,
-                                                           pending=pending))  # type: ignore
-        finally:
-            self.model.__dict__["_grad_scale"] = 1.0
+        for j in range(k):
+            outs.append(self.model.train_step_replicas(self._split(batch, it * k + j), self.optimizer,
+                                                       pending=pending, grad_scale=scale))  # type: ignore
         self.model.apply_accumulated(pending, self.optimizer)  # type: ignore
         return outs
 
