@@ -719,10 +719,6 @@ static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n
     if (fwd && !fuse) a.sweep_shift = sweep_shift_for(d, n_query, n_neg);
     const int red = reduce_of(d);
     hipStream_t st = as_stream(stream);
-    if (!fwd && a.items_per_query > 1 && dq) {
-        hipError_t e = fill_words_async(dq, 0u, n_query * W, st);
-        if (e != hipSuccess) return fail(static_cast<int>(e), "memset d_query: %s", hipGetErrorString(e));
-    }
     // A 16-lane group keeps 16 x 16 chunks of a row in registers (1024 f32 / 2048 f16 scalars at full vector
     // width).  Wider rows are processed in column windows of that size: the dot product and the p = 1 distance are
     // sums over columns (forward: later windows add to the scores; backward: every window writes its own columns).
@@ -735,6 +731,11 @@ static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n
         if (fuse)
             return fail(BESS_EUNSUPPORTED, "neg_score_pertriple: fused training forward on rows of %d scalars (more than %d)",
                         W, max_cols);
+    }
+    // (cleared only now: a refused call leaves its outputs as they were)
+    if (!fwd && a.items_per_query > 1 && dq) {
+        hipError_t e = fill_words_async(dq, 0u, n_query * W, st);
+        if (e != hipSuccess) return fail(static_cast<int>(e), "memset d_query: %s", hipGetErrorString(e));
     }
     const int64_t sz = d->dtype == BESS_F32 ? 4 : 2;
     for (int col0 = 0; col0 < W; col0 += max_cols) {
