@@ -496,36 +496,12 @@ __global__ __launch_bounds__(256) void k_aff_pertriple_bwd(AffArgs a, const floa
         }
 }
 
-template <typename T, int VEC, int IT, int NPART>
-static void aff_pt_launch(int p, bool fwd, const AffArgs& a, float* out, const float* d_out, int64_t ld, float* dq,
-                          float* dn, hipStream_t st) {
-    const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_query * a.items_per_query, 4));
-    if (fwd) {
-        if (p == 1) k_aff_pertriple_fwd<T, VEC, IT, NPART, 1><<<blocks, 256, 0, st>>>(a, out, ld);
-        else k_aff_pertriple_fwd<T, VEC, IT, NPART, 2><<<blocks, 256, 0, st>>>(a, out, ld);
-    } else {
-        if (p == 1) k_aff_pertriple_bwd<T, VEC, IT, NPART, 1><<<blocks, 256, 0, st>>>(a, d_out, ld, dq, dn);
-        else k_aff_pertriple_bwd<T, VEC, IT, NPART, 2><<<blocks, 256, 0, st>>>(a, d_out, ld, dq, dn);
-    }
-}
-
-template <typename T, int VEC, int NPART>
-static int aff_pt_by_it(int it, int p, bool fwd, const AffArgs& a, float* out, const float* d_out, int64_t ld,
-                        float* dq, float* dn, hipStream_t st) {
-    if (it <= 1) aff_pt_launch<T, VEC, 1, NPART>(p, fwd, a, out, d_out, ld, dq, dn, st);
-    else if (it <= 2) aff_pt_launch<T, VEC, 2, NPART>(p, fwd, a, out, d_out, ld, dq, dn, st);
-    else if (it <= 4) aff_pt_launch<T, VEC, 4, NPART>(p, fwd, a, out, d_out, ld, dq, dn, st);
-    else if (it <= 8) aff_pt_launch<T, VEC, 8, NPART>(p, fwd, a, out, d_out, ld, dq, dn, st);
-    else return fail(BESS_EUNSUPPORTED, "affine scorers: part of %d scalars too wide", a.d);
-    return BESS_OK;
-}
-
 int affine_pertriple(const bess_model_desc* d, bool fwd, const float* query, int64_t n_query, const void* neg_base,
                      const int32_t* neg_idx, int64_t n_neg, float* out, const float* d_out, int64_t ld, float* dq,
                      float* dn, hipStream_t st) {
     const int n_part = d->reserved[0];
     const int dd = d->width / n_part;
-    const int vec = (dd % 4 == 0) ? 4 : 1;
+    const int vec = part_vec_of(dd);
     AffArgs a;
     a.query = query;
     a.base = neg_base;
@@ -534,10 +510,8 @@ int affine_pertriple(const bess_model_desc* d, bool fwd, const float* query, int
     a.n_neg = static_cast<int>(n_neg);
     a.d = dd;
     a.nch = dd / vec;
-    int nb = 64;
-    while (nb > 8 && n_query * ceil_div(n_neg, nb) < 256 * 16 * 2) nb >>= 1;
-    a.nb = nb;
-    a.items_per_query = static_cast<int>(ceil_div(n_neg, nb));
+    a.nb = negatives_per_item(n_query, n_neg);
+    a.items_per_query = static_cast<int>(ceil_div(n_neg, a.nb));
     a.normalize = d->reserved[1] & 1;
     a.p = static_cast<float>(d->norm_p);
     const int it = static_cast<int>(ceil_div(a.nch, 16));
@@ -545,14 +519,19 @@ int affine_pertriple(const bess_model_desc* d, bool fwd, const float* query, int
         hipError_t e = fill_words_async(dq, 0u, n_query * (n_part + 1) * dd, st);
         if (e != hipSuccess) return fail(static_cast<int>(e), "memset d_query: %s", hipGetErrorString(e));
     }
-    int rc;
-#define BESS_AFF(T, V)                                                                                   \
-    (n_part == 1 ? aff_pt_by_it<T, V, 1>(it, d->norm_p, fwd, a, out, d_out, ld, dq, dn, st)              \
-                 : aff_pt_by_it<T, V, 2>(it, d->norm_p, fwd, a, out, d_out, ld, dq, dn, st))
-    if (d->dtype == BESS_F32) rc = vec == 4 ? BESS_AFF(float, 4) : BESS_AFF(float, 1);
-    else rc = vec == 4 ? BESS_AFF(half_t, 4) : BESS_AFF(half_t, 1);
-#undef BESS_AFF
-    if (rc) return rc;
+    const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_query * a.items_per_query, 4));
+    const bool ok = dispatch_row_class<PartRows>(d->dtype, vec, it, [&](auto c) {
+        using C = decltype(c);
+        using T = typename C::T;
+        with_constant<1, 2>(n_part, [&](auto np) {
+            with_constant<1, 2>(d->norm_p, [&](auto p) {
+                constexpr int NPART = decltype(np)::value, P = decltype(p)::value;
+                if (fwd) k_aff_pertriple_fwd<T, C::VEC, C::IT, NPART, P><<<blocks, 256, 0, st>>>(a, out, ld);
+                else k_aff_pertriple_bwd<T, C::VEC, C::IT, NPART, P><<<blocks, 256, 0, st>>>(a, d_out, ld, dq, dn);
+            });
+        });
+    });
+    if (!ok) return fail(BESS_EUNSUPPORTED, "affine scorers: part of %d scalars too wide", a.d);
     return check_launch(fwd ? "neg_score_pertriple_fwd (affine)" : "neg_score_pertriple_bwd (affine)");
 }
 
@@ -749,24 +728,6 @@ __global__ __launch_bounds__(256) void k_aff_long_segments(AffSegArgs a, float* 
     }
 }
 
-template <typename T, int VEC, int NPART>
-static int aff_seg_by_it(int it, int p, const AffSegArgs& a, float* grad_seg, void* rw, float lr, unsigned grid,
-                         hipStream_t st, float* long_grad = nullptr, int32_t* long_cnt = nullptr, int32_t cap = 0) {
-    T* t = static_cast<T*>(rw);
-#define BESS_AFS(ITV)                                                                                              \
-    (long_grad ? (p == 1 ? k_aff_long_segments<T, VEC, ITV, NPART, 1><<<grid, 256, 0, st>>>(a, long_grad, long_cnt, cap, grad_seg, t, lr) \
-                         : k_aff_long_segments<T, VEC, ITV, NPART, 2><<<grid, 256, 0, st>>>(a, long_grad, long_cnt, cap, grad_seg, t, lr)) \
-               : (p == 1 ? k_aff_grad_segments<T, VEC, ITV, NPART, 1><<<grid, 256, 0, st>>>(a, grad_seg, t, lr)     \
-                         : k_aff_grad_segments<T, VEC, ITV, NPART, 2><<<grid, 256, 0, st>>>(a, grad_seg, t, lr)))
-    if (it <= 1) BESS_AFS(1);
-    else if (it <= 2) BESS_AFS(2);
-    else if (it <= 4) BESS_AFS(4);
-    else if (it <= 8) BESS_AFS(8);
-    else return fail(BESS_EUNSUPPORTED, "affine scorers: part of %d scalars too wide", a.d);
-#undef BESS_AFS
-    return BESS_OK;
-}
-
 int affine_grad_segments(const bess_model_desc* d, const float* query, void* table, int64_t n_neg,
                          const float* d_out, int64_t ld_dout, const int32_t* refs_sorted, const int32_t* seg_rows,
                          const int32_t* seg_offsets, const int32_t* n_seg, int64_t max_seg, float* grad_seg,
@@ -774,29 +735,35 @@ int affine_grad_segments(const bess_model_desc* d, const float* query, void* tab
                          int32_t* long_count, hipStream_t st) {
     const int n_part = d->reserved[0];
     const int dd = d->width / n_part;
-    const int vec = (dd % 4 == 0) ? 4 : 1;
+    const int vec = part_vec_of(dd);
     AffSegArgs a{query, table, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg, static_cast<int>(n_neg),
                  dd, dd / vec, d->reserved[1] & 1, long_segs, static_cast<float>(d->norm_p)};
     const int it = static_cast<int>(ceil_div(a.nch, 16));
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16));
-    int rc;
-#define BESS_AFSD(T, V)                                                                                       \
-    (n_part == 1 ? aff_seg_by_it<T, V, 1>(it, d->norm_p, a, grad_seg, table, fused_sgd_lr, grid, st)          \
-                 : aff_seg_by_it<T, V, 2>(it, d->norm_p, a, grad_seg, table, fused_sgd_lr, grid, st))
-    if (d->dtype == BESS_F32) rc = vec == 4 ? BESS_AFSD(float, 4) : BESS_AFSD(float, 1);
-    else rc = vec == 4 ? BESS_AFSD(half_t, 4) : BESS_AFSD(half_t, 1);
-#undef BESS_AFSD
-    if (rc) return rc;
-    if (long_segs) {  // the rows left out above, by all groups together (usually none)
-        const int32_t cap = static_cast<int32_t>(long_cap);
-#define BESS_AFSL(T, V)                                                                                                  \
-    (n_part == 1 ? aff_seg_by_it<T, V, 1>(it, d->norm_p, a, grad_seg, table, fused_sgd_lr, 1024, st, long_grad, long_count, cap) \
-                 : aff_seg_by_it<T, V, 2>(it, d->norm_p, a, grad_seg, table, fused_sgd_lr, 1024, st, long_grad, long_count, cap))
-        if (d->dtype == BESS_F32) rc = vec == 4 ? BESS_AFSL(float, 4) : BESS_AFSL(float, 1);
-        else rc = vec == 4 ? BESS_AFSL(half_t, 4) : BESS_AFSL(half_t, 1);
-#undef BESS_AFSL
-        if (rc) return rc;
-    }
+    // lgrad: the slices of the long segments (k_aff_long_segments), else one group per row
+    auto launch = [&](unsigned blocks, float* lgrad, int32_t* lcnt, int32_t cap) {
+        const bool ok = dispatch_row_class<PartRows>(d->dtype, vec, it, [&](auto c) {
+            using C = decltype(c);
+            using T = typename C::T;
+            T* rw = static_cast<T*>(table);
+            with_constant<1, 2>(n_part, [&](auto np) {
+                with_constant<1, 2>(d->norm_p, [&](auto p) {
+                    constexpr int NPART = decltype(np)::value, P = decltype(p)::value;
+                    if (lgrad)
+                        k_aff_long_segments<T, C::VEC, C::IT, NPART, P>
+                            <<<blocks, 256, 0, st>>>(a, lgrad, lcnt, cap, grad_seg, rw, fused_sgd_lr);
+                    else
+                        k_aff_grad_segments<T, C::VEC, C::IT, NPART, P>
+                            <<<blocks, 256, 0, st>>>(a, grad_seg, rw, fused_sgd_lr);
+                });
+            });
+        });
+        return ok ? BESS_OK : fail(BESS_EUNSUPPORTED, "affine scorers: part of %d scalars too wide", a.d);
+    };
+    if (int rc = launch(grid, nullptr, nullptr, 0)) return rc;
+    // the rows left out above, by all groups together (usually none)
+    if (long_segs)
+        if (int rc = launch(1024u, long_grad, long_count, static_cast<int32_t>(long_cap))) return rc;
     return check_launch("neg_pertriple_grad_segments (affine)");
 }
 

@@ -27,6 +27,9 @@
 
 namespace bess {
 
+static const char* const BOX_TOO_WIDE =
+    "BoxE: embedding size %d too wide for the kernels (max 512; 128 when not a multiple of 4)";
+
 struct BoxArgs {
     const float* query;  // [n_query, 6 d]
     const void* base;
@@ -293,45 +296,13 @@ __global__ __launch_bounds__(256) void k_box_bwd(BoxArgs a, const float* __restr
         }
 }
 
-template <typename T, int VEC, int IT, int P>
-static void box_launch(int flags, bool fwd, const BoxArgs& a, float* out, const float* d_out, int64_t ld, float* dq,
-                       float* dn, int dn_atomic, hipStream_t st, const float* thr, const CountArgs* cnt) {
-    const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_query * a.items_per_query, 4));
-    const bool th = flags & 1, pd = flags & 2;
-    const CountArgs none{nullptr, nullptr, 0, 0};
-#define BESS_BOX(TH, PD)                                                                                   \
-    (cnt ? k_box_fwd<T, VEC, IT, P, TH, PD, true><<<blocks, 256, 0, st>>>(a, nullptr, 0, thr, *cnt)        \
-     : fwd ? k_box_fwd<T, VEC, IT, P, TH, PD, false><<<blocks, 256, 0, st>>>(a, out, ld, nullptr, none)    \
-           : k_box_bwd<T, VEC, IT, P, TH, PD><<<blocks, 256, 0, st>>>(a, d_out, ld, dq, dn, dn_atomic))
-    if (th && pd) BESS_BOX(true, true);
-    else if (th) BESS_BOX(true, false);
-    else if (pd) BESS_BOX(false, true);
-    else BESS_BOX(false, false);
-#undef BESS_BOX
-}
-
-template <typename T, int VEC>
-static int box_by_it(int it, int p, int flags, bool fwd, const BoxArgs& a, float* out, const float* d_out, int64_t ld,
-                     float* dq, float* dn, int dn_atomic, hipStream_t st, const float* thr, const CountArgs* cnt) {
-#define BESS_BOXP(ITV)                                                                                  \
-    (p == 1 ? box_launch<T, VEC, ITV, 1>(flags, fwd, a, out, d_out, ld, dq, dn, dn_atomic, st, thr, cnt) \
-            : box_launch<T, VEC, ITV, 2>(flags, fwd, a, out, d_out, ld, dq, dn, dn_atomic, st, thr, cnt))
-    if (it <= 1) BESS_BOXP(1);
-    else if (it <= 2) BESS_BOXP(2);
-    else if (it <= 4) BESS_BOXP(4);
-    else if (it <= 8) BESS_BOXP(8);
-    else return fail(BESS_EUNSUPPORTED, "BoxE: embedding size %d too wide for the kernels (max 512; 128 when not a multiple of 4)", a.d);
-#undef BESS_BOXP
-    return BESS_OK;
-}
-
 // shared == true: idx is one list of n_neg rows for every query (or NULL = rows 0..n_neg-1), d_neg is [n_neg, 2d]
 int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float* query, int64_t n_query,
                    const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* out, const float* d_out,
                    int64_t ld, float* dq, float* dn, hipStream_t st, const float* thr, const CountArgs* count) {
     BESS_REQUIRE(!count || (fwd && shared && thr), "BoxE: counting is a forward over shared candidates");
     const int dd = d->width / 2;
-    const int vec = (dd % 4 == 0) ? 4 : 1;
+    const int vec = part_vec_of(dd);
     BoxArgs a;
     a.query = query;
     a.base = neg_base;
@@ -341,10 +312,9 @@ int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float*
     a.n_neg = static_cast<int>(n_neg);
     a.d = dd;
     a.nch = dd / vec;
-    int nb = count ? 256 : 64;  // (counting: a wave's candidates end in one atomic pair)
-    while (nb > 8 && n_query * ceil_div(n_neg, nb) < 256 * 16 * 2) nb >>= 1;
-    a.nb = nb;
-    a.items_per_query = static_cast<int>(ceil_div(n_neg, nb));
+    // (counting: a wave's candidates end in one atomic pair)
+    a.nb = negatives_per_item(n_query, n_neg, count ? 256 : 64);
+    a.items_per_query = static_cast<int>(ceil_div(n_neg, a.nb));
     BESS_REQUIRE(!count || ceil_div(n_query * a.items_per_query, 4) < (1ll << 31), "BoxE: problem too large for one launch");
     a.p = static_cast<float>(d->norm_p);
     const int it = static_cast<int>(ceil_div(a.nch, 16));
@@ -354,15 +324,26 @@ int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float*
         if (e == hipSuccess && shared && dn) e = fill_words_async(dn, 0u, n_neg * 2 * dd, st);
         if (e != hipSuccess) return fail(static_cast<int>(e), "memset: %s", hipGetErrorString(e));
     }
-    int rc;
-    const int flags = d->reserved[0];
-    if (d->dtype == BESS_F32)
-        rc = vec == 4 ? box_by_it<float, 4>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count)
-                      : box_by_it<float, 1>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count);
-    else
-        rc = vec == 4 ? box_by_it<half_t, 4>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count)
-                      : box_by_it<half_t, 1>(it, d->norm_p, flags, fwd, a, out, d_out, ld, dq, dn, shared, st, thr, count);
-    if (rc) return rc;
+    const unsigned blocks = static_cast<unsigned>(ceil_div(a.n_query * a.items_per_query, 4));
+    const int dn_atomic = shared;
+    const CountArgs none{nullptr, nullptr, 0, 0};
+    const bool ok = dispatch_row_class<PartRows>(d->dtype, vec, it, [&](auto c) {
+        using C = decltype(c);
+        using T = typename C::T;
+        with_constant<1, 2>(d->norm_p, [&](auto p) {
+            with_constant<0, 1, 2, 3>(d->reserved[0] & 3, [&](auto fl) {  // bit 0 = tanh, bit 1 = per dimension
+                constexpr int P = decltype(p)::value;
+                constexpr bool TH = decltype(fl)::value & 1, PD = decltype(fl)::value & 2;
+                if (count)
+                    k_box_fwd<T, C::VEC, C::IT, P, TH, PD, true><<<blocks, 256, 0, st>>>(a, nullptr, 0, thr, *count);
+                else if (fwd)
+                    k_box_fwd<T, C::VEC, C::IT, P, TH, PD, false><<<blocks, 256, 0, st>>>(a, out, ld, nullptr, none);
+                else
+                    k_box_bwd<T, C::VEC, C::IT, P, TH, PD><<<blocks, 256, 0, st>>>(a, d_out, ld, dq, dn, dn_atomic);
+            });
+        });
+    });
+    if (!ok) return fail(BESS_EUNSUPPORTED, BOX_TOO_WIDE, a.d);
     return check_launch(fwd ? "neg_score fwd (BoxE)" : "neg_score bwd (BoxE)");
 }
 
@@ -562,63 +543,41 @@ __global__ __launch_bounds__(256) void k_box_long_segments(BoxSegArgs a, float* 
     }
 }
 
-template <typename T, int VEC, int IT, int P>
-static void box_seg_launch(int flags, const BoxSegArgs& a, float* grad_seg, void* rw, float lr, unsigned grid,
-                           hipStream_t st, float* long_grad, int32_t* long_cnt, int32_t cap) {
-    T* t = static_cast<T*>(rw);
-    const bool th = flags & 1, pd = flags & 2;
-#define BESS_BOXS(TH, PD)                                                                                             \
-    (long_grad ? k_box_long_segments<T, VEC, IT, P, TH, PD><<<grid, 256, 0, st>>>(a, long_grad, long_cnt, cap, grad_seg, t, lr) \
-               : k_box_grad_segments<T, VEC, IT, P, TH, PD><<<grid, 256, 0, st>>>(a, grad_seg, t, lr))
-    if (th && pd) BESS_BOXS(true, true);
-    else if (th) BESS_BOXS(true, false);
-    else if (pd) BESS_BOXS(false, true);
-    else BESS_BOXS(false, false);
-#undef BESS_BOXS
-}
-
-template <typename T, int VEC>
-static int box_seg_by_it(int it, int p, int flags, const BoxSegArgs& a, float* grad_seg, void* rw, float lr,
-                         unsigned grid, hipStream_t st, float* long_grad = nullptr, int32_t* long_cnt = nullptr,
-                         int32_t cap = 0) {
-#define BESS_BOXSP(ITV)                                                                                    \
-    (p == 1 ? box_seg_launch<T, VEC, ITV, 1>(flags, a, grad_seg, rw, lr, grid, st, long_grad, long_cnt, cap) \
-            : box_seg_launch<T, VEC, ITV, 2>(flags, a, grad_seg, rw, lr, grid, st, long_grad, long_cnt, cap))
-    if (it <= 1) BESS_BOXSP(1);
-    else if (it <= 2) BESS_BOXSP(2);
-    else if (it <= 4) BESS_BOXSP(4);
-    else if (it <= 8) BESS_BOXSP(8);
-    else return fail(BESS_EUNSUPPORTED, "BoxE: embedding size %d too wide for the kernels (max 512; 128 when not a multiple of 4)", a.d);
-#undef BESS_BOXSP
-    return BESS_OK;
-}
-
 int boxe_grad_segments(const bess_model_desc* d, const float* query, void* table, int64_t n_neg, const float* d_out,
                        int64_t ld_dout, const int32_t* refs_sorted, const int32_t* seg_rows,
                        const int32_t* seg_offsets, const int32_t* n_seg, int64_t max_seg, float* grad_seg,
                        float fused_sgd_lr, const int32_t* long_segs, int64_t long_cap, float* long_grad,
                        int32_t* long_count, hipStream_t st) {
     const int dd = d->width / 2;
-    const int vec = (dd % 4 == 0) ? 4 : 1;
+    const int vec = part_vec_of(dd);
     BoxSegArgs a{query, table, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg, static_cast<int>(n_neg),
                  dd, dd / vec, long_segs, static_cast<float>(d->norm_p)};
     const int it = static_cast<int>(ceil_div(a.nch, 16));
-    const int flags = d->reserved[0];
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16));
-    int rc;
-#define BESS_BOXSD(G, LG, LC, CAP)                                                                                     \
-    (d->dtype == BESS_F32                                                                                              \
-         ? (vec == 4 ? box_seg_by_it<float, 4>(it, d->norm_p, flags, a, grad_seg, table, fused_sgd_lr, G, st, LG, LC, CAP)  \
-                     : box_seg_by_it<float, 1>(it, d->norm_p, flags, a, grad_seg, table, fused_sgd_lr, G, st, LG, LC, CAP)) \
-         : (vec == 4 ? box_seg_by_it<half_t, 4>(it, d->norm_p, flags, a, grad_seg, table, fused_sgd_lr, G, st, LG, LC, CAP) \
-                     : box_seg_by_it<half_t, 1>(it, d->norm_p, flags, a, grad_seg, table, fused_sgd_lr, G, st, LG, LC, CAP)))
-    rc = BESS_BOXSD(grid, nullptr, nullptr, 0);
-    if (rc) return rc;
-    if (long_segs) {
-        rc = BESS_BOXSD(1024u, long_grad, long_count, static_cast<int32_t>(long_cap));
-        if (rc) return rc;
-    }
-#undef BESS_BOXSD
+    // lgrad: the slices of the long segments (k_box_long_segments), else one group per row
+    auto launch = [&](unsigned blocks, float* lgrad, int32_t* lcnt, int32_t cap) {
+        const bool ok = dispatch_row_class<PartRows>(d->dtype, vec, it, [&](auto c) {
+            using C = decltype(c);
+            using T = typename C::T;
+            T* rw = static_cast<T*>(table);
+            with_constant<1, 2>(d->norm_p, [&](auto p) {
+                with_constant<0, 1, 2, 3>(d->reserved[0] & 3, [&](auto fl) {  // bit 0 = tanh, bit 1 = per dimension
+                    constexpr int P = decltype(p)::value;
+                    constexpr bool TH = decltype(fl)::value & 1, PD = decltype(fl)::value & 2;
+                    if (lgrad)
+                        k_box_long_segments<T, C::VEC, C::IT, P, TH, PD>
+                            <<<blocks, 256, 0, st>>>(a, lgrad, lcnt, cap, grad_seg, rw, fused_sgd_lr);
+                    else
+                        k_box_grad_segments<T, C::VEC, C::IT, P, TH, PD>
+                            <<<blocks, 256, 0, st>>>(a, grad_seg, rw, fused_sgd_lr);
+                });
+            });
+        });
+        return ok ? BESS_OK : fail(BESS_EUNSUPPORTED, BOX_TOO_WIDE, a.d);
+    };
+    if (int rc = launch(grid, nullptr, nullptr, 0)) return rc;
+    if (long_segs)
+        if (int rc = launch(1024u, long_grad, long_count, static_cast<int32_t>(long_cap))) return rc;
     return check_launch("neg_pertriple_grad_segments (BoxE)");
 }
 

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "../../include/besskge_hip.h"
 
 namespace bess {
@@ -295,6 +298,89 @@ template <typename T>
 __device__ __forceinline__ const T* row_ptr(const T* base, const int32_t* idx, int64_t i, int width) {
     const int64_t r = idx ? static_cast<int64_t>(idx[i]) : i;
     return base + r * width;
+}
+
+// ---- host side: which instantiation of a row kernel runs ---------------------------------------------------------
+// Every kernel that keeps a table row in the registers of a 16-lane group is a template over <T, VEC, IT>: the table
+// type, the scalars per lane load and the 16-chunk iterations per row, rounded up to the next of 1, 2, 4, 8 (, 16).
+// dispatch_row_class turns the run-time (dtype, vec, it) into one call f(RowClass<T, VEC, IT>{}); a family's policy
+// lists its classes, and no other combination is ever instantiated.
+template <typename T_, int VEC_, int IT_>
+struct RowClass {
+    using T = T_;
+    static constexpr int VEC = VEC_, IT = IT_;
+};
+template <int... V>
+using Ints = std::integer_sequence<int, V...>;
+struct NativeRows {  // neg_pertriple.hip, segments.hip: vec_of() of the whole row
+    using f32_vecs = Ints<4, 1>;
+    using f16_vecs = Ints<8, 2, 1>;
+    using its = Ints<1, 2, 4, 8, 16>;
+};
+struct PartRows {  // affine.hip, boxe.hip: part_vec_of() of one part of the row, for both table types
+    using f32_vecs = Ints<4, 1>;
+    using f16_vecs = Ints<4, 1>;
+    using its = Ints<1, 2, 4, 8>;
+};
+template <typename T, int VEC, typename F, int... ITS>
+bool row_class_by_it(int it, F& f, Ints<ITS...>) {  // the first IT >= it
+    return ((it <= ITS ? (f(RowClass<T, VEC, ITS>{}), true) : false) || ...);
+}
+template <typename T, typename ITS, typename F, int... VECS>
+bool row_class_by_vec(int vec, int it, F& f, Ints<VECS...>) {
+    return ((vec == VECS && row_class_by_it<T, VECS>(it, f, ITS{})) || ...);
+}
+// false (f not called): the policy has no such class - `it` is above its largest IT, the row is too wide
+template <typename Policy, typename F>
+bool dispatch_row_class(int dtype, int vec, int it, F&& f) {
+    return dtype == BESS_F32 ? row_class_by_vec<float, typename Policy::its>(vec, it, f, typename Policy::f32_vecs{})
+                             : row_class_by_vec<half_t, typename Policy::its>(vec, it, f, typename Policy::f16_vecs{});
+}
+// The second compile-time axis of those kernels (RED, P, NPART, BoxE's flag bits): f(std::integral_constant<int, V>{})
+// for the V that equals v, the last V for every other v (RED_L2 and P == 2 stand for "any other p").
+template <int V0, int... VS, typename F>
+void with_constant(int v, F&& f) {
+    if constexpr (sizeof...(VS) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else with_constant<VS...>(v, f);
+}
+
+// scalars per lane load: the widest vector that divides the row (native family: f32 {4, 1}, f16 {8, 2, 1}) ...
+inline int vec_of(const bess_model_desc* d) {
+    const int maxvec = d->dtype == BESS_F32 ? 4 : 8;
+    if (d->width % maxvec == 0) return maxvec;
+    return (d->dtype == BESS_F16 && d->width % 2 == 0) ? 2 : 1;
+}
+// ... and that divides one part of dd scalars (affine scorers, BoxE: {4, 1} for both table types)
+inline int part_vec_of(int dd) { return (dd % 4 == 0) ? 4 : 1; }
+inline int64_t scalar_bytes_of(const bess_model_desc* d) { return d->dtype == BESS_F32 ? 4 : 2; }
+inline int64_t row_bytes_of(const bess_model_desc* d) { return d->width * scalar_bytes_of(d); }
+// Negatives per work item (a wave), from nb.  With row_bytes (native family): ~128 KiB of rows per item first (64
+// negatives of 2 KiB, up to 256 of 512 B: a wave then runs enough iterations to amortise its start-up).  Then
+// shrink the item while the launch would not fill 256 CUs x 16 waves.
+inline int negatives_per_item(int64_t n_query, int64_t n_neg, int nb = 64, int64_t row_bytes = 0) {
+    while (row_bytes > 0 && nb < 256 && nb * row_bytes < 131072) nb <<= 1;
+    while (nb > 8 && n_query * ceil_div(n_neg, nb) < 256 * 16 * 2) nb >>= 1;
+    return nb;
+}
+
+// Column windows of `win` scalars over a row of W (the last one may be shorter; n_conc: windows side by side in one
+// launch share it): f(window) for each, until one returns an error.
+struct ColWindow {
+    int col0, cols;
+    int nch;  // chunks of vec scalars per (concurrent) window
+    int it;   // 16-chunk iterations: the IT of dispatch_row_class
+    template <typename P>
+    P* at(P* p) const { return p ? p + col0 : nullptr; }  // the window's columns of an optional row-major matrix
+};
+template <typename F>
+int for_each_window(int W, int win, int vec, int n_conc, F&& f) {
+    for (int col0 = 0; col0 < W; col0 += win) {
+        const int cols = W - col0 < win ? W - col0 : win;
+        const int nch = cols / vec / n_conc;
+        if (int rc = f(ColWindow{col0, cols, nch, static_cast<int>(ceil_div(nch, 16))})) return rc;
+    }
+    return BESS_OK;
 }
 
 }  // namespace bess

@@ -63,6 +63,19 @@ struct FuseArgs {
     int mask_cols = 0, mask_from = 0;
 };
 
+// (host side) the loss descriptor's part of it
+static FuseArgs fuse_args(const bess_loss_desc* l, const float* pos, float* st_ml, float* st_acc) {
+    FuseArgs f;
+    f.pos = pos;
+    f.kind = l->kind;
+    f.beta = l->kind == BESS_LOSS_SSCE ? 1.f : (l->adversarial ? l->adversarial_scale : 0.f);
+    f.margin = l->margin;
+    f.shift = l->kind == BESS_LOSS_SSCE ? l->ssce_shift : 0.f;
+    f.st_ml = st_ml;
+    f.st_acc = st_acc;
+    return f;
+}
+
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 
 template <typename T, int VEC, int IT, int RED, int UNROLL, bool FUSE>
@@ -622,51 +635,9 @@ static void launch_bwd(const NegPtArgs& a, const float* d_out, int64_t ld, float
     k_neg_pertriple_bwd<T, VEC, IT, RED, BU><<<ceil_div(items, 4), 256, 0, st>>>(a, d_out, ld, dq, dn);
 }
 
-template <typename T, int VEC, int IT>
-static void by_red(int red, bool fwd, const NegPtArgs& a, float* out, const float* d_out, int64_t ld,
-                   float* dq, float* dn, const FuseArgs* fuse, hipStream_t st) {
-    switch (red) {
-        case RED_DOT:
-            fwd ? launch_fwd<T, VEC, IT, RED_DOT>(a, out, ld, fuse, st)
-                : launch_bwd<T, VEC, IT, RED_DOT>(a, d_out, ld, dq, dn, st);
-            break;
-        case RED_L1:
-            fwd ? launch_fwd<T, VEC, IT, RED_L1>(a, out, ld, fuse, st)
-                : launch_bwd<T, VEC, IT, RED_L1>(a, d_out, ld, dq, dn, st);
-            break;
-        default:
-            fwd ? launch_fwd<T, VEC, IT, RED_L2>(a, out, ld, fuse, st)
-                : launch_bwd<T, VEC, IT, RED_L2>(a, d_out, ld, dq, dn, st);
-    }
-}
-
-template <typename T, int VEC>
-static int by_it(int it, int red, bool fwd, const NegPtArgs& a, float* out, const float* d_out,
-                 int64_t ld, float* dq, float* dn, const FuseArgs* fuse, hipStream_t st) {
-    if (it <= 1) by_red<T, VEC, 1>(red, fwd, a, out, d_out, ld, dq, dn, fuse, st);
-    else if (it <= 2) by_red<T, VEC, 2>(red, fwd, a, out, d_out, ld, dq, dn, fuse, st);
-    else if (it <= 4) by_red<T, VEC, 4>(red, fwd, a, out, d_out, ld, dq, dn, fuse, st);
-    else if (it <= 8) by_red<T, VEC, 8>(red, fwd, a, out, d_out, ld, dq, dn, fuse, st);
-    else if (it <= 16) by_red<T, VEC, 16>(red, fwd, a, out, d_out, ld, dq, dn, fuse, st);
-    else return fail(BESS_EUNSUPPORTED, "neg_score_pertriple: row of %d scalars too wide", a.W);
-    return BESS_OK;
-}
-
-// ~128 KiB of rows per work item (64 negatives of 2 KiB, up to 256 of 512 B: a wave then runs
-// enough iterations to amortise its start-up); shrink the item when the launch would not fill
-// 256 CUs x 16 waves
-static int negatives_per_item(int64_t n_query, int64_t n_neg, int64_t row_bytes) {
-    int nb = 64;
-    while (nb < 256 && nb * row_bytes < 131072) nb <<= 1;
-    while (nb > 8 && n_query * ceil_div(n_neg, nb) < 256 * 16 * 2) nb >>= 1;
-    return nb;
-}
-
-// scalars per lane load: the widest vector that divides the row (f32 {4,1}, f16 {8,2,1})
-static int vec_of(const bess_model_desc* d) {
-    const int maxvec = d->dtype == BESS_F32 ? 4 : 8;
-    if (d->width % maxvec == 0) return maxvec;
-    return (d->dtype == BESS_F16 && d->width % 2 == 0) ? 2 : 1;
+// negatives per work item of this file's kernels (from 64: grown to ~128 KiB of rows, shrunk to fill the chip)
+static int native_nb(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
+    return negatives_per_item(n_query, n_neg, 64, row_bytes_of(d));
 }
 
 // Row-ordered plain forward (k_neg_pertriple_fwd_sweep)?  Only where the caller gave the table's row count
@@ -709,9 +680,7 @@ static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n
     a.n_neg = static_cast<int>(n_neg);
     a.W = W;
     a.nch = W / vec;
-    // 64 negatives per work item: ~128 KiB of rows per wave at 2 KiB rows; shrink the
-    // item when the launch would not fill 256 CUs x 16 waves
-    a.nb = negatives_per_item(n_query, n_neg, static_cast<int64_t>(W) * (d->dtype == BESS_F32 ? 4 : 2));  // == row_bytes_of(d)
+    a.nb = native_nb(d, n_query, n_neg);
     a.items_per_query = static_cast<int>(ceil_div(n_neg, a.nb));
     a.sign = is_distance(d->scorer) ? -1.f : 1.f;
     a.p = static_cast<float>(d->norm_p);
@@ -737,28 +706,24 @@ static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n
         hipError_t e = fill_words_async(dq, 0u, n_query * W, st);
         if (e != hipSuccess) return fail(static_cast<int>(e), "memset d_query: %s", hipGetErrorString(e));
     }
-    const int64_t sz = d->dtype == BESS_F32 ? 4 : 2;
-    for (int col0 = 0; col0 < W; col0 += max_cols) {
-        const int cols = W - col0 < max_cols ? W - col0 : max_cols;
+    const int64_t sz = scalar_bytes_of(d);
+    const int rc = for_each_window(W, max_cols, vec, 1, [&](const ColWindow& win) {
         NegPtArgs w = a;
-        w.query = query + col0;
-        w.base = static_cast<const char*>(neg_base) + col0 * sz;
-        w.nch = cols / vec;
-        w.accum = col0 > 0;
-        const int it = static_cast<int>(ceil_div(w.nch, 16));
-        float* dqw = dq ? dq + col0 : nullptr;
-        float* dnw = dn ? dn + col0 : nullptr;
-        int rc = BESS_OK;
-        if (d->dtype == BESS_F32) {
-            if (vec == 4) rc = by_it<float, 4>(it, red, fwd, w, out, d_out, ld, dqw, dnw, fuse, st);
-            else rc = by_it<float, 1>(it, red, fwd, w, out, d_out, ld, dqw, dnw, fuse, st);
-        } else {
-            if (vec == 8) rc = by_it<half_t, 8>(it, red, fwd, w, out, d_out, ld, dqw, dnw, fuse, st);
-            else if (vec == 2) rc = by_it<half_t, 2>(it, red, fwd, w, out, d_out, ld, dqw, dnw, fuse, st);
-            else rc = by_it<half_t, 1>(it, red, fwd, w, out, d_out, ld, dqw, dnw, fuse, st);
-        }
-        if (rc) return rc;
-    }
+        w.query = query + win.col0;
+        w.base = static_cast<const char*>(neg_base) + win.col0 * sz;
+        w.nch = win.nch;
+        w.accum = win.col0 > 0;
+        const bool ok = dispatch_row_class<NativeRows>(d->dtype, vec, win.it, [&](auto c) {
+            using C = decltype(c);
+            with_constant<RED_DOT, RED_L1, RED_L2>(red, [&](auto r) {
+                constexpr int RED = decltype(r)::value;
+                if (fwd) launch_fwd<typename C::T, C::VEC, C::IT, RED>(w, out, ld, fuse, st);
+                else launch_bwd<typename C::T, C::VEC, C::IT, RED>(w, d_out, ld, win.at(dq), win.at(dn), st);
+            });
+        });
+        return ok ? BESS_OK : fail(BESS_EUNSUPPORTED, "neg_score_pertriple: row of %d scalars too wide", w.W);
+    });
+    if (rc) return rc;
     return check_launch(fwd ? "neg_score_pertriple_fwd" : "neg_score_pertriple_bwd");
 }
 
@@ -793,13 +758,9 @@ extern "C" int bess_neg_pertriple_sweep(const bess_model_desc* d, int64_t n_quer
     return BESS_OK;
 }
 
-static int64_t row_bytes_of(const bess_model_desc* d) {
-    return static_cast<int64_t>(d->width) * (d->dtype == BESS_F32 ? 4 : 2);
-}
-
 extern "C" int bess_neg_pertriple_items(const bess_model_desc* d, int64_t n_query, int64_t n_neg, int32_t* items) {
     if (!d || !items || n_query < 0 || n_neg < 0) return bess::fail(BESS_EINVAL, "neg_pertriple_items: bad argument");
-    *items = n_neg > 0 ? static_cast<int32_t>(bess::ceil_div(n_neg, bess::negatives_per_item(n_query, n_neg, row_bytes_of(d))))
+    *items = n_neg > 0 ? static_cast<int32_t>(bess::ceil_div(n_neg, bess::native_nb(d, n_query, n_neg)))
                        : 0;
     return BESS_OK;
 }
@@ -831,14 +792,7 @@ extern "C" int bess_neg_score_pertriple_fwd_dq_masked(const bess_model_desc* d, 
     BESS_REQUIRE(out && state_ml && state_acc && weight && (weight_len == 1 || weight_len == n_query),
                  "neg_score_pertriple_fwd_dq: NULL pointer or bad weight length");
     BESS_REQUIRE(pos || l->kind == BESS_LOSS_LOGSIGMOID, "neg_score_pertriple_fwd_dq: this loss needs the positive scores");
-    FuseArgs f;
-    f.pos = pos;
-    f.kind = l->kind;
-    f.beta = l->kind == BESS_LOSS_SSCE ? 1.f : (l->adversarial ? l->adversarial_scale : 0.f);
-    f.margin = l->margin;
-    f.shift = l->kind == BESS_LOSS_SSCE ? l->ssce_shift : 0.f;
-    f.st_ml = state_ml;
-    f.st_acc = state_acc;
+    FuseArgs f = fuse_args(l, pos, state_ml, state_acc);
     if (mask) {
         BESS_REQUIRE(mask_cols > 0 && mask_cols <= n_neg && (mask_rows == 1 || mask_rows == n_query),
                      "neg_score_pertriple_fwd_dq_masked: mask [%lld, %lld] for %lld queries x %lld negatives",
@@ -851,7 +805,7 @@ extern "C" int bess_neg_score_pertriple_fwd_dq_masked(const bess_model_desc* d, 
     const int rc = run(d, true, query, n_query, neg_base, neg_idx, n_neg, out, nullptr, ld_out, nullptr, nullptr, stream,
                        &f);
     if (rc) return rc;
-    const int items = static_cast<int>(ceil_div(n_neg, negatives_per_item(n_query, n_neg, row_bytes_of(d))));
+    const int items = static_cast<int>(ceil_div(n_neg, native_nb(d, n_query, n_neg)));
     if (!d_query) return BESS_OK;  // the partials stay as they are: bess_pertriple_tail combines them where it uses them
     k_combine_dq<<<static_cast<unsigned>(ceil_div(n_query, 4)), 256, 0, as_stream(stream)>>>(
         state_ml, state_acc, n_query, items, d->width, l->kind, l->loss_scale, pos, weight, weight_len, nullptr, d_query);
@@ -871,14 +825,7 @@ extern "C" int bess_neg_score_pertriple_fwd_partials(const bess_model_desc* d, c
                                        "which the scoring shard does not have", l->kind);
     if (n_query <= 0 || n_neg <= 0) return BESS_OK;
     BESS_REQUIRE(out && state_ml && state_acc, "neg_score_pertriple_fwd_partials: NULL pointer");
-    FuseArgs f;
-    f.pos = nullptr;
-    f.kind = l->kind;
-    f.beta = l->kind == BESS_LOSS_SSCE ? 1.f : (l->adversarial ? l->adversarial_scale : 0.f);
-    f.margin = l->margin;
-    f.shift = l->kind == BESS_LOSS_SSCE ? l->ssce_shift : 0.f;
-    f.st_ml = state_ml;
-    f.st_acc = state_acc;
+    FuseArgs f = fuse_args(l, nullptr, state_ml, state_acc);
     return run(d, true, query, n_query, neg_base, neg_idx, n_neg, out, nullptr, ld_out, nullptr, nullptr, stream, &f);
 }
 

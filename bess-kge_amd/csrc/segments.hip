@@ -989,36 +989,6 @@ __global__ __launch_bounds__(256) void k_map_extra_rows(const int32_t* __restric
     }
 }
 
-template <typename T, int VEC, int IT>
-static void seg_by_red(int red, const SegArgs& a, float* grad_seg, void* table_rw, float lr, unsigned grid,
-                       hipStream_t st, float* long_grad = nullptr, int32_t* long_cnt = nullptr, int32_t long_cap = 0) {
-    T* rw = static_cast<T*>(table_rw);
-    if (long_grad) {  // the slices of the long segments, all groups together
-        if (red == RED_DOT)
-            k_long_segments<T, VEC, IT, RED_DOT><<<grid, 256, 0, st>>>(a, long_grad, long_cnt, long_cap, grad_seg, rw, lr);
-        else if (red == RED_L1)
-            k_long_segments<T, VEC, IT, RED_L1><<<grid, 256, 0, st>>>(a, long_grad, long_cnt, long_cap, grad_seg, rw, lr);
-        else
-            k_long_segments<T, VEC, IT, RED_L2><<<grid, 256, 0, st>>>(a, long_grad, long_cnt, long_cap, grad_seg, rw, lr);
-        return;
-    }
-    if (red == RED_DOT) k_pertriple_grad_segments<T, VEC, IT, RED_DOT><<<grid, 256, 0, st>>>(a, grad_seg, rw, lr);
-    else if (red == RED_L1) k_pertriple_grad_segments<T, VEC, IT, RED_L1><<<grid, 256, 0, st>>>(a, grad_seg, rw, lr);
-    else k_pertriple_grad_segments<T, VEC, IT, RED_L2><<<grid, 256, 0, st>>>(a, grad_seg, rw, lr);
-}
-
-template <typename T, int VEC>
-static int seg_by_it(int it, int red, const SegArgs& a, float* grad_seg, void* rw, float lr, unsigned grid,
-                     hipStream_t st, float* long_grad = nullptr, int32_t* long_cnt = nullptr, int32_t long_cap = 0) {
-    if (it <= 1) seg_by_red<T, VEC, 1>(red, a, grad_seg, rw, lr, grid, st, long_grad, long_cnt, long_cap);
-    else if (it <= 2) seg_by_red<T, VEC, 2>(red, a, grad_seg, rw, lr, grid, st, long_grad, long_cnt, long_cap);
-    else if (it <= 4) seg_by_red<T, VEC, 4>(red, a, grad_seg, rw, lr, grid, st, long_grad, long_cnt, long_cap);
-    else if (it <= 8) seg_by_red<T, VEC, 8>(red, a, grad_seg, rw, lr, grid, st, long_grad, long_cnt, long_cap);
-    else if (it <= 16) seg_by_red<T, VEC, 16>(red, a, grad_seg, rw, lr, grid, st, long_grad, long_cnt, long_cap);
-    else return fail(BESS_EUNSUPPORTED, "grad_segments: row of %d scalars too wide", a.W);
-    return BESS_OK;
-}
-
 // ---- K9 + K10 without an index: direct-addressed accumulation --------------------------------------------------
 // For shards whose fp32 image fits a scratch budget, the backward kernels ADD their gradient rows straight into
 // acc[row id] (an [M, W] fp32 matrix that is zero between steps; fp32 atomics), so nothing has to be sorted to
@@ -1272,12 +1242,8 @@ static int grad_segments_impl(const bess_model_desc* d, const float* query, int6
                                   as_stream(stream));
     BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "grad_segments: scorer %d has no segmented form", d->scorer);
     const int W = d->width;
-    const int maxvec = d->dtype == BESS_F32 ? 4 : 8;
-    int vec = maxvec;
-    if (W % vec) vec = (d->dtype == BESS_F16 && W % 2 == 0) ? 2 : 1;
+    const int vec = vec_of(d);
     const int red = reduce_of(d);
-    // 16 segments per 256-thread workgroup; grid-stride over the (device-side) segment count
-    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16));
     hipStream_t st = as_stream(stream);
     // Every reference re-reads its query row, so the pass streams n_ref * W floats out of an
     // [n_query, W] matrix: 8 MiB for 4096 x 512, twice an XCD's L2 - the rows then come from the
@@ -1304,61 +1270,45 @@ static int grad_segments_impl(const bess_model_desc* d, const float* query, int6
     // ... and a window is at most what a 16-lane group keeps in registers (16 iterations): rows wider than that
     // (1024 f32 / 2048 f16 scalars) are windowed for this reason alone; the p = 2 norm needs the whole row
     if (red != RED_L2 && win > 16 * unit) win = 16 * unit;
-    const int64_t sz = d->dtype == BESS_F32 ? 4 : 2;
-    for (int col0 = 0; col0 < W; col0 += win) {
-        const int cols = W - col0 < win ? W - col0 : win;
-        char* tab = static_cast<char*>(table) + col0 * sz;
-        SegOpt wopt = opt;  // the window's columns of the state tables and of the extra gradients
-        if (wopt.state1) wopt.state1 += col0;
-        if (wopt.state2) wopt.state2 += col0;
-        if (wopt.xsum) wopt.xsum += col0;
-        SegArgs a{query + col0, tab, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg,
-                  static_cast<int>(n_neg), W, cols / vec / n_conc, is_distance(d->scorer) ? -1.f : 1.f, long_segs, wopt,
-                  static_cast<float>(d->norm_p), n_conc, cols / n_conc};
-        const int it = static_cast<int>(ceil_div(a.nch, 16));
-        float* gs = grad_seg ? grad_seg + col0 : nullptr;
-        const unsigned grid = static_cast<unsigned>(n_conc * std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16 / n_conc));
-        int rc;
-        if (d->dtype == BESS_F32) {
-            rc = (vec == 4) ? seg_by_it<float, 4>(it, red, a, gs, tab, fused_sgd_lr, grid, st)
-                            : seg_by_it<float, 1>(it, red, a, gs, tab, fused_sgd_lr, grid, st);
-        } else {
-            rc = (vec == 8) ? seg_by_it<half_t, 8>(it, red, a, gs, tab, fused_sgd_lr, grid, st)
-                 : (vec == 2) ? seg_by_it<half_t, 2>(it, red, a, gs, tab, fused_sgd_lr, grid, st)
-                              : seg_by_it<half_t, 1>(it, red, a, gs, tab, fused_sgd_lr, grid, st);
-        }
-        if (rc) return rc;
-    }
+    const int64_t sz = scalar_bytes_of(d);
+    // one launch per window of `win` columns (n_conc of them side by side); lgrad: the slices of the long segments
+    auto launch_windows = [&](int win, int n_conc, unsigned grid, float* lgrad, int32_t* lcnt, int32_t cap) {
+        return for_each_window(W, win, vec, n_conc, [&](const ColWindow& w) {
+            char* tab = static_cast<char*>(table) + w.col0 * sz;
+            SegOpt wopt = opt;  // the window's columns of the state tables and of the extra gradients
+            wopt.state1 = w.at(wopt.state1);
+            wopt.state2 = w.at(wopt.state2);
+            wopt.xsum = w.at(wopt.xsum);
+            const SegArgs a{query + w.col0, tab, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg,
+                            static_cast<int>(n_neg), W, w.nch, is_distance(d->scorer) ? -1.f : 1.f, long_segs, wopt,
+                            static_cast<float>(d->norm_p), n_conc, w.cols / n_conc};
+            float* gs = w.at(grad_seg);
+            float* lg = w.at(lgrad);
+            const bool ok = dispatch_row_class<NativeRows>(d->dtype, vec, w.it, [&](auto c) {
+                using C = decltype(c);
+                using T = typename C::T;
+                T* rw = reinterpret_cast<T*>(tab);
+                with_constant<RED_DOT, RED_L1, RED_L2>(red, [&](auto r) {
+                    constexpr int RED = decltype(r)::value;
+                    if (lg)
+                        k_long_segments<T, C::VEC, C::IT, RED>
+                            <<<grid, 256, 0, st>>>(a, lg, lcnt, cap, gs, rw, fused_sgd_lr);
+                    else
+                        k_pertriple_grad_segments<T, C::VEC, C::IT, RED><<<grid, 256, 0, st>>>(a, gs, rw, fused_sgd_lr);
+                });
+            });
+            return ok ? BESS_OK : fail(BESS_EUNSUPPORTED, "grad_segments: row of %d scalars too wide", W);
+        });
+    };
+    // 16 segments per 256-thread workgroup; grid-stride over the (device-side) segment count
+    const unsigned grid = static_cast<unsigned>(n_conc * std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16 / n_conc));
+    if (int rc = launch_windows(win, n_conc, grid, nullptr, nullptr, 0)) return rc;
     if (long_segs) {  // the rows left out above (usually none: one launch that finds nothing to do)
-        const int32_t cap = static_cast<int32_t>(long_cap);
         // whole rows, unless they are wider than a group's registers (windows as above; the scratch rows and the
         // counters are left zero by every launch, so the windows can share them)
         const int lwin = (red != RED_L2 && W > 16 * unit) ? 16 * unit : W;
-        for (int col0 = 0; col0 < W; col0 += lwin) {
-            const int cols = W - col0 < lwin ? W - col0 : lwin;
-            SegOpt wopt = opt;
-            if (wopt.state1) wopt.state1 += col0;
-            if (wopt.state2) wopt.state2 += col0;
-            if (wopt.xsum) wopt.xsum += col0;
-            char* tab = static_cast<char*>(table) + col0 * sz;
-            SegArgs a{query + col0, tab, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg,
-                      static_cast<int>(n_neg), W, cols / vec, is_distance(d->scorer) ? -1.f : 1.f, long_segs, wopt,
-                      static_cast<float>(d->norm_p), 1, cols};
-            const int it = static_cast<int>(ceil_div(a.nch, 16));
-            const unsigned lgrid = 1024;  // 16 K groups share the slices
-            float* gs = grad_seg ? grad_seg + col0 : nullptr;
-            float* lg = long_grad + col0;
-            int rc;
-            if (d->dtype == BESS_F32) {
-                rc = (vec == 4) ? seg_by_it<float, 4>(it, red, a, gs, tab, fused_sgd_lr, lgrid, st, lg, long_count, cap)
-                                : seg_by_it<float, 1>(it, red, a, gs, tab, fused_sgd_lr, lgrid, st, lg, long_count, cap);
-            } else {
-                rc = (vec == 8) ? seg_by_it<half_t, 8>(it, red, a, gs, tab, fused_sgd_lr, lgrid, st, lg, long_count, cap)
-                     : (vec == 2) ? seg_by_it<half_t, 2>(it, red, a, gs, tab, fused_sgd_lr, lgrid, st, lg, long_count, cap)
-                                  : seg_by_it<half_t, 1>(it, red, a, gs, tab, fused_sgd_lr, lgrid, st, lg, long_count, cap);
-            }
-            if (rc) return rc;
-        }
+        // (1024 workgroups: 16 K groups share the slices)
+        if (int rc = launch_windows(lwin, 1, 1024u, long_grad, long_count, static_cast<int32_t>(long_cap))) return rc;
     }
     return check_launch("neg_pertriple_grad_segments");
 }

@@ -2,7 +2,7 @@
 reduction that hangs off them (`bess_neg_pertriple_grad_segments`, csrc/segments.hip) and the query / positive-score
 kernels of csrc/prepare.hip against float64 - other tests use these kernels AS their reference (the row-ordered and the
 fused forward, the segment tests, the small step, the optimisers), so they are anchored here, in every class the host
-dispatch (`run` -> `by_it` -> `by_red`, `seg_by_it` -> `seg_by_red`) selects:
+dispatch (`dispatch_row_class<NativeRows>` of csrc/common.h, called by `run` and `grad_segments_impl`) selects:
 
   0. the reference itself, on the CPU (no device): the K5 rule of include/besskge_hip.h in float64 with closed-form
      gradients == `oracle.kge._reduce` and its float64 autograd; the (VEC, IT, window) class of every width; the
