@@ -285,6 +285,10 @@ inline hipError_t fill_words_async(void* p, uint32_t v, int64_t n_words, hipStre
 // p=scoring_norm)`).  The kernels' RED_L2 branch carries p at run time: p = 2 keeps its multiply / sqrt (a
 // wave-uniform test), every other p goes through powf.   norm = (sum |d|^p)^(1/p);   d norm / d d_w =
 // sgn(d_w) |d_w|^(p-1) * norm^(1-p).
+// (The row-ordered forward's pipelined p = 2 loop, add_square in neg_pertriple.hip, writes `acc += lp_term(d, 2)` out
+// as an unfused product and sum, because that is what the compiler makes of `acc += lp_term(d, p)` with p at run time:
+// the product leaves the branch on p before it is added.  Its scores must equal k_neg_pertriple_fwd's bit for bit, so
+// a change of this term, or a toolchain that fuses it, has to be met there.)
 __device__ __forceinline__ float lp_term(float d, float p) { return p == 2.f ? d * d : powf(fabsf(d), p); }
 __device__ __forceinline__ float lp_root(float acc, float p) { return p == 2.f ? sqrtf(acc) : powf(acc, 1.f / p); }
 __device__ __forceinline__ float lp_dterm(float d, float p) {

@@ -249,9 +249,120 @@ struct SweepArgs {
     int qstride;   // floats per staged query (IT * 16 * VEC)
 };
 
+// acc + d * d in two roundings: lp_term's p == 2 term as k_neg_pertriple_fwd adds it, where the product comes out of
+// the branch on p and is never fused into the sum (see the note at lp_term in common.h: the two must change together;
+// tests/test_pertriple_l2_sweep.py and test_pertriple_sweep_pipeline.py compare them bit for bit)
+__device__ __forceinline__ float add_square(float acc, float d) {
+#pragma clang fp contract(off)
+    const float m = d * d;
+    return acc + m;
+}
+
+// The sweep of one wave over its entries e0, e0 + 16 UNROLL, ... < n of the share (e0 < n), software-pipelined: two
+// register sets of UNROLL rows as loaded (table type: converted when scored); the rows of iteration i + 1 are issued
+// before iteration i is scored, so a wave has row loads in flight all the time but in its last iteration, which
+// issues nothing.  The loop holds no branch around a load (the compiler's wait counts stay exact) and every row
+// address comes from an entry clamped into [0, n).  Lanes past the row's end read its last chunk and score zeros, as
+// load_chunk gives them.
+// !PIPE: one register set, each iteration waits for its own rows - for the p-norms that go through powf, which are
+// bound by that arithmetic and whose scoring code leaves no room for a second set; PIPE with RED_L2 means p == 2.
+template <typename T, int VEC, int IT, int RED, int UNROLL, bool PIPE>
+__device__ __forceinline__ void sweep_share(const NegPtArgs& a, const float* qs, int qstride, const int2* ent, int n,
+                                            int e0, float* __restrict__ oblk, int64_t ld_out) {
+    typedef T raw_t __attribute__((ext_vector_type(VEC)));
+    constexpr int STEP = 16 * UNROLL;
+    const int g = threadIdx.x & 15;
+    const int sub = (threadIdx.x & 63) >> 4;
+    const T* base = static_cast<const T*>(a.base);
+    auto entries = [&](int e, int2(&x)[UNROLL]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) x[u] = ent[min(e + sub + 4 * u, n - 1)];  // clamped: keeps the wave converged
+    };
+    auto issue = [&](const int2(&x)[UNROLL], raw_t(&r)[UNROLL][IT]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const T* rp = base + static_cast<int64_t>(x[u].x) * a.W;
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                r[u][it] = *reinterpret_cast<const raw_t*>(rp + min(g + 16 * it, a.nch - 1) * VEC);
+            }
+        }
+    };
+    auto score = [&](const int2(&x)[UNROLL], const raw_t(&r)[UNROLL][IT], int e) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const int qi = x[u].y >> 16;
+            const int kk = x[u].y & 0xffff;
+            const float* qp = qs + qi * qstride;
+            float acc = 0.f;
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                float qv[VEC];
+                VecLoad<float, VEC>::load(qp + (g + 16 * it) * VEC, qv);
+                const bool live = g + 16 * it < a.nch;
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    const float ev = live ? static_cast<float>(r[u][it][v]) : 0.f;
+                    if (RED == RED_DOT) {
+                        acc = fmaf(qv[v], ev, acc);
+                    } else if (RED == RED_L1) {
+                        acc += fabsf(qv[v] - ev);
+                    } else if (PIPE) {
+                        acc = add_square(acc, qv[v] - ev);
+                    } else {
+                        acc += lp_term(qv[v] - ev, a.p);
+                    }
+                }
+            }
+            acc = row16_allreduce_sum(acc);
+            if (RED == RED_L2) acc = PIPE ? sqrtf(acc) : lp_root(acc, a.p);
+            if (g == 0 && e + sub + 4 * u < n) oblk[qi * ld_out + kk] = a.sign * acc;
+        }
+    };
+
+    raw_t r0[UNROLL][IT], r1[UNROLL][IT];
+    int2 x0[UNROLL], x1[UNROLL], nx[UNROLL];  // nx: the entries of the iteration after the one in flight
+    entries(e0, x0);
+    if (!PIPE) {
+        for (; e0 < n; e0 += STEP) {
+            issue(x0, r0);
+            entries(e0 + STEP, x1);
+            score(x0, r0, e0);
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) x0[u] = x1[u];
+        }
+        return;
+    }
+    entries(e0 + STEP, nx);
+    issue(x0, r0);
+    // two iterations per trip, one per register set; the loop's only exit is at its top, so that no path on which a
+    // set is still in flight leads back into it
+    for (; e0 + 2 * STEP < n; e0 += 2 * STEP) {  // e0 is wave-uniform
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) x1[u] = nx[u];
+        entries(e0 + 2 * STEP, nx);
+        issue(x1, r1);
+        score(x0, r0, e0);
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) x0[u] = nx[u];
+        entries(e0 + 3 * STEP, nx);
+        issue(x0, r0);
+        score(x1, r1, e0 + STEP);
+    }
+    // one or two iterations are left, the first of them in flight
+    const bool two = e0 + STEP < n;
+    if (two) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) x1[u] = nx[u];
+        issue(x1, r1);
+    }
+    score(x0, r0, e0);
+    if (two) score(x1, r1, e0 + STEP);
+}
+
 template <typename T, int VEC, int IT, int RED, int UNROLL>
-__global__ __launch_bounds__(256) void k_neg_pertriple_fwd_sweep(NegPtArgs a, SweepArgs s, float* __restrict__ out,
-                                                                 int64_t ld_out) {
+__global__ __launch_bounds__(256, 2) void k_neg_pertriple_fwd_sweep(NegPtArgs a, SweepArgs s, float* __restrict__ out,
+                                                                    int64_t ld_out) {
     // (static arrays of whole 16-B units: the dynamic region after them stays 16-B aligned)
     extern __shared__ __attribute__((aligned(16))) float qs[];  // [qb][IT * 16 chunks][VEC]
     __shared__ int hist[SW_NB + 4];  // counts, then bucket starts (hist[SW_NB] = P), then slot cursors
@@ -398,54 +509,19 @@ __global__ __launch_bounds__(256) void k_neg_pertriple_fwd_sweep(NegPtArgs a, Sw
     }
     __syncthreads();
 
-    // the sweep: 16-lane group `sub` of wave `wave` scores entries it * 16 * UNROLL + wave * 4 * UNROLL + sub + 4 u
+    // the sweep (sweep_share): in its i-th iteration, 16-lane group `sub` of wave `wave` scores the entries
+    // i * 16 * UNROLL + wave * 4 * UNROLL + sub + 4 u, u < UNROLL
     const int n = hi - lo;
-    const int g = lane & 15;
-    const int sub = lane >> 4;
-    const T* base = static_cast<const T*>(a.base);
-    int2 nx[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) nx[u] = ent[max(0, min(wave * 4 * UNROLL + sub + 4 * u, n - 1))];
-    for (int e0 = wave * 4 * UNROLL; e0 < n; e0 += 16 * UNROLL) {  // wave-uniform
-        float ev[UNROLL][IT][VEC];
-        int2 cur[UNROLL];
-        bool valid[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const int e = e0 + sub + 4 * u;
-            valid[u] = e < n;
-            cur[u] = nx[u];
-            const T* rp = base + static_cast<int64_t>(cur[u].x) * a.W;  // clamped entry: keeps the wave converged
-            nx[u] = ent[min(e + 16 * UNROLL, n - 1)];
-#pragma unroll
-            for (int it = 0; it < IT; ++it) load_chunk<T, VEC>(rp, g + 16 * it, a.nch, ev[u][it]);
-        }
-#pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
-            const int qi = cur[u].y >> 16;
-            const int kk = cur[u].y & 0xffff;
-            const float* qp = qs + qi * s.qstride;
-            float acc = 0.f;
-#pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                float qv[VEC];
-                VecLoad<float, VEC>::load(qp + (g + 16 * it) * VEC, qv);
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    if (RED == RED_DOT) {
-                        acc = fmaf(qv[v], ev[u][it][v], acc);
-                    } else if (RED == RED_L1) {
-                        acc += fabsf(qv[v] - ev[u][it][v]);
-                    } else {
-                        acc += lp_term(qv[v] - ev[u][it][v], a.p);
-                    }
-                }
-            }
-            acc = row16_allreduce_sum(acc);
-            if (RED == RED_L2) acc = lp_root(acc, a.p);
-            if (g == 0 && valid[u]) out[(q0 + qi) * ld_out + kc0 + kk] = a.sign * acc;
-        }
-    }
+    // wave-uniform, and through readfirstlane the compiler knows it: the loop's counter and branches are scalar
+    const int e0 = __builtin_amdgcn_readfirstlane(wave) * 4 * UNROLL;
+    // A wave without an entry loads nothing: ent[] holds n entries and is uninitialised LDS past them - all of it when
+    // the share is empty.  (No barrier follows, so the wave may leave.)
+    if (e0 >= n) return;
+    float* oblk = out + q0 * ld_out + kc0;
+    if (RED == RED_L2 && a.p != 2.f)
+        sweep_share<T, VEC, IT, RED, UNROLL, false>(a, qs, s.qstride, ent, n, e0, oblk, ld_out);
+    else
+        sweep_share<T, VEC, IT, RED, UNROLL, true>(a, qs, s.qstride, ent, n, e0, oblk, ld_out);
 }
 
 // d loss / d query from the items' partials, one wave per query (loss_rows.h: combine_dq_row)
