@@ -155,7 +155,8 @@ def test_training_step_dispatch_count_c4_notebook_shape(dev):
 def test_direct_update_equals_the_indexed_update(dev, dtype, opt_name):
     """bess_direct_update (gradient rows added into a [M, W] accumulator at their row ids, one wave per reference
     claims its row) against bess_build_segment_index + bess_coalesced_update on the same lists: duplicates inside
-    and across lists, several steps (the accumulator and the generation stamps are left consistent)."""
+    and across lists, several steps (the accumulator and the generation stamps are left consistent).  Both sides share
+    `opt_step`: each is anchored to the float64 rule on its own in tests/test_row_update_kernels.py."""
     from besskge import _native as nat
 
     gen = torch.Generator().manual_seed(7)
