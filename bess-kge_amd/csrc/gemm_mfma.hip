@@ -191,6 +191,68 @@ __device__ __forceinline__ void stage_store(float* img, const Stage<TILE>& st) {
     }
 }
 
+// ---- one wave's MT x MT MFMA tiles: shared by the two kernels below ---------------------------
+template <int MT>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[MT][MT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// the 16 k steps of one slice: acc += A(wm .., k) B(k, wn ..) from the [k][m] / [k][n] images
+template <int MT, int LDA, int LDB>
+__device__ __forceinline__ void mfma_slice(const float* a_img, const float* b_img, f32x16 (&acc)[MT][MT], int wm, int wn,
+                                           int l31, int lk) {
+    // fragments of step kk + 2 are read while the MFMAs of step kk issue (two register
+    // sets): the LDS latency is off the MFMA issue path
+    float a[2][MT], b[2][MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        a[0][i] = a_img[lk * LDA + wm + 32 * i + l31];
+        b[0][i] = b_img[lk * LDB + wn + 32 * i + l31];
+    }
+#pragma unroll
+    for (int kk = 0; kk < GK; kk += 2) {
+        const int c = (kk >> 1) & 1;
+        if (kk + 2 < GK) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                a[c ^ 1][i] = a_img[(kk + 2 + lk) * LDA + wm + 32 * i + l31];
+                b[c ^ 1][i] = b_img[(kk + 2 + lk) * LDB + wn + 32 * i + l31];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // keep the reads above the MFMAs (the scheduler sinks them)
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < MT; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][i], b[c][j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+template <int MT>
+__device__ __forceinline__ void store_wave_tile(const f32x16 (&acc)[MT][MT], float* __restrict__ C, int64_t ldc,
+                                                int64_t m0, int64_t n0, int wm, int wn, int64_t M, int64_t N, int l31,
+                                                int lk) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j) {
+            const int64_t col = n0 + wn + j * 32 + l31;
+            if (col >= N) continue;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                if (row < M) C[row * ldc + col] = acc[i][j][r];
+            }
+        }
+}
+
 template <typename TA, bool A_ROWS_K, typename TB, bool B_ROWS_K, int TILE, bool FAST>
 __global__ __launch_bounds__(256) void k_gemm_f32_mfma(GemmOperand A, GemmOperand B, int64_t M, int64_t N,
                                                        int64_t K, float* __restrict__ C, int64_t ldc) {
@@ -212,12 +274,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32_mfma(GemmOperand A, GemmOperan
     const int l31 = lane & 31, lk = lane >> 5;
 
     f32x16 acc[MT][MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc<MT>(acc);
 
     // Two workgroups share a CU (one wave each per SIMD) and run the same code at the same rate:
     // started together they reach their load / LDS-store phases together and the matrix pipe
@@ -249,34 +306,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32_mfma(GemmOperand A, GemmOperan
             la.next_rows((s + 2) * GK);  // and the row indices of the slice after that
             lb.next_rows((s + 2) * GK);
         }
-        const float* a_img = As[cur];
-        const float* b_img = Bs[cur];
-        // fragments of step kk + 2 are read while the MFMAs of step kk issue (two register
-        // sets): the LDS latency is off the MFMA issue path
-        float a[2][MT], b[2][MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            a[0][i] = a_img[lk * LDA + wm + 32 * i + l31];
-            b[0][i] = b_img[lk * LDB + wn + 32 * i + l31];
-        }
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2) {
-            const int c = (kk >> 1) & 1;
-            if (kk + 2 < GK) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    a[c ^ 1][i] = a_img[(kk + 2 + lk) * LDA + wm + 32 * i + l31];
-                    b[c ^ 1][i] = b_img[(kk + 2 + lk) * LDB + wn + 32 * i + l31];
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);  // keep the reads above the MFMAs (the scheduler sinks them)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < MT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][i], b[c][j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        mfma_slice<MT, LDA, LDB>(As[cur], Bs[cur], acc, wm, wn, l31, lk);
         if (more) {
             la.fix((s + 1) * GK, sa);
             lb.fix((s + 1) * GK, sb);
@@ -285,20 +315,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32_mfma(GemmOperand A, GemmOperan
         }
         __syncthreads();
     }
-
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j) {
-            const int64_t col = n0 + wn + j * 32 + l31;
-            if (col >= N) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                if (row < M) C[row * ldc + col] = acc[i][j][r];
-            }
-        }
+    store_wave_tile<MT>(acc, C, ldc, m0, n0, wm, wn, M, N, l31, lk);
 }
 
 // Producer / consumer variant of the 128 x 128 kernel: 512 threads, waves 0-3 only issue
@@ -326,7 +343,6 @@ __global__ __launch_bounds__(512) void k_gemm_f32_mfma_ws(GemmOperand A, GemmOpe
     // also runs as a persistent grid (fewer workgroups than tiles); on this shape that measured
     // 93 vs 101 TFLOP/s, with either tile order and with one or two slices in flight.
     const int slot = blockIdx.x, slots = gridDim.x;
-    const int t_begin = 0, t_end = n_tiles;
     auto tile_origin = [&](int li, int64_t& m0, int64_t& n0) {
         m0 = static_cast<int64_t>(li / tiles_x) * TILE;
         n0 = static_cast<int64_t>(li % tiles_x) * TILE;
@@ -336,7 +352,7 @@ __global__ __launch_bounds__(512) void k_gemm_f32_mfma_ws(GemmOperand A, GemmOpe
         Stage<TILE> sa, sb;
         Loader<TA, A_ROWS_K, TILE, true> la;
         Loader<TB, B_ROWS_K, TILE, true> lb;
-        for (int tile = t_begin + slot; tile < t_end; tile += slots) {
+        for (int tile = slot; tile < n_tiles; tile += slots) {
             int64_t m0, n0;
             tile_origin(tile, m0, n0);
             la.init(A, m0, M, K);
@@ -366,58 +382,17 @@ __global__ __launch_bounds__(512) void k_gemm_f32_mfma_ws(GemmOperand A, GemmOpe
     const int wave = threadIdx.x >> 6;
     const int wm = (wave >> 1) * WT, wn = (wave & 1) * WT;
     const int l31 = lane & 31, lk = lane >> 5;
-    for (int tile = t_begin + slot; tile < t_end; tile += slots) {
+    for (int tile = slot; tile < n_tiles; tile += slots) {
         int64_t m0, n0;
         tile_origin(tile, m0, n0);
         f32x16 acc[MT][MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < MT; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        zero_acc<MT>(acc);
         __syncthreads();  // slice 0 stored
         for (int s = 0; s < n_slice; ++s) {
-            const float* a_img = As[s & 1];
-            const float* b_img = Bs[s & 1];
-            float a[2][MT], b[2][MT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                a[0][i] = a_img[lk * LDA + wm + 32 * i + l31];
-                b[0][i] = b_img[lk * LDB + wn + 32 * i + l31];
-            }
-#pragma unroll
-            for (int kk = 0; kk < GK; kk += 2) {
-                const int c = (kk >> 1) & 1;
-                if (kk + 2 < GK) {
-#pragma unroll
-                    for (int i = 0; i < MT; ++i) {
-                        a[c ^ 1][i] = a_img[(kk + 2 + lk) * LDA + wm + 32 * i + l31];
-                        b[c ^ 1][i] = b_img[(kk + 2 + lk) * LDB + wn + 32 * i + l31];
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < MT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[c][i], b[c][j], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            mfma_slice<MT, LDA, LDB>(As[s & 1], Bs[s & 1], acc, wm, wn, l31, lk);
             __syncthreads();  // done with slice s: its buffer may be refilled
         }
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < MT; ++j) {
-                const int64_t col = n0 + wn + j * 32 + l31;
-                if (col >= N) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int64_t row = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                    if (row < M) C[row * ldc + col] = acc[i][j][r];
-                }
-            }
+        store_wave_tile<MT>(acc, C, ldc, m0, n0, wm, wn, M, N, l31, lk);
     }
 }
 

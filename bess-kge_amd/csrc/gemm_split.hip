@@ -43,6 +43,12 @@
 //               8 ds_read_b128, 12 MFMAs.  The barrier that releases a slice sits between its
 //               two k steps (after both have been read into registers), so the fragment reads of
 //               the next slice are issued under the MFMAs of this one.
+//   k_gemm_split_w8    256 x 128 tiles, eight waves that each load and multiply (described at the kernel):
+//               forward products whose tiles fill the chip.
+// The two GEMM kernels share what a wave does with its 64 x 64: WaveTile (the accumulators, the lane's fragment
+// offsets, the fragment reads and the MFMA group of a k step) and wave_tile_epilogue<EPI> (stores / pruned stores /
+// counts) exist once.  A kernel owns its tile shape, the way slices reach LDS, and how it interleaves reads and
+// MFMAs.  launch_product picks the instantiation from one [B_LO][EPI] table per kernel.
 #include "common.h"
 
 namespace bess {
@@ -69,6 +75,12 @@ struct SplitSrc {
 
 // an element the split cannot represent (hi would be inf / nan): the product then falls back to the fp32 kernels
 __device__ __forceinline__ bool unsplittable(float x) { return !(fabsf(x) < 65504.f); }
+
+// the two halves of x = hi + lo / 2048 (x - hi is exact in fp32)
+__device__ __forceinline__ void split_hi_lo(float x, _Float16& hi, _Float16& lo) {
+    hi = static_cast<_Float16>(x);
+    lo = static_cast<_Float16>((x - static_cast<float>(hi)) * 2048.f);
+}
 
 // 16-B slot `c` (0..7) of image row `row`, swizzled: rows r, r+2, .. r+14 of one parity land
 // on the 8 slots of their half of the 256-B bank row
@@ -99,8 +111,10 @@ __device__ __forceinline__ void split_rows_body(const SplitSrc& src, int W, int 
     bool bad = false;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        hi[i] = static_cast<_Float16>(x[i]);
-        lo[i] = static_cast<_Float16>((x[i] - static_cast<float>(hi[i])) * 2048.f);
+        _Float16 h, l;
+        split_hi_lo(x[i], h, l);
+        hi[i] = h;
+        lo[i] = l;
         bad |= unsplittable(x[i]);
     }
     if (bad && src.range_flag) atomicOr(src.range_flag, 1);
@@ -165,8 +179,8 @@ __global__ __launch_bounds__(256) void k_split_tile32(SplitSrc src, int64_t C, c
         h8 o;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const _Float16 hi = static_cast<_Float16>(x[i]);
-            const _Float16 lo = static_cast<_Float16>((x[i] - static_cast<float>(hi)) * 2048.f);
+            _Float16 hi, lo;
+            split_hi_lo(x[i], hi, lo);
             o[i] = piece < 4 ? hi : lo;
         }
         *reinterpret_cast<h8*>(line + piece * 16) = o;
@@ -252,8 +266,181 @@ __device__ __forceinline__ f32x16 mma16(h8 a, h8 b, f32x16 c) {
 #define BESS_TICK_BARRIER(acc) __syncthreads()
 #endif
 
+// ---- one wave's 64 x 64 of a tile: shared by the two GEMM kernels below ----------------------
+// 2 x 2 MFMA tiles x {main, corr} accumulators over the images of a slice; B_LO: B has a lo half (fp32 table)
+struct Frags {
+    h8 a[2][2], b[2][2];  // [row block][hi | lo]
+};
+
+struct WaveTile {
+    f32x16 accm[2][2], accc[2][2];
+    int off_a[2][2], off_b[2][2];  // byte offsets of this lane's fragments: [k step][hi | lo], row block i adds 32 rows
+
+    // wave tile at rows wm of A's image and rows wn of B's, which starts b_base bytes into the buffer it is read from
+    __device__ __forceinline__ void init(int wm, int wn, int l31, int lk, int b_base) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int part = 0; part < 2; ++part) {
+                off_a[ks][part] = slot_off(wm + l31, ks * 2 + lk + 4 * part);
+                off_b[ks][part] = b_base + slot_off(wn + l31, ks * 2 + lk + 4 * part);
+            }
+        zero();
+    }
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    accm[i][j][r] = 0.f;
+                    accc[i][j][r] = 0.f;
+                }
+    }
+    // the 8 (B_LO) or 6 fragment reads of k step ks
+    template <bool B_LO>
+    __device__ __forceinline__ void read(Frags& f, const char* ia, const char* ib, int ks) const {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            f.a[i][0] = *reinterpret_cast<const h8*>(ia + off_a[ks][0] + i * 32 * ROW_B);
+            f.a[i][1] = *reinterpret_cast<const h8*>(ia + off_a[ks][1] + i * 32 * ROW_B);
+            f.b[i][0] = *reinterpret_cast<const h8*>(ib + off_b[ks][0] + i * 32 * ROW_B);
+            if (B_LO) f.b[i][1] = *reinterpret_cast<const h8*>(ib + off_b[ks][1] + i * 32 * ROW_B);
+        }
+    }
+    // the 12 (B_LO) or 8 MFMAs of a k step: main = hi.hi, then corr = lo.hi (+ hi.lo)
+    template <bool B_LO>
+    __device__ __forceinline__ void mma(const Frags& f) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) accm[i][j] = mma16(f.a[i][0], f.b[j][0], accm[i][j]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) accc[i][j] = mma16(f.a[i][1], f.b[j][0], accc[i][j]);
+        if (B_LO) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) accc[i][j] = mma16(f.a[i][0], f.b[j][1], accc[i][j]);
+        }
+    }
+};
+
+// Scheduling of one k step's MFMAs with the fragment reads issued next to them (128 x 128 kernel): one read per
+// MFMA gap, then the remaining MFMAs
+template <bool B_LO>
+__device__ __forceinline__ void interleave_reads() {
+    constexpr int N_RD = B_LO ? 8 : 6, N_MM = B_LO ? 12 : 8;
+#pragma unroll
+    for (int q = 0; q < N_RD; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x008, N_MM - N_RD, 0);
+}
+
+// A finished wave tile (rows m0 .., columns n0 .. of the M x N product): main + corr / 2048 -> C, where c0 points at
+// this lane's first element.  C/D layout of the 32x32 MFMA: col = lane & 31 (l31),
+// row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (lk).
+template <int EPI>  // 0 stores, 1 pruned stores (top-k passes), 2 counts (ranks; nothing is stored)
+__device__ __forceinline__ void wave_tile_epilogue(const f32x16 (&accm)[2][2], const f32x16 (&accc)[2][2], int64_t m0,
+                                                   int64_t n0, float* __restrict__ c0, int64_t ldc, int64_t M, int64_t N,
+                                                   const float* __restrict__ thr, uint8_t* __restrict__ pflags,
+                                                   int64_t ldf, const CountArgs& cnt, int l31, int lk) {
+    if constexpr (EPI == 2) {
+        // counting epilogue (ranks): nothing is stored.  Lane l of the wave keeps the two counts of row
+        // m0 + l: a row's 64 scores sit in the 32 lanes of one lk, so one ballot per comparison holds two
+        // rows' verdicts (low half: row rr, high half: rr + 4), counted with s_bcnt1 and kept by the
+        // row's lane; one pair of atomics per row and tile at the end
+        const int l64 = threadIdx.x & 63;
+        const bool rok = m0 + l64 < M;
+        const int tv = __builtin_bit_cast(int, rok ? thr[m0 + l64] : INFINITY);
+        // the row's excluded column, relative to this wave's first one (anything outside 0 .. 63: none here)
+        int64_t exl = rok ? static_cast<int64_t>(cnt.excl[m0 + l64]) - (cnt.col0 + n0) : -1;
+        const int ex = (exl >= 0 && exl < 64) ? static_cast<int>(exl) : -1;
+        int cgt = 0, ceq = 0;
+        const bool ok0 = n0 + l31 < N, ok1 = n0 + l31 + 32 < N;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
+                const float th0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr));
+                const float th1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr + 4));
+                const int e0 = __builtin_amdgcn_readlane(ex, rr), e1 = __builtin_amdgcn_readlane(ex, rr + 4);
+                const float th = lk ? th1 : th0;
+                const int e = lk ? e1 : e0;
+                const float v0 = count_value(accm[i][0][r] + accc[i][0][r] * (1.f / 2048.f), cnt.round16);
+                const float v1 = count_value(accm[i][1][r] + accc[i][1][r] * (1.f / 2048.f), cnt.round16);
+                const bool in0 = ok0 && l31 != e, in1 = ok1 && l31 + 32 != e;
+                const unsigned long long g0 = __ballot(in0 && v0 > th), g1 = __ballot(in1 && v1 > th);
+                const unsigned long long q0 = __ballot(in0 && v0 == th), q1 = __ballot(in1 && v1 == th);
+                const int gt_lo = __builtin_popcount(static_cast<unsigned>(g0)) + __builtin_popcount(static_cast<unsigned>(g1));
+                const int gt_hi = __builtin_popcount(static_cast<unsigned>(g0 >> 32)) + __builtin_popcount(static_cast<unsigned>(g1 >> 32));
+                const int eq_lo = __builtin_popcount(static_cast<unsigned>(q0)) + __builtin_popcount(static_cast<unsigned>(q1));
+                const int eq_hi = __builtin_popcount(static_cast<unsigned>(q0 >> 32)) + __builtin_popcount(static_cast<unsigned>(q1 >> 32));
+                if (l64 == rr) cgt = gt_lo, ceq = eq_lo;  // (every row of the wave is met exactly once)
+                if (l64 == rr + 4) cgt = gt_hi, ceq = eq_hi;
+            }
+        if (rok && n0 < N) {
+            if (cgt) atomicAdd(cnt.counts + 2 * (m0 + l64), cgt);
+            if (ceq) atomicAdd(cnt.counts + 2 * (m0 + l64) + 1, ceq);
+        }
+    } else if constexpr (EPI == 1) {
+        // pruned stores (top-k passes): the 32 lanes with this lk hold a row's 64 columns - the row's block
+        // is written only when one of them is above the row's threshold, and flagged.  The thresholds of
+        // the wave's 64 rows come in with ONE load (lane l: row m0 + l) and are read out per row with
+        // v_readlane; the rows' verdicts are collected in a scalar mask and leave as one byte store per lane
+        const int l64 = threadIdx.x & 63;
+        const int tv = __builtin_bit_cast(int, (m0 + l64 < M) ? thr[m0 + l64] : INFINITY);
+        unsigned long long rows_hit = 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
+                const float th0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr));
+                const float th1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr + 4));
+                const float th = lk ? th1 : th0;
+                const bool ok0 = n0 + l31 < N, ok1 = n0 + l31 + 32 < N;
+                const float v0 = accm[i][0][r] + accc[i][0][r] * (1.f / 2048.f);
+                const float v1 = accm[i][1][r] + accc[i][1][r] * (1.f / 2048.f);
+                const unsigned long long hits = __ballot((ok0 && v0 > th) || (ok1 && v1 > th));
+                const bool any0 = (hits & 0xffffffffull) != 0, any1 = (hits >> 32) != 0;
+                rows_hit |= (any0 ? 1ull << rr : 0ull) | (any1 ? 1ull << (rr + 4) : 0ull);
+                if (lk ? any1 : any0) {  // (rows past M have threshold +inf: never stored)
+                    if (ok0) c0[rr * ldc] = v0;
+                    if (ok1) c0[rr * ldc + 32] = v1;
+                }
+            }
+        if (m0 + l64 < M && n0 < N) pflags[(m0 + l64) * ldf + n0 / 64] = (rows_hit >> l64) & 1ull;
+    } else if (m0 + 64 <= M && n0 + 64 <= N) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    c0[(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc + j * 32] = accm[i][j][r] + accc[i][j][r] * (1.f / 2048.f);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int rr = i * 32 + (r & 3) + 8 * (r >> 2);
+                    if (m0 + 4 * lk + rr < M && n0 + l31 + j * 32 < N)
+                        c0[rr * ldc + j * 32] = accm[i][j][r] + accc[i][j][r] * (1.f / 2048.f);
+                }
+    }
+}
+
 // A, B: split images of M and N rows (n_slice lines each); C[m, n] = A[m] . B[n]
-template <bool B_LO, int EPI>  // EPI: 0 stores, 1 pruned stores (top-k passes), 2 counts (ranks; nothing is stored)
+template <bool B_LO, int EPI>  // EPI: see wave_tile_epilogue
 // Split K (the backward products have few output tiles and a long k): a "tile" index t stands for
 // output tile t / ksplit and the k range [t % ksplit, +1) * n_slice lines; part p of an output
 // tile goes to C + p * part_stride (summed in a fixed order by k_sum_parts: deterministic).
@@ -332,183 +519,38 @@ __global__ __launch_bounds__(512) void k_gemm_split_f16(const char* __restrict__
     const int wave = threadIdx.x >> 6;
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int l31 = lane & 31, lk = lane >> 5;
-    // byte offsets of this lane's fragments inside an image: [k step][hi | lo], row block i adds 32 rows
-    int off_a[2][2], off_b[2][2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-            off_a[ks][part] = slot_off(wm + l31, ks * 2 + lk + 4 * part);
-            off_b[ks][part] = slot_off(wn + l31, ks * 2 + lk + 4 * part);
-        }
-
-    f32x16 accm[2][2], accc[2][2];
-    auto zero = [&]() {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    accm[i][j][r] = 0.f;
-                    accc[i][j][r] = 0.f;
-                }
-    };
-    zero();
-
-    h8 fa[2][2][2], fb[2][2][2];  // [register set][row block][hi | lo]
-#define BESS_RD(set, g, ks)                                                                          \
-    {                                                                                                \
-        const char* ia = lds[(g) & 1][0];                                                            \
-        const char* ib = lds[(g) & 1][1];                                                            \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                              \
-            fa[set][i][0] = *reinterpret_cast<const h8*>(ia + off_a[ks][0] + i * 32 * ROW_B);        \
-            fa[set][i][1] = *reinterpret_cast<const h8*>(ia + off_a[ks][1] + i * 32 * ROW_B);        \
-            fb[set][i][0] = *reinterpret_cast<const h8*>(ib + off_b[ks][0] + i * 32 * ROW_B);        \
-            if (B_LO) fb[set][i][1] = *reinterpret_cast<const h8*>(ib + off_b[ks][1] + i * 32 * ROW_B); \
-        }                                                                                            \
-    }
-#define BESS_MM_MAIN(set)                                                                                   \
-    {                                                                                                       \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)         \
-            accm[i][j] = mma16(fa[set][i][0], fb[set][j][0], accm[i][j]); \
-    }
-#define BESS_MM_CORR(set)                                                                                   \
-    {                                                                                                       \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)         \
-            accc[i][j] = mma16(fa[set][i][1], fb[set][j][0], accc[i][j]); \
-        if (B_LO) {                                                                                         \
-            _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)     \
-                accc[i][j] = mma16(fa[set][i][0], fb[set][j][1], accc[i][j]); \
-        }                                                                                                   \
-    }
+    WaveTile wt;
+    wt.init(wm, wn, l31, lk, 0);
+    Frags f[2];  // two register sets
+    auto read = [&](Frags& x, int g, int ks) { wt.read<B_LO>(x, lds[g & 1][0], lds[g & 1][1], ks); };
 
     // Per slice: [12 MFMAs of k-step 0, the 8 fragment reads of k-step 1 slotted one per MFMA gap]
     // barrier [12 MFMAs of k-step 1, with the reads of k-step 0 of the next slice].  A burst of
     // reads between two MFMAs would leave the pipe idle while they issue; one per gap is hidden
     // (profiles/ubench/mfma_f16.hip).  Every read has >= 4 MFMAs (128 cycles) before its first
     // use and the barrier finds the slice already in registers.
-    constexpr int N_RD = B_LO ? 8 : 6, N_MM = B_LO ? 12 : 8;
-#define BESS_INTERLEAVE()                                                  \
-    {                                                                      \
-        _Pragma("unroll") for (int q = 0; q < N_RD; ++q) {                 \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             \
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);             \
-        }                                                                  \
-        __builtin_amdgcn_sched_group_barrier(0x008, N_MM - N_RD, 0);       \
-    }
     int s = 0, tile = slot;
     __syncthreads();  // slice 0 stored
-    BESS_RD(0, 0, 0);
+    read(f[0], 0, 0);
     for (int g = 0; g < total; ++g) {
         __builtin_amdgcn_sched_barrier(0);
-        BESS_RD(1, g, 1);
-        BESS_MM_MAIN(0);
-        BESS_MM_CORR(0);
-        BESS_INTERLEAVE();
+        read(f[1], g, 1);
+        wt.mma<B_LO>(f[0]);
+        interleave_reads<B_LO>();
         __builtin_amdgcn_sched_barrier(0);
         BESS_TICK_BARRIER(cw);  // slice g is in registers (buffer released); slice g + 1 is stored
         __builtin_amdgcn_sched_barrier(0);
-        BESS_RD(0, g + 1, 0);  // after the last slice: a stale image, never used
-        BESS_MM_MAIN(1);
-        BESS_MM_CORR(1);
-        BESS_INTERLEAVE();
+        read(f[0], g + 1, 0);  // after the last slice: a stale image, never used
+        wt.mma<B_LO>(f[1]);
+        interleave_reads<B_LO>();
         __builtin_amdgcn_sched_barrier(0);
-        if (++s == n_slice) {  // tile done: main + corr / 2048 -> C
+        if (++s == n_slice) {  // tile done
             const int ot = tile / ksplit;
             const int64_t m0 = static_cast<int64_t>(tiles_x ? ot / tiles_x : ot) * 128 + wm;
             const int64_t n0 = static_cast<int64_t>(tiles_x ? ot % tiles_x : ot) * 128 + wn;
-            // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
             float* c0 = C + (tile % ksplit) * part_stride + (m0 + 4 * lk) * ldc + (tiles_x ? n0 : wn) + l31;
-            if constexpr (EPI == 2) {
-                // counting epilogue (ranks): nothing is stored.  Lane l of the wave keeps the two counts of row
-                // m0 + l: a row's 64 scores sit in the 32 lanes of one lk, so one ballot per comparison holds two
-                // rows' verdicts (low half: row rr, high half: rr + 4), counted with s_bcnt1 and kept by the
-                // row's lane; one pair of atomics per row and tile at the end
-                const int l64 = threadIdx.x & 63;
-                const bool rok = m0 + l64 < M;
-                const int tv = __builtin_bit_cast(int, rok ? thr[m0 + l64] : INFINITY);
-                // the row's excluded column, relative to this wave's first one (anything outside 0 .. 63: none here)
-                int64_t exl = rok ? static_cast<int64_t>(cnt.excl[m0 + l64]) - (cnt.col0 + n0) : -1;
-                const int ex = (exl >= 0 && exl < 64) ? static_cast<int>(exl) : -1;
-                int cgt = 0, ceq = 0;
-                const bool ok0 = n0 + l31 < N, ok1 = n0 + l31 + 32 < N;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
-                        const float th0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr));
-                        const float th1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr + 4));
-                        const int e0 = __builtin_amdgcn_readlane(ex, rr), e1 = __builtin_amdgcn_readlane(ex, rr + 4);
-                        const float th = lk ? th1 : th0;
-                        const int e = lk ? e1 : e0;
-                        const float v0 = count_value(accm[i][0][r] + accc[i][0][r] * (1.f / 2048.f), cnt.round16);
-                        const float v1 = count_value(accm[i][1][r] + accc[i][1][r] * (1.f / 2048.f), cnt.round16);
-                        const bool in0 = ok0 && l31 != e, in1 = ok1 && l31 + 32 != e;
-                        const unsigned long long g0 = __ballot(in0 && v0 > th), g1 = __ballot(in1 && v1 > th);
-                        const unsigned long long q0 = __ballot(in0 && v0 == th), q1 = __ballot(in1 && v1 == th);
-                        const int gt_lo = __builtin_popcount(static_cast<unsigned>(g0)) + __builtin_popcount(static_cast<unsigned>(g1));
-                        const int gt_hi = __builtin_popcount(static_cast<unsigned>(g0 >> 32)) + __builtin_popcount(static_cast<unsigned>(g1 >> 32));
-                        const int eq_lo = __builtin_popcount(static_cast<unsigned>(q0)) + __builtin_popcount(static_cast<unsigned>(q1));
-                        const int eq_hi = __builtin_popcount(static_cast<unsigned>(q0 >> 32)) + __builtin_popcount(static_cast<unsigned>(q1 >> 32));
-                        if (l64 == rr) cgt = gt_lo, ceq = eq_lo;  // (every row of the wave is met exactly once)
-                        if (l64 == rr + 4) cgt = gt_hi, ceq = eq_hi;
-                    }
-                if (rok && n0 < N) {
-                    if (cgt) atomicAdd(cnt.counts + 2 * (m0 + l64), cgt);
-                    if (ceq) atomicAdd(cnt.counts + 2 * (m0 + l64) + 1, ceq);
-                }
-            } else if constexpr (EPI == 1) {
-                // pruned stores (top-k passes): the 32 lanes with this lk hold a row's 64 columns - the row's block
-                // is written only when one of them is above the row's threshold, and flagged.  The thresholds of
-                // the wave's 64 rows come in with ONE load (lane l: row m0 + l) and are read out per row with
-                // v_readlane; the rows' verdicts are collected in a scalar mask and leave as one byte store per lane
-                const int l64 = threadIdx.x & 63;
-                const int tv = __builtin_bit_cast(int, (m0 + l64 < M) ? thr[m0 + l64] : INFINITY);
-                unsigned long long rows_hit = 0;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
-                        const float th0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr));
-                        const float th1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr + 4));
-                        const float th = lk ? th1 : th0;
-                        const bool ok0 = n0 + l31 < N, ok1 = n0 + l31 + 32 < N;
-                        const float v0 = accm[i][0][r] + accc[i][0][r] * (1.f / 2048.f);
-                        const float v1 = accm[i][1][r] + accc[i][1][r] * (1.f / 2048.f);
-                        const unsigned long long hits = __ballot((ok0 && v0 > th) || (ok1 && v1 > th));
-                        const bool any0 = (hits & 0xffffffffull) != 0, any1 = (hits >> 32) != 0;
-                        rows_hit |= (any0 ? 1ull << rr : 0ull) | (any1 ? 1ull << (rr + 4) : 0ull);
-                        if (lk ? any1 : any0) {  // (rows past M have threshold +inf: never stored)
-                            if (ok0) c0[rr * ldc] = v0;
-                            if (ok1) c0[rr * ldc + 32] = v1;
-                        }
-                    }
-                if (m0 + l64 < M && n0 < N) pflags[(m0 + l64) * ldf + n0 / 64] = (rows_hit >> l64) & 1ull;
-            } else if (m0 + 64 <= M && n0 + 64 <= N) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            c0[(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc + j * 32] =
-                                accm[i][j][r] + accc[i][j][r] * (1.f / 2048.f);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int rr = i * 32 + (r & 3) + 8 * (r >> 2);
-                            if (m0 + 4 * lk + rr < M && n0 + l31 + j * 32 < N)
-                                c0[rr * ldc + j * 32] = accm[i][j][r] + accc[i][j][r] * (1.f / 2048.f);
-                        }
-            }
-            zero();
+            wave_tile_epilogue<EPI>(wt.accm, wt.accc, m0, n0, c0, ldc, M, N, thr, pflags, ldf, cnt, l31, lk);
+            wt.zero();
             s = 0;
             tile += slots;
         }
@@ -520,10 +562,6 @@ __global__ __launch_bounds__(512) void k_gemm_split_f16(const char* __restrict__
         C[3] = static_cast<float>(total);
     }
 #endif
-#undef BESS_RD
-#undef BESS_MM_MAIN
-#undef BESS_MM_CORR
-#undef BESS_INTERLEAVE
 }
 
 // ---- 256 x 128 tile, eight symmetric waves ------------------------------------------------
@@ -538,7 +576,7 @@ __global__ __launch_bounds__(512) void k_gemm_split_f16(const char* __restrict__
 // products are never stored), so a thread's six line pointers are one base plus constants.
 constexpr int W8_A = 256, W8_B = 128, W8_IMG = (W8_A + W8_B) * ROW_B;  // 48 KiB per buffer
 
-template <bool B_LO, int EPI>  // EPI: 0 stores, 1 pruned stores (top-k passes), 2 counts (ranks; nothing is stored)
+template <bool B_LO, int EPI>  // EPI: see wave_tile_epilogue
 __global__ __launch_bounds__(512) void k_gemm_split_w8(const char* __restrict__ A, const char* __restrict__ B,
                                                        int64_t M, int64_t N, int n_slice,
                                                        float* __restrict__ C, int64_t ldc, int tiles_x,
@@ -585,50 +623,12 @@ __global__ __launch_bounds__(512) void k_gemm_split_w8(const char* __restrict__ 
     // MFMA role: wave tile 64 x 64 at (wm, wn) of the 256 x 128 tile
     const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
     const int l31 = lane & 31, lk = lane >> 5;
-    int off_a[2][2], off_b[2][2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int part = 0; part < 2; ++part) {
-            off_a[ks][part] = slot_off(wm + l31, ks * 2 + lk + 4 * part);
-            off_b[ks][part] = W8_A * ROW_B + slot_off(wn + l31, ks * 2 + lk + 4 * part);
-        }
-    f32x16 accm[2][2], accc[2][2];
-    auto zero = [&]() {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    accm[i][j][r] = 0.f;
-                    accc[i][j][r] = 0.f;
-                }
-    };
-    zero();
-    auto kstep = [&](const char* img, int ks) {
-        h8 fa[2][2], fb[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            fa[i][0] = *reinterpret_cast<const h8*>(img + off_a[ks][0] + i * 32 * ROW_B);
-            fa[i][1] = *reinterpret_cast<const h8*>(img + off_a[ks][1] + i * 32 * ROW_B);
-            fb[i][0] = *reinterpret_cast<const h8*>(img + off_b[ks][0] + i * 32 * ROW_B);
-            if (B_LO) fb[i][1] = *reinterpret_cast<const h8*>(img + off_b[ks][1] + i * 32 * ROW_B);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) accm[i][j] = mma16(fa[i][0], fb[j][0], accm[i][j]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) accc[i][j] = mma16(fa[i][1], fb[j][0], accc[i][j]);
-        if (B_LO) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) accc[i][j] = mma16(fa[i][0], fb[j][1], accc[i][j]);
-        }
+    WaveTile wt;
+    wt.init(wm, wn, l31, lk, W8_A * ROW_B);
+    auto kstep = [&](const char* img, int ks) {  // fragments are single-buffered here
+        Frags f;
+        wt.read<B_LO>(f, img, img, ks);
+        wt.mma<B_LO>(f);
     };
 
     u32x4 r0[6], r1[6];  // slices g (even) / g (odd) on their way to LDS
@@ -645,100 +645,13 @@ __global__ __launch_bounds__(512) void k_gemm_split_w8(const char* __restrict__ 
         kstep(img, 1);
         put(lds8 + ((g + 1) & 1) * W8_IMG, next);  // slice g + 1 (after the last slice: a surplus copy)
         __syncthreads();
-        if (++s == n_slice) {  // tile done: main + corr / 2048 -> C
+        if (++s == n_slice) {  // tile done
             const int ot = tile / ksplit;
             const int64_t m0 = static_cast<int64_t>(ot / tiles_x) * W8_A + wm;
             const int64_t n0 = static_cast<int64_t>(ot % tiles_x) * W8_B + wn;
             float* c0 = C + (tile % ksplit) * part_stride + (m0 + 4 * lk) * ldc + n0 + l31;
-            if constexpr (EPI == 2) {
-                // counting epilogue (ranks): nothing is stored.  Lane l of the wave keeps the two counts of row
-                // m0 + l: a row's 64 scores sit in the 32 lanes of one lk, so one ballot per comparison holds two
-                // rows' verdicts (low half: row rr, high half: rr + 4), counted with s_bcnt1 and kept by the
-                // row's lane; one pair of atomics per row and tile at the end
-                const int l64 = threadIdx.x & 63;
-                const bool rok = m0 + l64 < M;
-                const int tv = __builtin_bit_cast(int, rok ? thr[m0 + l64] : INFINITY);
-                // the row's excluded column, relative to this wave's first one (anything outside 0 .. 63: none here)
-                int64_t exl = rok ? static_cast<int64_t>(cnt.excl[m0 + l64]) - (cnt.col0 + n0) : -1;
-                const int ex = (exl >= 0 && exl < 64) ? static_cast<int>(exl) : -1;
-                int cgt = 0, ceq = 0;
-                const bool ok0 = n0 + l31 < N, ok1 = n0 + l31 + 32 < N;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
-                        const float th0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr));
-                        const float th1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr + 4));
-                        const int e0 = __builtin_amdgcn_readlane(ex, rr), e1 = __builtin_amdgcn_readlane(ex, rr + 4);
-                        const float th = lk ? th1 : th0;
-                        const int e = lk ? e1 : e0;
-                        const float v0 = count_value(accm[i][0][r] + accc[i][0][r] * (1.f / 2048.f), cnt.round16);
-                        const float v1 = count_value(accm[i][1][r] + accc[i][1][r] * (1.f / 2048.f), cnt.round16);
-                        const bool in0 = ok0 && l31 != e, in1 = ok1 && l31 + 32 != e;
-                        const unsigned long long g0 = __ballot(in0 && v0 > th), g1 = __ballot(in1 && v1 > th);
-                        const unsigned long long q0 = __ballot(in0 && v0 == th), q1 = __ballot(in1 && v1 == th);
-                        const int gt_lo = __builtin_popcount(static_cast<unsigned>(g0)) + __builtin_popcount(static_cast<unsigned>(g1));
-                        const int gt_hi = __builtin_popcount(static_cast<unsigned>(g0 >> 32)) + __builtin_popcount(static_cast<unsigned>(g1 >> 32));
-                        const int eq_lo = __builtin_popcount(static_cast<unsigned>(q0)) + __builtin_popcount(static_cast<unsigned>(q1));
-                        const int eq_hi = __builtin_popcount(static_cast<unsigned>(q0 >> 32)) + __builtin_popcount(static_cast<unsigned>(q1 >> 32));
-                        if (l64 == rr) cgt = gt_lo, ceq = eq_lo;  // (every row of the wave is met exactly once)
-                        if (l64 == rr + 4) cgt = gt_hi, ceq = eq_hi;
-                    }
-                if (rok && n0 < N) {
-                    if (cgt) atomicAdd(cnt.counts + 2 * (m0 + l64), cgt);
-                    if (ceq) atomicAdd(cnt.counts + 2 * (m0 + l64) + 1, ceq);
-                }
-            } else if constexpr (EPI == 1) {
-                // pruned stores (top-k passes): the 32 lanes with this lk hold a row's 64 columns - the row's block
-                // is written only when one of them is above the row's threshold, and flagged.  The thresholds of
-                // the wave's 64 rows come in with ONE load (lane l: row m0 + l) and are read out per row with
-                // v_readlane; the rows' verdicts are collected in a scalar mask and leave as one byte store per lane
-                const int l64 = threadIdx.x & 63;
-                const int tv = __builtin_bit_cast(int, (m0 + l64 < M) ? thr[m0 + l64] : INFINITY);
-                unsigned long long rows_hit = 0;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
-                        const float th0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr));
-                        const float th1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(tv, rr + 4));
-                        const float th = lk ? th1 : th0;
-                        const bool ok0 = n0 + l31 < N, ok1 = n0 + l31 + 32 < N;
-                        const float v0 = accm[i][0][r] + accc[i][0][r] * (1.f / 2048.f);
-                        const float v1 = accm[i][1][r] + accc[i][1][r] * (1.f / 2048.f);
-                        const unsigned long long hits = __ballot((ok0 && v0 > th) || (ok1 && v1 > th));
-                        const bool any0 = (hits & 0xffffffffull) != 0, any1 = (hits >> 32) != 0;
-                        rows_hit |= (any0 ? 1ull << rr : 0ull) | (any1 ? 1ull << (rr + 4) : 0ull);
-                        if (lk ? any1 : any0) {  // (rows past M have threshold +inf: never stored)
-                            if (ok0) c0[rr * ldc] = v0;
-                            if (ok1) c0[rr * ldc + 32] = v1;
-                        }
-                    }
-                if (m0 + l64 < M && n0 < N) pflags[(m0 + l64) * ldf + n0 / 64] = (rows_hit >> l64) & 1ull;
-            } else if (m0 + 64 <= M && n0 + 64 <= N) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            c0[(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc + j * 32] =
-                                accm[i][j][r] + accc[i][j][r] * (1.f / 2048.f);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int rr = i * 32 + (r & 3) + 8 * (r >> 2);
-                            if (m0 + 4 * lk + rr < M && n0 + l31 + j * 32 < N)
-                                c0[rr * ldc + j * 32] = accm[i][j][r] + accc[i][j][r] * (1.f / 2048.f);
-                        }
-            }
-            zero();
+            wave_tile_epilogue<EPI>(wt.accm, wt.accc, m0, n0, c0, ldc, M, N, thr, pflags, ldf, cnt, l31, lk);
+            wt.zero();
             s = 0;
             tile += slots;
         }
@@ -751,9 +664,15 @@ __global__ __launch_bounds__(512) void k_gemm_split_w8(const char* __restrict__ 
     if (g < total) slice(g, r0, r1);
 }
 
-// (the switch that keeps the exact fp32 MFMA kernels is a descriptor flag, BESS_FLAG_FP32_MATH: the callers in
-// neg_shared.hip do not ask for this path then; the library reads no environment variables for dispatch)
-static bool split_disabled() { return false; }
+// the instantiations of the two kernels, [B_LO][EPI]
+using SplitKernel = void (*)(const char*, const char*, int64_t, int64_t, int, float*, int64_t, int, int, int, int64_t,
+                             const int32_t*, const float*, uint8_t*, int64_t, CountArgs);
+static const SplitKernel SPLIT_F16[2][3] = {
+    {k_gemm_split_f16<false, 0>, k_gemm_split_f16<false, 1>, k_gemm_split_f16<false, 2>},
+    {k_gemm_split_f16<true, 0>, k_gemm_split_f16<true, 1>, k_gemm_split_f16<true, 2>}};
+static const SplitKernel SPLIT_W8[2][3] = {
+    {k_gemm_split_w8<false, 0>, k_gemm_split_w8<false, 1>, k_gemm_split_w8<false, 2>},
+    {k_gemm_split_w8<true, 0>, k_gemm_split_w8<true, 1>, k_gemm_split_w8<true, 2>}};
 
 static int n_compute_units() {
     static const int n = [] {
@@ -784,85 +703,48 @@ static int launch_product(const char* A, const char* B, int64_t M, int64_t N, in
     const int64_t tx = ceil_div(N, 128);
     const int64_t t8 = tx * ceil_div(M, W8_A) * ksplit, t4 = tx * ceil_div(M, 128) * ksplit;
     BESS_REQUIRE(t4 < (1ll << 31), "gemm_split: too many tiles");
-    if (diag) {  // the diagonal 128 x 128 tiles only (M == N), C is [M, 128]
+    // one launch form: `tiles` tiles of kernel k[b_lo][epi], one persistent workgroup per CU at most
+    auto launch = [&](const SplitKernel (&k)[2][3], int64_t tiles, int lds_bytes, int64_t tiles_x, const char* what) {
+        const int grid = static_cast<int>(tiles < cus ? tiles : cus);
+        k[b_lo][epi]<<<grid, 512, lds_bytes, st>>>(A, B, M, N, n_slice, C, ldc, static_cast<int>(tiles_x),
+                                                   static_cast<int>(tiles), ksplit, part_stride, flag, thr, pflags, ldf, cnt);
+        return check_launch(what);
+    };
+    if (diag) {  // the diagonal 128 x 128 tiles only (M == N, tiles_x = 0), C is [M, 128]
         BESS_REQUIRE(M == N && ksplit == 1 && !thr && !count && ldc == 128, "gemm_split: bad diagonal product");
-        const int64_t td = ceil_div(M, 128);
-        const int grid = static_cast<int>(td < cus ? td : cus);
-        if (b_lo)
-            k_gemm_split_f16<true, 0><<<grid, 512, 0, st>>>(A, B, M, N, n_slice, C, ldc, 0, static_cast<int>(td), 1, 0, flag,
-                                                            nullptr, nullptr, 0, cnt);
-        else
-            k_gemm_split_f16<false, 0><<<grid, 512, 0, st>>>(A, B, M, N, n_slice, C, ldc, 0, static_cast<int>(td), 1, 0, flag,
-                                                             nullptr, nullptr, 0, cnt);
-        return check_launch("gemm_split_f16 (diagonal tiles)");
+        return launch(SPLIT_F16, ceil_div(M, 128), 0, 0, "gemm_split_f16 (diagonal tiles)");
     }
-    const bool wide = padded && t8 >= cus;
-    if (wide) {
+    if (padded && t8 >= cus) {
         static const bool attr = [] {
-            const int bytes = 2 * W8_IMG;
             bool ok = true;
-            for (const void* f : {reinterpret_cast<const void*>(&k_gemm_split_w8<true, 0>),
-                                  reinterpret_cast<const void*>(&k_gemm_split_w8<false, 0>),
-                                  reinterpret_cast<const void*>(&k_gemm_split_w8<true, 1>),
-                                  reinterpret_cast<const void*>(&k_gemm_split_w8<false, 1>),
-                                  reinterpret_cast<const void*>(&k_gemm_split_w8<true, 2>),
-                                  reinterpret_cast<const void*>(&k_gemm_split_w8<false, 2>)})
-                ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+            for (const auto& row : SPLIT_W8)
+                for (const SplitKernel f : row)
+                    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   2 * W8_IMG) == hipSuccess;
             return ok;
         }();
         BESS_REQUIRE(attr, "gemm_split: cannot reserve %d bytes of LDS", 2 * W8_IMG);
-        const int grid = static_cast<int>(t8 < cus ? t8 : cus);
-#define BESS_W8(LO, PR)                                                                                          \
-    k_gemm_split_w8<LO, PR><<<grid, 512, 2 * W8_IMG, st>>>(A, B, M, N, n_slice, C, ldc, static_cast<int>(tx),     \
-                                                           static_cast<int>(t8), ksplit, part_stride, flag, thr, \
-                                                           pflags, ldf, cnt)
-        if (epi == 2) {
-            if (b_lo) BESS_W8(true, 2);
-            else BESS_W8(false, 2);
-        } else if (epi == 1) {
-            if (b_lo) BESS_W8(true, 1);
-            else BESS_W8(false, 1);
-        } else {
-            if (b_lo) BESS_W8(true, 0);
-            else BESS_W8(false, 0);
-        }
-#undef BESS_W8
-        return check_launch("gemm_split_w8");
+        return launch(SPLIT_W8, t8, 2 * W8_IMG, tx, "gemm_split_w8");
     }
-    const int grid = static_cast<int>(t4 < cus ? t4 : cus);
-#define BESS_T4(LO, PR)                                                                                    \
-    k_gemm_split_f16<LO, PR><<<grid, 512, 0, st>>>(A, B, M, N, n_slice, C, ldc, static_cast<int>(tx),        \
-                                                   static_cast<int>(t4), ksplit, part_stride, flag, thr, pflags, ldf, \
-                                                   cnt)
-    if (epi == 2) {
-        if (b_lo) BESS_T4(true, 2);
-        else BESS_T4(false, 2);
-    } else if (epi == 1) {
-        if (b_lo) BESS_T4(true, 1);
-        else BESS_T4(false, 1);
-    } else {
-        if (b_lo) BESS_T4(true, 0);
-        else BESS_T4(false, 0);
-    }
-#undef BESS_T4
-    return check_launch("gemm_split_f16");
+    return launch(SPLIT_F16, t4, 0, tx, "gemm_split_f16");
 }
 
 static int64_t split_pitch(int W) { return ceil_div(W, SK) * ROW_B; }
 constexpr int64_t FLAG_BYTES = 256;  // tail of every workspace: the range flag (one int32, zeroed per call)
 constexpr int64_t SPLIT_CHUNK = 65536;  // candidate rows split per pass at most (128 MiB of lines at W = 512)
 
-// Workspace the split path wants for this shape; 0 = the shape is left to the fp32 kernels
-// (too few 128-tiles to occupy the chip, or the path is switched off).
-int64_t gemm_split_workspace(int64_t S, int64_t N, int W) {
-    if (split_disabled() || S < 1 || N < 1 || W < 1) return 0;
-    if (ceil_div(N, 128) * ceil_div(S, 128) < 256) return 0;
+// Workspace of a forward product: both images and the flag - for a caller that takes the split path whatever the
+// shape (pair scores in the arithmetic of a larger product)
+int64_t gemm_split_workspace_any(int64_t S, int64_t N, int W) {
     return (pad_a(S) + pad_b(N < SPLIT_CHUNK ? N : SPLIT_CHUNK)) * split_pitch(W) + FLAG_BYTES;
 }
 
-// the same for a caller that takes the split path whatever the shape (pair scores in the arithmetic of a larger product)
-int64_t gemm_split_workspace_any(int64_t S, int64_t N, int W) {
-    return (pad_a(S) + pad_b(N < SPLIT_CHUNK ? N : SPLIT_CHUNK)) * split_pitch(W) + FLAG_BYTES;
+// Workspace the split path wants for this shape; 0 = the shape is left to the fp32 kernels
+// (too few 128-tiles to occupy the chip).
+int64_t gemm_split_workspace(int64_t S, int64_t N, int W) {
+    if (S < 1 || N < 1 || W < 1) return 0;
+    if (ceil_div(N, 128) * ceil_div(S, 128) < 256) return 0;
+    return gemm_split_workspace_any(S, N, W);
 }
 
 // splits `a` (f32 rows; skipped when a.rows == 0) and `b` (table dtype) in one launch
@@ -960,7 +842,7 @@ struct BwdLayout {
     int64_t g_plain, g_trans, e_trans, q_trans, parts, total;
 };
 static bool bwd_layout(int64_t S, int64_t N, int W, BwdLayout& L) {
-    if (split_disabled() || S < 128 || N < 128 || W < 64 || W % 4) return false;
+    if (S < 128 || N < 128 || W < 64 || W % 4) return false;
     const int64_t tw = ceil_div(W, 128);
     L.pq = plan_k(ceil_div(S, 128) * tw, N);
     L.pe = plan_k(ceil_div(N, 128) * tw, S);

@@ -3,6 +3,7 @@
 //   hipcc -O3 -std=c++17 -fno-slp-vectorize --offload-arch=gfx950
 //         [-DBESS_PROBE_NO_MFMA] [-DBESS_PROBE_NO_LOAD] gemm_split_probe.hip -o probe && ./probe
 #include "../../bess-kge_amd/csrc/gemm_split.hip"
+#include "../../bess-kge_amd/csrc/gemm_mfma.hip"  // the fp32 kernels queued behind the split ones (never run here)
 
 #include <stdio.h>
 
@@ -47,7 +48,8 @@ int main() {
     char* eb = qa + S * n_slice * 128;
     hipEventRecord(a);
     for (int i = 0; i < reps; ++i)
-        bess::k_gemm_split_f16<true><<<256, 512>>>(qa, eb, S, N, n_slice, out, N, 32, 1024, 1, 0);
+        bess::k_gemm_split_f16<true, 0><<<256, 512>>>(qa, eb, S, N, n_slice, out, N, 32, 1024, 1, 0, nullptr, nullptr,
+                                                      nullptr, 0, bess::CountArgs{nullptr, nullptr, 0, 0});
     hipEventRecord(b);
     hipEventSynchronize(b);
     hipEventElapsedTime(&ms, a, b);
