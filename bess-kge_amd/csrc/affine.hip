@@ -1093,36 +1093,40 @@ static int aff_bwd_launch(const float* X, int64_t nx, const float* Y, int64_t ny
     return BESS_OK;
 }
 
+// the shared-candidate kernels' <NPART, P> class: f(np, p) as integral constants (P == 2 stands for any other p)
+template <typename F>
+static void with_parts_and_p(const bess_model_desc* d, F&& f) {
+    with_constant<1, 2>(d->reserved[0], [&](auto np) { with_constant<1, 2>(d->norm_p, [&](auto p) { f(np, p); }); });
+}
+
 int affine_shared_fwd(const bess_model_desc* d, const float* query, int64_t S, const float* cand, int64_t N, float* out,
                       int64_t ld, hipStream_t st) {
-    const int n_part = d->reserved[0];
-    const int dd = d->width / n_part;
+    const int dd = d->width / d->reserved[0];
     const float pf = static_cast<float>(d->norm_p);
     const dim3 grid(static_cast<unsigned>(ceil_div(N, 64)), static_cast<unsigned>(ceil_div(S, 64)));
     const AffCand<float> C{cand, nullptr, nullptr, 0};
     const CountArgs none{nullptr, nullptr, 0, 0};
-#define BESS_AFF_FWD(NP, PP) \
-    k_aff_shared_fwd<NP, PP, float, false, false, false><<<grid, 256, 0, st>>>(query, S, C, N, dd, out, ld, pf, nullptr, none, 1)
-    if (n_part == 1) {
-        if (d->norm_p == 1) BESS_AFF_FWD(1, 1);
-        else BESS_AFF_FWD(1, 2);
-    } else {
-        if (d->norm_p == 1) BESS_AFF_FWD(2, 1);
-        else BESS_AFF_FWD(2, 2);
-    }
-#undef BESS_AFF_FWD
+    with_parts_and_p(d, [&](auto np, auto p) {
+        k_aff_shared_fwd<decltype(np)::value, decltype(p)::value, float, false, false, false>
+            <<<grid, 256, 0, st>>>(query, S, C, N, dd, out, ld, pf, nullptr, none, 1);
+    });
     return check_launch("neg_score_shared_fwd (affine)");
+}
+
+// k_normalize_rows on n rows of a table of either type (out == NULL: the inverse norms only)
+static void normalize_rows_launch(int dtype, const void* base, const int32_t* idx, int64_t n, int dd, int n_part,
+                                  int normalize, float* out, float* inv, hipStream_t st) {
+    with_table_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        k_normalize_rows<T><<<static_cast<unsigned>(ceil_div(n, 4)), 256, 0, st>>>(static_cast<const T*>(base), idx, n, dd,
+                                                                                   n_part, normalize, out, inv);
+    });
 }
 
 // inverse part norms of n table rows (k_normalize_rows without its output): inv [n, n_part]
 int affine_inv_norms(const bess_model_desc* d, const void* base, const int32_t* idx, int64_t n, float* inv, hipStream_t st) {
     const int n_part = d->reserved[0];
-    const int dd = d->width / n_part;
-    const unsigned blocks = static_cast<unsigned>(ceil_div(n, 4));
-    if (d->dtype == BESS_F32)
-        k_normalize_rows<float><<<blocks, 256, 0, st>>>(static_cast<const float*>(base), idx, n, dd, n_part, 1, nullptr, inv);
-    else
-        k_normalize_rows<half_t><<<blocks, 256, 0, st>>>(static_cast<const half_t*>(base), idx, n, dd, n_part, 1, nullptr, inv);
+    normalize_rows_launch(d->dtype, base, idx, n, d->width / n_part, n_part, 1, nullptr, inv, st);
     return check_launch("inverse norms (affine)");
 }
 
@@ -1149,50 +1153,31 @@ static void aff_table_launch(const float* query, int64_t S, const AffCand<TC>& C
 int affine_table_fwd(const bess_model_desc* d, const float* query, int64_t S, const void* base, const int32_t* idx,
                      const float* inv, int64_t N, float* out, int64_t ld, const float* thr, const CountArgs* cnt,
                      hipStream_t st) {
-    const int n_part = d->reserved[0];
-    const int dd = d->width / n_part;
+    const int dd = d->width / d->reserved[0];
     const float pf = static_cast<float>(d->norm_p);
     BESS_REQUIRE(ceil_div(S, 64) < 65536, "affine scorers: more than 4 M queries in one call");
     const int vec = dd % 4 == 0 && reinterpret_cast<uintptr_t>(base) % 16 == 0;
-#define BESS_AFF_TAB(NP, PP)                                                                                     \
-    do {                                                                                                         \
-        if (d->dtype == BESS_F32)                                                                                \
-            aff_table_launch<NP, PP, float>(query, S, AffCand<float>{static_cast<const float*>(base), idx, inv, vec}, N, dd, \
-                                            out, ld, pf, thr, cnt, st);                                          \
-        else                                                                                                     \
-            aff_table_launch<NP, PP, half_t>(query, S, AffCand<half_t>{static_cast<const half_t*>(base), idx, inv, vec}, N, \
-                                             dd, out, ld, pf, thr, cnt, st);                                     \
-    } while (0)
-    if (n_part == 1) {
-        if (d->norm_p == 1) BESS_AFF_TAB(1, 1);
-        else BESS_AFF_TAB(1, 2);
-    } else {
-        if (d->norm_p == 1) BESS_AFF_TAB(2, 1);
-        else BESS_AFF_TAB(2, 2);
-    }
-#undef BESS_AFF_TAB
+    with_parts_and_p(d, [&](auto np, auto p) {
+        with_table_type(d->dtype, [&](auto t) {
+            using T = decltype(t);
+            aff_table_launch<decltype(np)::value, decltype(p)::value, T>(
+                query, S, AffCand<T>{static_cast<const T*>(base), idx, inv, vec}, N, dd, out, ld, pf, thr, cnt, st);
+        });
+    });
     return check_launch(cnt ? "neg_score_table_fwd_counts (affine)" : "neg_score_table_fwd_pairs (affine)");
 }
 
 int affine_shared_bwd(const bess_model_desc* d, const float* query, int64_t S, const float* cand, int64_t N,
                       const float* out, int64_t ld_out, const float* d_out, int64_t ld_dout, float* d_query,
                       float* d_cand, hipStream_t st) {
-    const int n_part = d->reserved[0];
-    const int dd = d->width / n_part;
+    const int dd = d->width / d->reserved[0];
     const float pf = static_cast<float>(d->norm_p);
     int rc;
-#define BESS_AFFB(NP, PP)                                                                                          \
-    do {                                                                                                           \
-        rc = aff_bwd_launch<NP, PP, true>(query, S, cand, N, dd, d_out, ld_dout, 1, out, ld_out, 1, d_query, st, pf);  \
-        if (!rc) rc = aff_bwd_launch<NP, PP, false>(cand, N, query, S, dd, d_out, 1, ld_dout, out, 1, ld_out,      \
-                                                    d_cand, st, pf);                                               \
-    } while (0)
-    if (n_part == 1) {
-        if (d->norm_p == 1) BESS_AFFB(1, 1); else BESS_AFFB(1, 2);
-    } else {
-        if (d->norm_p == 1) BESS_AFFB(2, 1); else BESS_AFFB(2, 2);
-    }
-#undef BESS_AFFB
+    with_parts_and_p(d, [&](auto np, auto p) {
+        constexpr int NPART = decltype(np)::value, P = decltype(p)::value;
+        rc = aff_bwd_launch<NPART, P, true>(query, S, cand, N, dd, d_out, ld_dout, 1, out, ld_out, 1, d_query, st, pf);
+        if (!rc) rc = aff_bwd_launch<NPART, P, false>(cand, N, query, S, dd, d_out, 1, ld_dout, out, 1, ld_out, d_cand, st, pf);
+    });
     if (rc) return rc;
     return check_launch("neg_score_shared_bwd (affine)");
 }
@@ -1207,13 +1192,7 @@ extern "C" int bess_normalize_rows(int32_t dtype, const void* base, const int32_
     BESS_REQUIRE(n_rows >= 0 && width > 0 && n_part > 0 && width % n_part == 0, "normalize_rows: bad shape");
     if (n_rows == 0) return BESS_OK;
     BESS_REQUIRE(base && out, "normalize_rows: NULL pointer");
-    const unsigned blocks = static_cast<unsigned>(ceil_div(n_rows, 4));
-    if (dtype == BESS_F32)
-        k_normalize_rows<float><<<blocks, 256, 0, as_stream(stream)>>>(static_cast<const float*>(base), idx, n_rows,
-                                                                       width / n_part, n_part, normalize, out, inv_norm);
-    else
-        k_normalize_rows<half_t><<<blocks, 256, 0, as_stream(stream)>>>(static_cast<const half_t*>(base), idx, n_rows,
-                                                                        width / n_part, n_part, normalize, out, inv_norm);
+    normalize_rows_launch(dtype, base, idx, n_rows, width / n_part, n_part, normalize, out, inv_norm, as_stream(stream));
     return check_launch("normalize_rows");
 }
 

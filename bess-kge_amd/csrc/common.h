@@ -348,6 +348,25 @@ void with_constant(int v, F&& f) {
     else if (v == V0) f(std::integral_constant<int, V0>{});
     else with_constant<VS...>(v, f);
 }
+// The same for a flag, for the table type and for the per-triple kernels' eight <T, SCORER> classes (prepare.hip):
+// f(std::bool_constant<B>{}); f(T{}) with T = float or half_t; f(T{}, std::integral_constant<int, SCORER>{}) for the
+// four native scorers - no call for any other scorer.
+template <typename F>
+void with_flag(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <typename F>
+auto with_table_type(int dtype, F&& f) {
+    return dtype == BESS_F32 ? f(float{}) : f(half_t{});
+}
+template <typename F>
+void dispatch_scorer_class(const bess_model_desc* d, F&& f) {
+    if (d->scorer > BESS_COMPLEX) return;  // (check_desc came first: 0 .. BESS_BOXE)
+    with_table_type(d->dtype, [&](auto t) {
+        with_constant<BESS_TRANSE, BESS_ROTATE, BESS_DISTMULT, BESS_COMPLEX>(d->scorer, [&](auto sc) { f(t, sc); });
+    });
+}
 
 // scalars per lane load: the widest vector that divides the row (native family: f32 {4, 1}, f16 {8, 2, 1}) ...
 inline int vec_of(const bess_model_desc* d) {

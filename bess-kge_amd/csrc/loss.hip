@@ -142,29 +142,14 @@ __global__ __launch_bounds__(1024) void k_sum_rows(const float* __restrict__ row
     if (threadIdx.x == 0) loss[0] = part[0];
 }
 
-template <int KIND, bool ADV, int CH>
-static void launch_loss_ch(bool grad, const bess_loss_desc& l, const float* pos, const float* neg,
-                           int64_t S, int64_t N, int64_t ld, const float* w, int64_t wl, float* rl,
-                           float* dp, float* dn, int64_t ldd, float* rn, int32_t* cnt, float* loss, hipStream_t st) {
-    const unsigned grid = static_cast<unsigned>(ceil_div(S, 4));
-    if (grad) k_loss_rows<KIND, ADV, true, CH><<<grid, 256, 0, st>>>(l, pos, neg, S, N, ld, w, wl, rl, dp, dn, ldd, rn, cnt, loss);
-    else k_loss_rows<KIND, ADV, false, CH><<<grid, 256, 0, st>>>(l, pos, neg, S, N, ld, w, wl, rl, dp, dn, ldd, rn, cnt, loss);
-}
-
-template <int KIND, bool ADV>
-static void launch_loss(bool grad, const bess_loss_desc& l, const float* pos, const float* neg,
-                        int64_t S, int64_t N, int64_t ld, const float* w, int64_t wl, float* rl,
-                        float* dp, float* dn, int64_t ldd, float* rn, int32_t* cnt, float* loss, hipStream_t st) {
-    // rows in registers when their shape allows 16-byte accesses (see k_loss_rows)
+// CH of k_loss_rows (loss_rows.h): rows in registers when their shape allows 16-byte accesses - 4, 12 or 24 chunks
+// for rows of up to 256 * CH scores, -1 for longer ones; 0: any shape, 4 bytes per lane
+static int loss_chunks(bool grad, const float* neg, int64_t N, int64_t ld, const float* dn, int64_t ldd) {
     const bool vec = N % 4 == 0 && ld % 4 == 0 && reinterpret_cast<uintptr_t>(neg) % 16 == 0 &&
                      (!grad || (ldd % 4 == 0 && reinterpret_cast<uintptr_t>(dn) % 16 == 0));
-#define BESS_LOSS_CH(CH) launch_loss_ch<KIND, ADV, CH>(grad, l, pos, neg, S, N, ld, w, wl, rl, dp, dn, ldd, rn, cnt, loss, st)
-    if (!vec) BESS_LOSS_CH(0);
-    else if (N > 256 * 24) BESS_LOSS_CH(-1);
-    else if (N <= 256 * 4) BESS_LOSS_CH(4);
-    else if (N <= 256 * 12) BESS_LOSS_CH(12);
-    else BESS_LOSS_CH(24);
-#undef BESS_LOSS_CH
+    if (!vec) return 0;
+    if (N > 256 * 24) return -1;
+    return N <= 256 * 4 ? 4 : N <= 256 * 12 ? 12 : 24;
 }
 
 }  // namespace bess
@@ -220,15 +205,20 @@ static int loss_impl(const bess_loss_desc* l, const float* pos, const float* neg
     // the one-launch form costs one atomic per workgroup (4 rows each), taken in two levels (last_workgroup_ticket:
     // same-address atomics serialise at ~40 ns a piece).  Very large grids keep the second launch.
     if (n_triple > 4 * 4096) counter = nullptr;
-#define BESS_LOSS(KIND, ADV) \
-    launch_loss<KIND, ADV>(grad, *l, pos, neg, n_triple, n_neg, ld_neg, weight, weight_len, row_loss, d_pos, d_neg, ld_dneg, \
-                           row_norm, counter, loss, st)
-    switch (l->kind) {
-        case BESS_LOSS_LOGSIGMOID: adv ? BESS_LOSS(BESS_LOSS_LOGSIGMOID, true) : BESS_LOSS(BESS_LOSS_LOGSIGMOID, false); break;
-        case BESS_LOSS_MARGIN: adv ? BESS_LOSS(BESS_LOSS_MARGIN, true) : BESS_LOSS(BESS_LOSS_MARGIN, false); break;
-        default: BESS_LOSS(BESS_LOSS_SSCE, false);
-    }
-#undef BESS_LOSS
+    const unsigned grid = static_cast<unsigned>(ceil_div(n_triple, 4));
+    auto launch = [&](auto kind, auto adv_c) {  // (SSCE has no adversarial form)
+        with_constant<0, -1, 4, 12, 24>(loss_chunks(grad, neg, n_neg, ld_neg, d_neg, ld_dneg), [&](auto ch) {
+            with_flag(grad, [&](auto g) {
+                k_loss_rows<decltype(kind)::value, decltype(adv_c)::value, decltype(g)::value, decltype(ch)::value>
+                    <<<grid, 256, 0, st>>>(*l, pos, neg, n_triple, n_neg, ld_neg, weight, weight_len, row_loss, d_pos, d_neg,
+                                           ld_dneg, row_norm, counter, loss);
+            });
+        });
+    };
+    with_constant<BESS_LOSS_LOGSIGMOID, BESS_LOSS_MARGIN, BESS_LOSS_SSCE>(l->kind, [&](auto kind) {
+        if constexpr (decltype(kind)::value == BESS_LOSS_SSCE) launch(kind, std::false_type{});
+        else with_flag(adv, [&](auto a) { launch(kind, a); });
+    });
     if (int e = check_launch("loss rows")) return e;
     if (counter) return BESS_OK;  // summed by the launch's last workgroup
     k_sum_rows<<<1, 1024, 0, st>>>(row_loss, n_triple, loss);

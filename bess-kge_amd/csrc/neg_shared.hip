@@ -11,8 +11,9 @@
 // 64 x 64 output tile per 256-thread workgroup, 4 x 4 register micro-tile per
 // lane, 16-deep K stages; negative rows are gathered by index straight into the
 // LDS tile (never materialised in HBM).  The p-norm forms have no matrix-core
-// formulation (|a - b| is not bilinear) and run on the VALU; the dot form uses
-// the same tiling here and is the candidate for the f32 MFMA path.
+// formulation (|a - b| is not bilinear) and run on the VALU: these kernels.  The
+// dot form of DistMult / ComplEx runs on the matrix cores (gemm_split.hip,
+// gemm_mfma.hip); the entry points below send it there.
 //
 // Backward reuses one tiled kernel:
 //   dX[a, w] = sum_b coef[a, b] * f'(X[a, w], Y[b, w])
@@ -64,7 +65,6 @@ __device__ __forceinline__ void load_stage(const RowSrc<T>& src, int64_t m0, int
 }
 
 // 16 stage values of one thread: 4 scalars of row m at columns kc..kc+3
-template <typename T>
 __device__ __forceinline__ void stage_store(float (*tile)[LDP], int kc, int m, const float (&v)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) tile[kc + i][m] = v[i];
@@ -110,9 +110,7 @@ __global__ __launch_bounds__(256) void k_neg_shared_fwd(RowSrc<float> Q, RowSrc<
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (RED == RED_DOT) {
-                        acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
-                    } else if (RED == RED_L1) {
+                    if (RED == RED_L1) {
                         acc[i][j] += fabsf(a[i] - b[j]);
                     } else {
                         acc[i][j] += lp_term(a[i] - b[j], p);
@@ -129,8 +127,8 @@ __global__ __launch_bounds__(256) void k_neg_shared_fwd(RowSrc<float> Q, RowSrc<
         VecLoad<float, 4>::load(qp, qv);
         VecLoad<T, 4>::load(ep, ev);
         for (int k0 = 0; k0 < W; k0 += KT) {
-            stage_store<float>(Qs, kc, m, qv);
-            stage_store<float>(Es, kc, m, ev);
+            stage_store(Qs, kc, m, qv);
+            stage_store(Es, kc, m, ev);
             __syncthreads();
             if (k0 + KT < W) {
                 VecLoad<float, 4>::load(qp + k0 + KT, qv);
@@ -173,7 +171,6 @@ __global__ __launch_bounds__(256) void k_neg_shared_fwd(RowSrc<float> Q, RowSrc<
 }
 
 // dX[a, w] = sum_b coef(a, b) * f'(X[a, w], Y[b, w]);  coef from d_out (and out for p=2)
-//   DOT: coef = g            f' = y
 //   L1 : coef = sign*g       f' = sgn(x - y)
 //   L2 : coef = g / out      f' = x - y        (out = -dist; 0 where dist == 0)
 // g = d_out[a*sa + b*sb], out likewise with (oa, ob) strides.
@@ -317,8 +314,7 @@ __device__ __forceinline__ void neg_shared_bwd_tile(const BwdSide<TX, TY>& S, in
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if (RED == RED_DOT) acc[i][j] = fmaf(c[i], y[j], acc[i][j]);
-                    else if (RED == RED_L1) acc[i][j] = fmaf(c[i], sgn_prescaled(xv[i][j] - y[j]), acc[i][j]);
+                    if (RED == RED_L1) acc[i][j] = fmaf(c[i], sgn_prescaled(xv[i][j] - y[j]), acc[i][j]);
                     else acc[i][j] = fmaf(c[i], lp_dterm(xv[i][j] - y[j], p), acc[i][j]);
                 }
         }
@@ -616,7 +612,7 @@ struct L1BothPlan {
     int nw;
     int64_t i_chunk, slices, jt, wt;
 };
-static L1BothPlan plan_l1_bwd_both(int64_t S, int64_t N, int W, bool /*unused*/) {
+static L1BothPlan plan_l1_bwd_both(int64_t S, int64_t N, int W) {
     L1BothPlan p;
     // eight waves (256 candidates) per workgroup; four where the candidates are few (finer tiles: 544 candidates
     // are 4.25 tiles of 128 but 2.1 of 256).  Measured (profiles/sweep_l1_bwd.py, us, 4 / 8 waves): 512 x 544
@@ -673,6 +669,9 @@ static L1PartsPlan plan_l1_bwd_parts(int64_t S, int64_t N, int W) {
     return p;
 }
 
+// score = -distance for the distance scorers: the factor the kernels apply to their sums
+static float score_sign(const bess_model_desc* d) { return is_distance(d->scorer) ? -1.f : 1.f; }
+
 template <typename TE>
 static int run_l1_bwd_parts(const bess_model_desc* d, RowSrc<float> Q, RowSrc<TE> E, const float* d_out,
                             int64_t ld_dout, float* dq_parts, float* de_parts, hipStream_t st, bool round16) {
@@ -681,15 +680,11 @@ static int run_l1_bwd_parts(const bess_model_desc* d, RowSrc<float> Q, RowSrc<TE
     const int64_t tasks = p.groups * p.slices;
     BESS_REQUIRE(tasks < (1ll << 31) && ceil_div(W, FB_TW) < 65536, "neg_score_shared_bwd_parts: problem too large");
     const dim3 grid(static_cast<unsigned>(ceil_div(tasks, 4)), static_cast<unsigned>(ceil_div(W, FB_TW)));
-    const float sign = is_distance(d->scorer) ? -1.f : 1.f;
-    if (round16)
-        k_l1_bwd_parts<TE, true><<<grid, 256, 0, st>>>(Q, E, W, sign, d_out, ld_dout, dq_parts, de_parts,
-                                                       static_cast<int>(p.i_chunk), static_cast<int>(p.groups),
-                                                       static_cast<int>(tasks));
-    else
-        k_l1_bwd_parts<TE, false><<<grid, 256, 0, st>>>(Q, E, W, sign, d_out, ld_dout, dq_parts, de_parts,
-                                                        static_cast<int>(p.i_chunk), static_cast<int>(p.groups),
-                                                        static_cast<int>(tasks));
+    with_flag(round16, [&](auto r16) {
+        k_l1_bwd_parts<TE, decltype(r16)::value><<<grid, 256, 0, st>>>(
+            Q, E, W, score_sign(d), d_out, ld_dout, dq_parts, de_parts, static_cast<int>(p.i_chunk),
+            static_cast<int>(p.groups), static_cast<int>(tasks));
+    });
     return check_launch("neg_score_shared_bwd_parts");
 }
 
@@ -697,23 +692,17 @@ template <typename TE>
 static int run_l1_bwd_both(const bess_model_desc* d, RowSrc<float> Q, RowSrc<TE> E, const float* d_out,
                            int64_t ld_dout, float* d_query, float* d_neg, hipStream_t st, bool round16) {
     const int W = d->width;
-    const L1BothPlan p = plan_l1_bwd_both(Q.n, E.n, W, false);
-    const int nw = p.nw;
-    const int64_t jt = p.jt, wt = p.wt, slices = p.slices;
-    BESS_REQUIRE(jt < (1ll << 31) && wt < 65536 && slices < 65536, "neg_score_shared_bwd: problem too large for one launch");
-    const dim3 grid(static_cast<unsigned>(jt), static_cast<unsigned>(wt), static_cast<unsigned>(slices));
-    const float sign = is_distance(d->scorer) ? -1.f : 1.f;
-    const int ic = static_cast<int>(p.i_chunk);
-#define BESS_FB(R16, NW) \
-    k_l1_bwd_both<TE, R16, NW><<<grid, 64 * NW, 0, st>>>(Q, E, W, sign, d_out, ld_dout, d_query, d_neg, ic)
-    if (nw == 8) {
-        if (round16) BESS_FB(true, 8);
-        else BESS_FB(false, 8);
-    } else {
-        if (round16) BESS_FB(true, 4);
-        else BESS_FB(false, 4);
-    }
-#undef BESS_FB
+    const L1BothPlan p = plan_l1_bwd_both(Q.n, E.n, W);
+    BESS_REQUIRE(p.jt < (1ll << 31) && p.wt < 65536 && p.slices < 65536,
+                 "neg_score_shared_bwd: problem too large for one launch");
+    const dim3 grid(static_cast<unsigned>(p.jt), static_cast<unsigned>(p.wt), static_cast<unsigned>(p.slices));
+    with_constant<8, 4>(p.nw, [&](auto nw) {
+        with_flag(round16, [&](auto r16) {
+            constexpr int NW = decltype(nw)::value;
+            k_l1_bwd_both<TE, decltype(r16)::value, NW><<<grid, 64 * NW, 0, st>>>(
+                Q, E, W, score_sign(d), d_out, ld_dout, d_query, d_neg, static_cast<int>(p.i_chunk));
+        });
+    });
     return check_launch("neg_score_shared_bwd (p = 1, both products)");
 }
 
@@ -723,23 +712,15 @@ static int run_fwd(const bess_model_desc* d, RowSrc<float> Q, RowSrc<T> E, float
     // 32-row tiles when the 64-row grid would leave most CUs without a workgroup
     const bool small = ceil_div(E.n, TN) * ceil_div(Q.n, TM) < 192;
     const dim3 grid(static_cast<unsigned>(ceil_div(E.n, TN)), static_cast<unsigned>(ceil_div(Q.n, small ? TM / 2 : TM)));
-    const float sign = is_distance(d->scorer) ? -1.f : 1.f;
-    const bool aligned = d->width % KT == 0;
-#define BESS_FWD_ARGS <<<grid, 256, 0, st>>>(Q, E, d->width, sign, out, ld, static_cast<float>(d->norm_p))
-#define BESS_FWD(RED)                                                         \
-    do {                                                                      \
-        if (aligned && small) k_neg_shared_fwd<T, RED, true, 2> BESS_FWD_ARGS;  \
-        else if (aligned) k_neg_shared_fwd<T, RED, true, 4> BESS_FWD_ARGS;      \
-        else if (small) k_neg_shared_fwd<T, RED, false, 2> BESS_FWD_ARGS;       \
-        else k_neg_shared_fwd<T, RED, false, 4> BESS_FWD_ARGS;                  \
-    } while (0)
-    switch (reduce_of(d)) {
-        case RED_DOT: BESS_FWD(RED_DOT); break;
-        case RED_L1: BESS_FWD(RED_L1); break;
-        default: BESS_FWD(RED_L2);
-    }
-#undef BESS_FWD
-#undef BESS_FWD_ARGS
+    // (RED_L1 or RED_L2: the entry point sends the bilinear scorers to the matrix cores)
+    with_constant<RED_L1, RED_L2>(reduce_of(d), [&](auto red) {
+        with_flag(d->width % KT == 0, [&](auto aligned) {
+            with_constant<2, 4>(small ? 2 : 4, [&](auto mi) {
+                k_neg_shared_fwd<T, decltype(red)::value, decltype(aligned)::value, decltype(mi)::value>
+                    <<<grid, 256, 0, st>>>(Q, E, d->width, score_sign(d), out, ld, static_cast<float>(d->norm_p));
+            });
+        });
+    });
     return check_launch("neg_score_shared_fwd");
 }
 
@@ -773,20 +754,28 @@ static bool plan_bwd_side(int W, BwdSide<TX, TY>& S) {
     return small;
 }
 
+// Gradient targets that receive sums of fp32 atomics start from zero: d_query (zq) and d_neg (zn), with one fill
+// when both are wanted and share an allocation (d_neg right behind d_query).  Nothing to do when the caller cleared
+// both (BESS_FLAG_PREZEROED: one launch for all fills of a step, bess_step_prologue).  `what`: the error text's prefix
+static int zero_gradients(const bess_model_desc* d, float* d_query, int64_t nq, bool zq, float* d_neg, int64_t nn, bool zn,
+                          const char* what, hipStream_t st) {
+    if (d->reserved[0] & BESS_FLAG_PREZEROED) return BESS_OK;
+    hipError_t e = hipSuccess;
+    if (zq && zn && d_neg == d_query + nq) {
+        e = fill_words_async(d_query, 0u, nq + nn, st);
+    } else {
+        if (zq) e = fill_words_async(d_query, 0u, nq, st);
+        if (zn && e == hipSuccess) e = fill_words_async(d_neg, 0u, nn, st);
+    }
+    return e == hipSuccess ? BESS_OK : fail(static_cast<int>(e), "%s: %s", what, hipGetErrorString(e));
+}
+
 template <typename TE>
 static int run_bwd(const bess_model_desc* d, RowSrc<float> Q, RowSrc<TE> E, const float* d_out, int64_t ld_dout,
                    const float* out, int64_t ld_out, float* d_query, float* d_neg, hipStream_t st, bool round16) {
     const int W = d->width;
     if (use_l1_bwd_both(d, Q.n, E.n) && Q.idx == nullptr) {  // (the kernel reads the dense f32 query matrix)
-        if (!(d->reserved[0] & BESS_FLAG_PREZEROED)) {  // its outputs are sums of atomics
-            hipError_t e = hipSuccess;
-            if (d_neg == d_query + Q.n * W) e = fill_words_async(d_query, 0u, (Q.n + E.n) * W, st);
-            else {
-                e = fill_words_async(d_query, 0u, Q.n * W, st);
-                if (e == hipSuccess) e = fill_words_async(d_neg, 0u, E.n * W, st);
-            }
-            if (e != hipSuccess) return fail(static_cast<int>(e), "fill: %s", hipGetErrorString(e));
-        }
+        if (int e = zero_gradients(d, d_query, Q.n * W, true, d_neg, E.n * W, true, "fill", st)) return e;
         return run_l1_bwd_both<TE>(d, Q, E, d_out, ld_dout, d_query, d_neg, st, round16);
     }
     BwdSide<float, TE> A{Q, E, ld_dout, 1, ld_out, 1, d_query, 0, 0, 0, 0};
@@ -794,42 +783,27 @@ static int run_bwd(const bess_model_desc* d, RowSrc<float> Q, RowSrc<TE> E, cons
     const bool small_a = plan_bwd_side(W, A), small_b = plan_bwd_side(W, B);
     const int64_t blocks_a = static_cast<int64_t>(A.gx) * A.gy * A.gz, blocks_b = static_cast<int64_t>(B.gx) * B.gy * B.gz;
     BESS_REQUIRE(blocks_a + blocks_b < (1ll << 31), "neg_score_shared_bwd: problem too large for one launch");
-    // partial sums of several slices are combined with fp32 atomics: zero their targets - with one memset
-    // when both gradients share an allocation (d_neg right behind d_query)
-    auto zero = [&](float* p, int64_t n) -> int {
-        hipError_t e = fill_words_async(p, 0u, n, st);
-        return e == hipSuccess ? BESS_OK : fail(static_cast<int>(e), "memset: %s", hipGetErrorString(e));
-    };
-    if (d->reserved[0] & BESS_FLAG_PREZEROED) {
-        // the caller cleared both targets (one launch for all fills of a step: bess_step_prologue)
-    } else if (A.gz > 1 && B.gz > 1 && d_neg == d_query + Q.n * W) {
-        if (int e = zero(d_query, (Q.n + E.n) * W)) return e;
-    } else {
-        if (A.gz > 1)
-            if (int e = zero(d_query, Q.n * W)) return e;
-        if (B.gz > 1)
-            if (int e = zero(d_neg, E.n * W)) return e;
-    }
+    // partial sums of several slices are combined with fp32 atomics
+    if (int e = zero_gradients(d, d_query, Q.n * W, A.gz > 1, d_neg, E.n * W, B.gz > 1, "memset", st)) return e;
     const unsigned grid = static_cast<unsigned>(blocks_a + blocks_b);
-    const int ba = static_cast<int>(blocks_a);
-    const float sign = is_distance(d->scorer) ? -1.f : 1.f;
+    auto launch = [&](auto red, auto vec4, auto r16) {
+        with_constant<2, 4>(small_a ? 2 : 4, [&](auto mia) {
+            with_constant<2, 4>(small_b ? 2 : 4, [&](auto mib) {
+                k_neg_shared_bwd<TE, decltype(red)::value, decltype(vec4)::value, decltype(r16)::value, decltype(mia)::value,
+                                 decltype(mib)::value><<<grid, 256, 0, st>>>(
+                    A, B, W, score_sign(d), d_out, out, static_cast<int>(blocks_a), static_cast<float>(d->norm_p));
+            });
+        });
+    };
+    // RED_L1 or RED_L2: the bilinear scorers' products run on the matrix cores.  ROUND16 exists for the shapes of the
+    // packed-fp16 forward only (p = 1, W % 4 == 0)
+    const int red = reduce_of(d);
     const bool vec4 = W % 4 == 0;
-#define BESS_BWD_ARGS <<<grid, 256, 0, st>>>(A, B, W, sign, d_out, out, ba, static_cast<float>(d->norm_p))
-#define BESS_BWD_MI(RED, V, R16)                                                   \
-    do {                                                                           \
-        if (small_a && small_b) k_neg_shared_bwd<TE, RED, V, R16, 2, 2> BESS_BWD_ARGS; \
-        else if (small_a) k_neg_shared_bwd<TE, RED, V, R16, 2, 4> BESS_BWD_ARGS;       \
-        else if (small_b) k_neg_shared_bwd<TE, RED, V, R16, 4, 2> BESS_BWD_ARGS;       \
-        else k_neg_shared_bwd<TE, RED, V, R16, 4, 4> BESS_BWD_ARGS;                    \
-    } while (0)
-    const int red = reduce_of(d);  // RED_L1 or RED_L2: the bilinear scorers' products run on the matrix cores
-    if (red == RED_L1 && vec4 && round16) BESS_BWD_MI(RED_L1, true, true);
-    else if (red == RED_L1 && vec4) BESS_BWD_MI(RED_L1, true, false);
-    else if (red == RED_L1) BESS_BWD_MI(RED_L1, false, false);
-    else if (vec4) BESS_BWD_MI(RED_L2, true, false);
-    else BESS_BWD_MI(RED_L2, false, false);
-#undef BESS_BWD_MI
-#undef BESS_BWD_ARGS
+    if (red == RED_L1 && vec4 && round16) {
+        launch(std::integral_constant<int, RED_L1>{}, std::true_type{}, std::true_type{});
+    } else {
+        with_constant<RED_L1, RED_L2>(red, [&](auto r) { with_flag(vec4, [&](auto v) { launch(r, v, std::false_type{}); }); });
+    }
     return BESS_OK;
 }
 
@@ -853,6 +827,37 @@ static int64_t affine_chunk_rows(const bess_model_desc* d) {
     const int64_t row_bytes = static_cast<int64_t>(d->width) * (d->dtype == BESS_F32 ? 4 : 2);
     const int64_t rows = BESS_AFFINE_COUNT_CHUNK_BYTES / row_bytes / 64 * 64;
     return rows < 64 ? 64 : rows;
+}
+
+// the candidates as an operand of the tile kernels: f(RowSrc<T>{...}) with T the table's type
+template <typename F>
+static int with_candidates(const bess_model_desc* d, const void* base, const int32_t* idx, int64_t n, F&& f) {
+    return with_table_type(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        return f(RowSrc<T>{static_cast<const T*>(base), idx, n});
+    });
+}
+
+// The split-fp16 product takes the call when the caller brought the workspace the shape wants (`wants`:
+// gemm_split_workspace or gemm_split_bwd_workspace; 0 = not a shape for it) and did not ask for the exact fp32 kernels
+static bool split_fits(const bess_model_desc* d, int64_t (*wants)(int64_t, int64_t, int), int64_t S, int64_t N,
+                       const void* workspace, int64_t workspace_bytes) {
+    if (!workspace || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return false;
+    const int64_t want = wants(S, N, d->width);
+    return want > 0 && workspace_bytes >= want;
+}
+
+// f(j0, nc, base, idx) for every chunk of at most `chunk` of the n candidates, until one returns an error: indexed
+// candidates advance the index list, dense ones the base (row_bytes a row)
+template <typename F>
+static int for_each_candidate_chunk(const void* base, const int32_t* idx, int64_t n, int64_t chunk, int64_t row_bytes,
+                                    F&& f) {
+    for (int64_t j0 = 0; j0 < n; j0 += chunk) {
+        const int64_t nc = n - j0 < chunk ? n - j0 : chunk;
+        const void* b = idx ? base : static_cast<const char*>(base) + j0 * row_bytes;
+        if (int e = f(j0, nc, b, idx ? idx + j0 : nullptr)) return e;
+    }
+    return BESS_OK;
 }
 
 }  // namespace bess
@@ -931,9 +936,7 @@ extern "C" int bess_neg_score_shared_fwd_ws(const bess_model_desc* d, const floa
                                  as_stream(stream));
     }
     if (reduce_of(d) == RED_DOT) {  // bilinear scorers: matrix cores
-        const bool fp32 = d->reserved[0] & BESS_FLAG_FP32_MATH;
-        const int64_t want = workspace && !fp32 ? gemm_split_workspace(n_query, n_neg, d->width) : 0;
-        if (want > 0 && workspace_bytes >= want)
+        if (split_fits(d, gemm_split_workspace, n_query, n_neg, workspace, workspace_bytes))
             return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, out, ld_out,
                                   workspace, workspace_bytes, as_stream(stream));
         return gemm_dot_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, out, ld_out,
@@ -941,12 +944,9 @@ extern "C" int bess_neg_score_shared_fwd_ws(const bess_model_desc* d, const floa
     }
     if (use_l1_pk(d, query, neg_base))
         return l1_pk_fwd(d, query, n_query, neg_base, neg_idx, n_neg, out, ld_out, nullptr, as_stream(stream));
-    RowSrc<float> Q{query, nullptr, n_query};
-    if (d->dtype == BESS_F32)
-        return run_fwd<float>(d, Q, RowSrc<float>{static_cast<const float*>(neg_base), neg_idx, n_neg}, out,
-                              ld_out, as_stream(stream));
-    return run_fwd<half_t>(d, Q, RowSrc<half_t>{static_cast<const half_t*>(neg_base), neg_idx, n_neg}, out,
-                           ld_out, as_stream(stream));
+    return with_candidates(d, neg_base, neg_idx, n_neg, [&](auto E) {
+        return run_fwd(d, RowSrc<float>{query, nullptr, n_query}, E, out, ld_out, as_stream(stream));
+    });
 }
 
 extern "C" int bess_neg_score_shared_fwd_pruned(const bess_model_desc* d, const float* query, int64_t n_query,
@@ -970,9 +970,7 @@ extern "C" int bess_neg_score_shared_fwd_pruned(const bess_model_desc* d, const 
     }
     if (d->scorer <= BESS_COMPLEX) {
         if (reduce_of(d) == RED_DOT) {
-            const bool fp32 = d->reserved[0] & BESS_FLAG_FP32_MATH;
-            const int64_t want = workspace && !fp32 ? gemm_split_workspace(n_query, n_neg, d->width) : 0;
-            if (want > 0 && workspace_bytes >= want)
+            if (split_fits(d, gemm_split_workspace, n_query, n_neg, workspace, workspace_bytes))
                 return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, out, ld_out,
                                       workspace, workspace_bytes, st, thr, flags, ld_flags);
         } else if (use_l1_pk(d, query, neg_base)) {
@@ -1068,15 +1066,11 @@ extern "C" int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const 
             // Infinity Cache while its query tiles pass over them - over all 2.5 M rows of a wikikg2 shard in one
             // launch every row tile would stream the table from HBM again
             constexpr int64_t L1_COUNT_CHUNK = 65536;
-            for (int64_t j0 = 0; j0 < n_neg; j0 += L1_COUNT_CHUNK) {
-                const int64_t nc = n_neg - j0 < L1_COUNT_CHUNK ? n_neg - j0 : L1_COUNT_CHUNK;
+            return for_each_candidate_chunk(neg_base, neg_idx, n_neg, L1_COUNT_CHUNK, row_bytes_of(d),
+                                            [&](int64_t j0, int64_t nc, const void* base, const int32_t* idx) {
                 const CountArgs cj{excl, counts, j0, cnt.round16};
-                const void* base = neg_idx ? neg_base : static_cast<const char*>(neg_base) + j0 * d->width * 2;
-                if (int e = l1_pk_fwd(d, query, n_query, base, neg_idx ? neg_idx + j0 : nullptr, nc, nullptr, 0, nullptr,
-                                      st, thr, nullptr, 0, &cj))
-                    return e;
-            }
-            return BESS_OK;
+                return l1_pk_fwd(d, query, n_query, base, idx, nc, nullptr, 0, nullptr, st, thr, nullptr, 0, &cj);
+            });
         }
     }
     // no counting epilogue for this scorer / shape: score tiles through the workspace, counted by a second kernel
@@ -1087,17 +1081,13 @@ extern "C" int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const 
                  "neg_score_shared_fwd_counts: workspace too small (bess_neg_score_shared_fwd_counts_workspace) or misaligned");
     float* tile = static_cast<float*>(workspace);
     const int64_t row_bytes = static_cast<int64_t>(d->width) * ((d->scorer == BESS_AFFINE || d->dtype == BESS_F32) ? 4 : 2);
-    for (int64_t j0 = 0; j0 < n_neg; j0 += cols) {
-        const int64_t nc = n_neg - j0 < cols ? n_neg - j0 : cols;
-        const void* base = neg_idx ? neg_base : static_cast<const char*>(neg_base) + j0 * row_bytes;
-        if (int e = bess_neg_score_shared_fwd_ws(d, query, n_query, base, neg_idx ? neg_idx + j0 : nullptr, nc, tile, cols,
-                                                 nullptr, 0, stream))
-            return e;
+    return for_each_candidate_chunk(neg_base, neg_idx, n_neg, cols, row_bytes,
+                                    [&](int64_t j0, int64_t nc, const void* base, const int32_t* idx) {
+        if (int e = bess_neg_score_shared_fwd_ws(d, query, n_query, base, idx, nc, tile, cols, nullptr, 0, stream)) return e;
         k_count_scores<<<static_cast<unsigned>(ceil_div(n_query, 4)), 256, 0, st>>>(tile, cols, n_query, nc, thr, excl,
                                                                                     j0, counts, cnt.round16);
-        if (int e = check_launch("count_scores")) return e;
-    }
-    return BESS_OK;
+        return check_launch("count_scores");
+    });
 }
 
 // ---- single (query, candidate) scores in the arithmetic of the all-entity kernels -------------------------
@@ -1203,18 +1193,13 @@ extern "C" int bess_neg_score_table_fwd_counts(const bess_model_desc* d, const f
                  "neg_score_table_fwd_counts: workspace too small (bess_neg_score_table_fwd_counts_workspace) or misaligned");
     hipStream_t st = as_stream(stream);
     float* inv = normalize ? static_cast<float*>(workspace) : nullptr;
-    const int64_t chunk = affine_chunk_rows(d);
-    const int64_t row_bytes = static_cast<int64_t>(d->width) * (d->dtype == BESS_F32 ? 4 : 2);
-    for (int64_t j0 = 0; j0 < n_neg; j0 += chunk) {
-        const int64_t nc = n_neg - j0 < chunk ? n_neg - j0 : chunk;
-        const void* base = neg_idx ? neg_base : static_cast<const char*>(neg_base) + j0 * row_bytes;
-        const int32_t* idx = neg_idx ? neg_idx + j0 : nullptr;
+    return for_each_candidate_chunk(neg_base, neg_idx, n_neg, affine_chunk_rows(d), row_bytes_of(d),
+                                    [&](int64_t j0, int64_t nc, const void* base, const int32_t* idx) {
         if (normalize)
             if (int e = affine_inv_norms(d, base, idx, nc, inv, st)) return e;
         const CountArgs cj{excl, counts, j0, round_f16 ? 1 : 0};
-        if (int e = affine_table_fwd(d, query, n_query, base, idx, inv, nc, nullptr, 0, thr, &cj, st)) return e;
-    }
-    return BESS_OK;
+        return affine_table_fwd(d, query, n_query, base, idx, inv, nc, nullptr, 0, thr, &cj, st);
+    });
 }
 
 extern "C" int64_t bess_neg_score_table_fwd_pairs_workspace(const bess_model_desc* d, int64_t like_n_query,
@@ -1290,14 +1275,12 @@ extern "C" int bess_neg_score_shared_bwd_parts(const bess_model_desc* d, const f
     if (d->scorer > BESS_COMPLEX || !use_l1_bwd_parts(d, n_query, n_neg))
         return fail(BESS_EUNSUPPORTED, "neg_score_shared_bwd_parts: this scorer / shape has no partial-sum form "
                                        "(bess_neg_score_shared_bwd_parts_plan says 0 parts)");
+    // the packed-fp16 forward (fp16 tables only) scores the query rounded to fp16: differentiate that function
     const bool r16 = use_l1_pk(d, query, neg_base);
-    RowSrc<float> Q{query, nullptr, n_query};
-    hipStream_t st = as_stream(stream);
-    if (d->dtype == BESS_F32)
-        return run_l1_bwd_parts<float>(d, Q, RowSrc<float>{static_cast<const float*>(neg_base), neg_idx, n_neg}, d_out,
-                                       ld_dout, dq_parts, dneg_parts, st, false);
-    return run_l1_bwd_parts<half_t>(d, Q, RowSrc<half_t>{static_cast<const half_t*>(neg_base), neg_idx, n_neg}, d_out,
-                                    ld_dout, dq_parts, dneg_parts, st, r16);
+    return with_candidates(d, neg_base, neg_idx, n_neg, [&](auto E) {
+        return run_l1_bwd_parts(d, RowSrc<float>{query, nullptr, n_query}, E, d_out, ld_dout, dq_parts, dneg_parts,
+                                as_stream(stream), r16);
+    });
 }
 
 extern "C" int bess_neg_score_shared_bwd(const bess_model_desc* d, const float* query,
@@ -1332,24 +1315,18 @@ extern "C" int bess_neg_score_shared_bwd_ws(const bess_model_desc* d, const floa
                                  ld_dout, d_query, d_neg, st);
     }
     if (reduce_of(d) == RED_DOT) {
-        const bool fp32 = d->reserved[0] & BESS_FLAG_FP32_MATH;
-        const int64_t want = workspace && !fp32 ? gemm_split_bwd_workspace(n_query, n_neg, d->width) : 0;
-        if (want > 0 && workspace_bytes >= want)
+        if (split_fits(d, gemm_split_bwd_workspace, n_query, n_neg, workspace, workspace_bytes))
             return gemm_split_bwd(d->dtype, d_out, ld_dout, n_query, query, neg_base, neg_idx, n_neg, d->width,
                                   d_query, d_neg, workspace, workspace_bytes, st);
         if (int e = gemm_dot_dq(d->dtype, d_out, ld_dout, n_query, neg_base, neg_idx, n_neg, d->width, d_query, st))
             return e;
         return gemm_dot_de(d_out, ld_dout, n_query, query, n_neg, d->width, d_neg, st);
     }
-    // the packed-fp16 forward scores the query rounded to fp16: differentiate that function
+    // the packed-fp16 forward (fp16 tables only) scores the query rounded to fp16: differentiate that function
     const bool r16 = use_l1_pk(d, query, neg_base);
-    RowSrc<float> Q{query, nullptr, n_query};
-    if (d->dtype == BESS_F32) {
-        RowSrc<float> E{static_cast<const float*>(neg_base), neg_idx, n_neg};
-        if (int e = run_bwd<float>(d, Q, E, d_out, ld_dout, out, ld_out, d_query, d_neg, st, false)) return e;
-    } else {
-        RowSrc<half_t> E{static_cast<const half_t*>(neg_base), neg_idx, n_neg};
-        if (int e = run_bwd<half_t>(d, Q, E, d_out, ld_dout, out, ld_out, d_query, d_neg, st, r16)) return e;
-    }
+    if (int e = with_candidates(d, neg_base, neg_idx, n_neg, [&](auto E) {
+            return run_bwd(d, RowSrc<float>{query, nullptr, n_query}, E, d_out, ld_dout, out, ld_out, d_query, d_neg, st, r16);
+        }))
+        return e;
     return check_launch("neg_score_shared_bwd");
 }

@@ -607,92 +607,15 @@ __global__ __launch_bounds__(256) void k_query_triple_bwd_parts(TripleArgs a, Qu
     query_triple_bwd_body<T, SCORER, true>(a, qa.side, s, lane, d_out[s], row, acc_head, acc_tail, d_rel);
 }
 
-template <template <typename, int> class Launcher, typename... Args>
-static int dispatch(const bess_model_desc* d, Args... args) {
-#define BESS_CASE(SC)                                                   \
-    case SC:                                                            \
-        if (d->dtype == BESS_F32) Launcher<float, SC>::run(args...);    \
-        else Launcher<half_t, SC>::run(args...);                        \
-        break;
-    switch (d->scorer) {
-        BESS_CASE(BESS_TRANSE)
-        BESS_CASE(BESS_ROTATE)
-        BESS_CASE(BESS_DISTMULT)
-        BESS_CASE(BESS_COMPLEX)
-    }
-#undef BESS_CASE
-    return BESS_OK;
+// k_pertriple_tail's workgroup: 16 waves (one triple each) once that still fills the chip, fewer when their rows would
+// not fit 32 KB of LDS (W = 4096: two waves)
+static int tail_waves(int64_t n, int W) {
+    int nw = n > 1024 ? 16 : 4;
+    while (nw > 1 && static_cast<size_t>(nw) * W * sizeof(float) > (32u << 10)) nw >>= 1;
+    return nw;
 }
-
-template <typename T, int SC>
-struct LTripleFwd {
-    static void run(TripleArgs a, float* out, hipStream_t st) {
-        k_score_triple_fwd<T, SC><<<ceil_div(a.n, 4), 256, 0, st>>>(a, out);
-    }
-};
-template <typename T, int SC>
-struct LTripleBwd {
-    static void run(TripleArgs a, const float* d_out, float* dh, float* dt, float* dr, hipStream_t st) {
-        k_score_triple_bwd<T, SC><<<ceil_div(a.n, 4), 256, 0, st>>>(a, d_out, dh, dt, dr);
-    }
-};
-template <typename T, int SC>
-struct LQueryFwd {
-    static void run(QueryArgs a, float* q, hipStream_t st) {
-        k_query_fwd<T, SC><<<ceil_div(a.n, 4), 256, 0, st>>>(a, q);
-    }
-};
-template <typename T, int SC>
-struct LQueryBwd {
-    static void run(QueryArgs a, const float* dq, float* dx, float* dr, hipStream_t st) {
-        k_query_bwd<T, SC><<<ceil_div(a.n, 4), 256, 0, st>>>(a, dq, dx, dr);
-    }
-};
-
-template <typename T, int SC>
-struct LQueryTripleFwd {
-    static void run(TripleArgs a, QueryArgs qa, float* q, float* out, hipStream_t st) {
-        k_query_triple_fwd<T, SC><<<ceil_div(a.n, 4), 256, 0, st>>>(a, qa, q, out);
-    }
-};
-template <typename T, int SC>
-struct LQueryTripleFwdJobs {
-    static void run(TripleArgs a, QueryArgs qa, float* q, float* out, WordJobs J, int job_blocks, hipStream_t st) {
-        const int tb = static_cast<int>(ceil_div(a.n, 4));
-        k_query_triple_fwd_jobs<T, SC><<<tb + job_blocks, 256, 0, st>>>(a, qa, q, out, J, tb);
-    }
-};
-template <typename T, int SC>
-struct LQueryTripleBwdParts {
-    static void run(TripleArgs a, QueryArgs qa, const float* d_out, const float* dqp, int n_dq, const float* dep, int n_de,
-                    int64_t n_neg, const int32_t* neg_idx, float* ah, float* at, float* an, float* dr, hipStream_t st) {
-        const int tb = static_cast<int>(ceil_div(a.n, 4));
-        const int nb = static_cast<int>(std::min<int64_t>(ceil_div(n_neg, 4), 1024));
-        k_query_triple_bwd_parts<T, SC><<<tb + nb, 256, 4 * a.W * sizeof(float), st>>>(a, qa, d_out, dqp, n_dq, dep, n_de,
-                                                                                      n_neg, neg_idx, ah, at, an, dr, tb);
-    }
-};
-template <typename T, int SC>
-struct LQueryTripleBwd {
-    static void run(TripleArgs a, QueryArgs qa, const float* d_out, const float* dq, float* dh, float* dt, float* dr,
-                    hipStream_t st) {
-        k_query_triple_bwd<T, SC><<<ceil_div(a.n, 4), 256, 0, st>>>(a, qa, d_out, dq, dh, dt, dr);
-    }
-};
-
-template <typename T, int SC>
-struct LPertripleTail {
-    static void run(TripleArgs a, QueryArgs qa, TailArgs t, float* dh, float* dt, float* dr, int ch, hipStream_t st) {
-        // 16 waves (one triple each) per workgroup once that still fills the chip, fewer when their rows would not fit
-        // 32 KB of LDS (W = 4096: two waves)
-        int nw = a.n > 1024 ? 16 : 4;
-        while (nw > 1 && static_cast<size_t>(nw) * a.W * sizeof(float) > (32u << 10)) nw >>= 1;
-        const unsigned grid = static_cast<unsigned>(ceil_div(a.n, nw));
-        const size_t lds = sizeof(float) * static_cast<size_t>(std::max(nw * a.W, 64 * nw));
-        if (ch == 4) k_pertriple_tail<T, SC, 4><<<grid, 64 * nw, lds, st>>>(a, qa, t, dh, dt, dr);
-        else k_pertriple_tail<T, SC, 12><<<grid, 64 * nw, lds, st>>>(a, qa, t, dh, dt, dr);
-    }
-};
+// ... and the CH of its loss rows (loss_rows.h: the row of up to 256 * CH scores stays in the wave's registers)
+static int tail_loss_chunks(int64_t n_neg) { return n_neg <= 1024 ? 4 : 12; }
 
 }  // namespace bess
 
@@ -718,7 +641,9 @@ extern "C" int bess_score_triple_fwd(const bess_model_desc* d, const void* head_
         return e;
     if (n_triple == 0) return BESS_OK;
     BESS_REQUIRE(out, "score_triple_fwd: NULL out");
-    dispatch<LTripleFwd>(d, a, out, as_stream(stream));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_score_triple_fwd<decltype(t), decltype(sc)::value><<<ceil_div(a.n, 4), 256, 0, as_stream(stream)>>>(a, out);
+    });
     return check_launch("score_triple_fwd");
 }
 
@@ -733,7 +658,10 @@ extern "C" int bess_score_triple_bwd(const bess_model_desc* d, const void* head_
         return e;
     if (n_triple == 0) return BESS_OK;
     BESS_REQUIRE(d_out && d_head && d_tail && d_rel_table, "score_triple_bwd: NULL pointer");
-    dispatch<LTripleBwd>(d, a, d_out, d_head, d_tail, d_rel_table, as_stream(stream));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_score_triple_bwd<decltype(t), decltype(sc)::value>
+            <<<ceil_div(a.n, 4), 256, 0, as_stream(stream)>>>(a, d_out, d_head, d_tail, d_rel_table);
+    });
     return check_launch("score_triple_bwd");
 }
 
@@ -758,7 +686,9 @@ extern "C" int bess_query_fwd(const bess_model_desc* d, int32_t side, const void
     if (int e = query_args(d, side, ent_base, ent_idx, rel_table, rel_idx, n_query, &a)) return e;
     if (n_query == 0) return BESS_OK;
     BESS_REQUIRE(query, "query_fwd: NULL out");
-    dispatch<LQueryFwd>(d, a, query, as_stream(stream));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_query_fwd<decltype(t), decltype(sc)::value><<<ceil_div(a.n, 4), 256, 0, as_stream(stream)>>>(a, query);
+    });
     return check_launch("query_fwd");
 }
 
@@ -775,8 +705,22 @@ extern "C" int bess_query_bwd(const bess_model_desc* d, int32_t side, const void
     if (int e = query_args(d, side, ent_base, ent_idx, rel_table, rel_idx, n_query, &a)) return e;
     if (n_query == 0) return BESS_OK;
     BESS_REQUIRE(d_query && d_ent && d_rel_table, "query_bwd: NULL pointer");
-    dispatch<LQueryBwd>(d, a, d_query, d_ent, d_rel_table, as_stream(stream));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_query_bwd<decltype(t), decltype(sc)::value>
+            <<<ceil_div(a.n, 4), 256, 0, as_stream(stream)>>>(a, d_query, d_ent, d_rel_table);
+    });
     return check_launch("query_bwd");
+}
+
+// the launches' two argument structs from an entry point's (side, head, tail, rel): the query is built from the head
+// for tail corruption, else from the tail.  `what`: the entry point's name in its refusal
+static int query_triple_args(const bess_model_desc* d, int32_t side, const void* hb, const int32_t* hi, const void* tb,
+                             const int32_t* ti, const void* rt, const int32_t* ri, int64_t n, const char* what,
+                             TripleArgs* a, QueryArgs* qa) {
+    if (int e = triple_args(d, hb, hi, tb, ti, rt, ri, n, a)) return e;
+    BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "%s: TransE / RotatE / DistMult / ComplEx only", what);
+    const bool tail = side == BESS_CORRUPT_TAIL;
+    return query_args(d, side, tail ? hb : tb, tail ? hi : ti, rt, ri, n, qa);
 }
 
 extern "C" int bess_query_triple_fwd(const bess_model_desc* d, int32_t side, const void* head_base,
@@ -784,17 +728,16 @@ extern "C" int bess_query_triple_fwd(const bess_model_desc* d, int32_t side, con
                                      const void* rel_table, const int32_t* rel_idx, int64_t n_triple, float* query,
                                      float* out, void* stream) {
     TripleArgs a;
-    if (int e = triple_args(d, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple, &a))
-        return e;
-    BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "query_triple_fwd: TransE / RotatE / DistMult / ComplEx only");
     QueryArgs qa;
-    const bool tail = side == BESS_CORRUPT_TAIL;
-    if (int e = query_args(d, side, tail ? head_base : tail_base, tail ? head_idx : tail_idx, rel_table, rel_idx,
-                           n_triple, &qa))
+    if (int e = query_triple_args(d, side, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple,
+                                  "query_triple_fwd", &a, &qa))
         return e;
     if (n_triple == 0) return BESS_OK;
     BESS_REQUIRE(query && out, "query_triple_fwd: NULL out");
-    dispatch<LQueryTripleFwd>(d, a, qa, query, out, as_stream(stream));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_query_triple_fwd<decltype(t), decltype(sc)::value>
+            <<<ceil_div(a.n, 4), 256, 0, as_stream(stream)>>>(a, qa, query, out);
+    });
     return check_launch("query_triple_fwd");
 }
 
@@ -804,13 +747,9 @@ extern "C" int bess_query_triple_fwd_jobs(const bess_model_desc* d, int32_t side
                                           float* out, int32_t n_jobs, void* const* job_dst, const void* const* job_src,
                                           const uint32_t* job_value, const int64_t* job_words, void* stream) {
     TripleArgs a;
-    if (int e = triple_args(d, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple, &a))
-        return e;
-    BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "query_triple_fwd_jobs: TransE / RotatE / DistMult / ComplEx only");
     QueryArgs qa;
-    const bool tail = side == BESS_CORRUPT_TAIL;
-    if (int e = query_args(d, side, tail ? head_base : tail_base, tail ? head_idx : tail_idx, rel_table, rel_idx,
-                           n_triple, &qa))
+    if (int e = query_triple_args(d, side, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple,
+                                  "query_triple_fwd_jobs", &a, &qa))
         return e;
     WordJobs J{};
     int64_t words = 0;
@@ -819,7 +758,11 @@ extern "C" int bess_query_triple_fwd_jobs(const bess_model_desc* d, int32_t side
     BESS_REQUIRE(n_triple == 0 || (query && out), "query_triple_fwd_jobs: NULL out");
     // ~8 words per thread of the job workgroups, at most one workgroup per CU
     const int job_blocks = static_cast<int>(std::min<int64_t>(ceil_div(words, 8 * 256), 256));
-    dispatch<LQueryTripleFwdJobs>(d, a, qa, query, out, J, job_blocks, as_stream(stream));
+    const int tb = static_cast<int>(ceil_div(a.n, 4));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_query_triple_fwd_jobs<decltype(t), decltype(sc)::value>
+            <<<tb + job_blocks, 256, 0, as_stream(stream)>>>(a, qa, query, out, J, tb);
+    });
     return check_launch("query_triple_fwd_jobs");
 }
 
@@ -831,20 +774,21 @@ extern "C" int bess_query_triple_bwd_parts(const bess_model_desc* d, int32_t sid
                                            const int32_t* neg_idx, float* acc_head, float* acc_tail, float* acc_neg,
                                            float* d_rel_table, void* stream) {
     TripleArgs a;
-    if (int e = triple_args(d, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple, &a))
-        return e;
-    BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "query_triple_bwd_parts: TransE / RotatE / DistMult / ComplEx only");
     QueryArgs qa;
-    const bool tail = side == BESS_CORRUPT_TAIL;
-    if (int e = query_args(d, side, tail ? head_base : tail_base, tail ? head_idx : tail_idx, rel_table, rel_idx,
-                           n_triple, &qa))
+    if (int e = query_triple_args(d, side, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple,
+                                  "query_triple_bwd_parts", &a, &qa))
         return e;
     BESS_REQUIRE(n_triple > 0 && n_neg > 0 && n_dq_parts >= 1 && n_dneg_parts >= 1, "query_triple_bwd_parts: bad sizes");
     BESS_REQUIRE(d_out && dq_parts && dneg_parts && neg_idx && head_idx && tail_idx && acc_head && acc_tail && acc_neg &&
                      d_rel_table, "query_triple_bwd_parts: NULL pointer (rows are named by index: by-row accumulators)");
     BESS_REQUIRE(d->width <= 4096, "query_triple_bwd_parts: rows of %d scalars (at most 4096)", d->width);
-    dispatch<LQueryTripleBwdParts>(d, a, qa, d_out, dq_parts, n_dq_parts, dneg_parts, n_dneg_parts, n_neg, neg_idx, acc_head,
-                                   acc_tail, acc_neg, d_rel_table, as_stream(stream));
+    const int tb = static_cast<int>(ceil_div(a.n, 4));
+    const int nb = static_cast<int>(std::min<int64_t>(ceil_div(n_neg, 4), 1024));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_query_triple_bwd_parts<decltype(t), decltype(sc)::value><<<tb + nb, 256, 4 * a.W * sizeof(float), as_stream(stream)>>>(
+            a, qa, d_out, dq_parts, n_dq_parts, dneg_parts, n_dneg_parts, n_neg, neg_idx, acc_head, acc_tail, acc_neg,
+            d_rel_table, tb);
+    });
     return check_launch("query_triple_bwd_parts");
 }
 
@@ -854,17 +798,16 @@ extern "C" int bess_query_triple_bwd(const bess_model_desc* d, int32_t side, con
                                      const float* d_out, const float* d_query, float* d_head, float* d_tail,
                                      float* d_rel_table, void* stream) {
     TripleArgs a;
-    if (int e = triple_args(d, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple, &a))
-        return e;
-    BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "query_triple_bwd: TransE / RotatE / DistMult / ComplEx only");
     QueryArgs qa;
-    const bool tail = side == BESS_CORRUPT_TAIL;
-    if (int e = query_args(d, side, tail ? head_base : tail_base, tail ? head_idx : tail_idx, rel_table, rel_idx,
-                           n_triple, &qa))
+    if (int e = query_triple_args(d, side, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple,
+                                  "query_triple_bwd", &a, &qa))
         return e;
     if (n_triple == 0) return BESS_OK;
     BESS_REQUIRE(d_out && d_query && d_head && d_tail && d_rel_table, "query_triple_bwd: NULL pointer");
-    dispatch<LQueryTripleBwd>(d, a, qa, d_out, d_query, d_head, d_tail, d_rel_table, as_stream(stream));
+    dispatch_scorer_class(d, [&](auto t, auto sc) {
+        k_query_triple_bwd<decltype(t), decltype(sc)::value>
+            <<<ceil_div(a.n, 4), 256, 0, as_stream(stream)>>>(a, qa, d_out, d_query, d_head, d_tail, d_rel_table);
+    });
     return check_launch("query_triple_bwd");
 }
 
@@ -881,12 +824,9 @@ extern "C" int bess_pertriple_tail(const bess_model_desc* d, const bess_loss_des
                                    int64_t ld_dneg, float* d_query, float* d_head, float* d_tail, float* d_rel_table,
                                    int32_t* counter, void* stream) {
     TripleArgs a;
-    if (int e = triple_args(d, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple, &a)) return e;
-    BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "pertriple_tail: TransE / RotatE / DistMult / ComplEx only");
     QueryArgs qa;
-    const bool tail = side == BESS_CORRUPT_TAIL;
-    if (int e = query_args(d, side, tail ? head_base : tail_base, tail ? head_idx : tail_idx, rel_table, rel_idx, n_triple,
-                           &qa))
+    if (int e = query_triple_args(d, side, head_base, head_idx, tail_base, tail_idx, rel_table, rel_idx, n_triple,
+                                  "pertriple_tail", &a, &qa))
         return e;
     BESS_REQUIRE(l, "pertriple_tail: NULL loss descriptor");
     BESS_REQUIRE(l->kind >= BESS_LOSS_LOGSIGMOID && l->kind <= BESS_LOSS_SSCE, "pertriple_tail: unknown loss %d", l->kind);
@@ -902,6 +842,14 @@ extern "C" int bess_pertriple_tail(const bess_model_desc* d, const bess_loss_des
                  "pertriple_tail: score rows must be 16-byte aligned");
     TailArgs t{state_ml, state_acc, items, *l, pos, neg, n_neg, ld_neg, weight, weight_len, row_loss, loss, d_pos, d_neg,
                ld_dneg, d_query, counter};
-    dispatch<LPertripleTail>(d, a, qa, t, d_head, d_tail, d_rel_table, n_neg <= 1024 ? 4 : 12, as_stream(stream));
+    const int nw = tail_waves(a.n, a.W);
+    const unsigned grid = static_cast<unsigned>(ceil_div(a.n, nw));
+    const size_t lds = sizeof(float) * static_cast<size_t>(std::max(nw * a.W, 64 * nw));
+    dispatch_scorer_class(d, [&](auto tt, auto sc) {
+        with_constant<4, 12>(tail_loss_chunks(n_neg), [&](auto ch) {
+            k_pertriple_tail<decltype(tt), decltype(sc)::value, decltype(ch)::value>
+                <<<grid, 64 * nw, lds, as_stream(stream)>>>(a, qa, t, d_head, d_tail, d_rel_table);
+        });
+    });
     return check_launch("pertriple_tail");
 }

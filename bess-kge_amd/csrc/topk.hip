@@ -363,14 +363,21 @@ __global__ __launch_bounds__(256) void k_topk_update_flagged(const float* __rest
 
 using namespace bess;
 
-static int topk_update_flagged(bool ord, const char* what, const float* scores, int64_t n_row, int64_t n_col, int64_t ld,
-                               const uint8_t* flags, int64_t ld_flags, const int32_t* ids, int32_t id_base,
-                               const int32_t* excl_ptr, const int32_t* excl_ids, int64_t n_excl, int32_t round_f16,
-                               float* best_score, int32_t* best_id, int32_t kk, void* stream) {
+// what both update calls ask of their sizes, list length and exclusion lists
+static int topk_check_sizes(const char* what, int64_t n_row, int64_t n_col, int64_t ld, int32_t kk, const int32_t* excl_ptr,
+                            const int32_t* excl_ids, int64_t n_excl) {
     BESS_REQUIRE(n_row >= 0 && n_row < (1ll << 31) && n_col >= 0 && ld >= n_col, "%s: bad sizes", what);
     BESS_REQUIRE(kk >= 1 && kk <= 128, "%s: list length %d not in [1, 128]", what, kk);
     BESS_REQUIRE(!excl_ptr == !excl_ids && n_excl >= 0 && n_excl < (1ll << 31),
                  "%s: excl_ptr and excl_ids go together (fewer than 2^31 entries)", what);
+    return BESS_OK;
+}
+
+static int topk_update_flagged(bool ord, const char* what, const float* scores, int64_t n_row, int64_t n_col, int64_t ld,
+                               const uint8_t* flags, int64_t ld_flags, const int32_t* ids, int32_t id_base,
+                               const int32_t* excl_ptr, const int32_t* excl_ids, int64_t n_excl, int32_t round_f16,
+                               float* best_score, int32_t* best_id, int32_t kk, void* stream) {
+    if (int e = topk_check_sizes(what, n_row, n_col, ld, kk, excl_ptr, excl_ids, n_excl)) return e;
     if (n_row == 0 || n_col == 0) return BESS_OK;
     BESS_REQUIRE(scores && flags && best_score && best_id, "%s: NULL pointer", what);
     BESS_REQUIRE(ld_flags % 4 == 0 && ld_flags >= (n_col + 63) / 64 && reinterpret_cast<uintptr_t>(flags) % 4 == 0,
@@ -378,17 +385,13 @@ static int topk_update_flagged(bool ord, const char* what, const float* scores, 
     const unsigned grid = static_cast<unsigned>(ceil_div(n_row, 4));
     const uint32_t* f32 = reinterpret_cast<const uint32_t*>(flags);
     hipStream_t st = as_stream(stream);
-#define BESS_TOPK_FLAGGED(TWO, ORD)                                                                               \
-    k_topk_update_flagged<TWO, ORD><<<grid, 256, 0, st>>>(scores, n_row, n_col, ld, f32, ld_flags / 4, ids, id_base, \
-                                                          excl_ptr, excl_ids, n_excl, round_f16, best_score, best_id, kk)
-    if (ord) {
-        if (kk > 64) BESS_TOPK_FLAGGED(true, true);
-        else BESS_TOPK_FLAGGED(false, true);
-    } else {
-        if (kk > 64) BESS_TOPK_FLAGGED(true, false);
-        else BESS_TOPK_FLAGGED(false, false);
-    }
-#undef BESS_TOPK_FLAGGED
+    with_flag(kk > 64, [&](auto two) {
+        with_flag(ord, [&](auto o) {
+            k_topk_update_flagged<decltype(two)::value, decltype(o)::value><<<grid, 256, 0, st>>>(
+                scores, n_row, n_col, ld, f32, ld_flags / 4, ids, id_base, excl_ptr, excl_ids, n_excl, round_f16, best_score,
+                best_id, kk);
+        });
+    });
     return check_launch(what);
 }
 
@@ -412,10 +415,7 @@ static int topk_update(bool ord, const char* what, const float* scores, int64_t 
                        const int32_t* ids, int64_t ids_rows, int32_t id_base, const uint8_t* mask, int64_t mask_rows,
                        const int32_t* excl_ptr, const int32_t* excl_ids, int64_t n_excl, int32_t round_f16,
                        float* best_score, int32_t* best_id, int32_t kk, void* stream) {
-    BESS_REQUIRE(n_row >= 0 && n_row < (1ll << 31) && n_col >= 0 && ld >= n_col, "%s: bad sizes", what);
-    BESS_REQUIRE(kk >= 1 && kk <= 128, "%s: list length %d not in [1, 128]", what, kk);
-    BESS_REQUIRE(!excl_ptr == !excl_ids && n_excl >= 0 && n_excl < (1ll << 31),
-                 "%s: excl_ptr and excl_ids go together (fewer than 2^31 entries)", what);
+    if (int e = topk_check_sizes(what, n_row, n_col, ld, kk, excl_ptr, excl_ids, n_excl)) return e;
     if (n_row == 0 || n_col == 0) return BESS_OK;
     BESS_REQUIRE(scores && best_score && best_id, "%s: NULL pointer", what);
     BESS_REQUIRE(!ids || ids_rows == 1 || ids_rows == n_row, "%s: ids_rows must be 1 or n_row", what);
@@ -426,29 +426,17 @@ static int topk_update(bool ord, const char* what, const float* scores, int64_t 
     const bool vec = ld % 4 == 0 && reinterpret_cast<uintptr_t>(scores) % 16 == 0;
     const unsigned grid = static_cast<unsigned>(wide ? n_row : ceil_div(n_row, 4));
     hipStream_t st = as_stream(stream);
-#define BESS_TOPK_K(WPR, VEC, TWO, ORD)                                                                             \
-    k_topk_update<WPR, VEC, TWO, ORD><<<grid, 256, 0, st>>>(scores, n_row, n_col, ld, ids, ids_rows, id_base, mask, \
-                                                            mask_rows, excl_ptr, excl_ids, n_excl, round_f16,      \
-                                                            best_score, best_id, kk)
-#define BESS_TOPK(WPR, VEC)                          \
-    do {                                             \
-        if (kk > 64) {                               \
-            if (ord) BESS_TOPK_K(WPR, VEC, true, true);    \
-            else BESS_TOPK_K(WPR, VEC, true, false);       \
-        } else {                                     \
-            if (ord) BESS_TOPK_K(WPR, VEC, false, true);   \
-            else BESS_TOPK_K(WPR, VEC, false, false);      \
-        }                                            \
-    } while (0)
-    if (wide) {
-        if (vec) BESS_TOPK(4, true);
-        else BESS_TOPK(4, false);
-    } else {
-        if (vec) BESS_TOPK(1, true);
-        else BESS_TOPK(1, false);
-    }
-#undef BESS_TOPK
-#undef BESS_TOPK_K
+    with_constant<4, 1>(wide ? 4 : 1, [&](auto wpr) {
+        with_flag(vec, [&](auto v) {
+            with_flag(kk > 64, [&](auto two) {
+                with_flag(ord, [&](auto o) {
+                    k_topk_update<decltype(wpr)::value, decltype(v)::value, decltype(two)::value, decltype(o)::value>
+                        <<<grid, 256, 0, st>>>(scores, n_row, n_col, ld, ids, ids_rows, id_base, mask, mask_rows, excl_ptr,
+                                               excl_ids, n_excl, round_f16, best_score, best_id, kk);
+                });
+            });
+        });
+    });
     return check_launch(what);
 }
 

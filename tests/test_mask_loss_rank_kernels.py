@@ -4,7 +4,7 @@ plain references - other tests use these kernels AS their reference, so they are
   0. the references themselves, on the CPU (no device): the K7 rule of include/besskge_hip.h restated element by
      element == `oracle.kge.apply_masks`; the float64 loss oracle == the fp32 one; the rank restatements == brute force;
   1. `mask_scores` == the rule, bit for bit;
-  2. loss, d_pos, d_neg and row_norm == the float64 oracle, over every row class `launch_loss` dispatches on, both
+  2. loss, d_pos, d_neg and row_norm == the float64 oracle, over every row class `loss_chunks` tells apart, both
      weight forms, four memory layouts and four value regimes;
   3. the one-launch form's grid sizes and ticket counters;
   4. the rank kernels == integer counts.
