@@ -33,6 +33,7 @@ from . import (  # noqa: E402,F401
     embedding,
     loss,
     metric,
+    negative_filter,
     negative_sampler,
     pipeline,
     query,
@@ -51,6 +52,7 @@ __all__ = [
     "embedding",
     "loss",
     "metric",
+    "negative_filter",
     "negative_sampler",
     "pipeline",
     "query",

@@ -199,6 +199,8 @@ SIGNATURES = {
     "bess_sample_bucket_indices": [_PG, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "bess_lookup_triples": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
     "bess_gather_candidate_lists": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp],
+    "bess_known_triple_mask": [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64,
+                               _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _i32, _vp],
     "bess_comm_unique_id": [_c_u8p],
     "bess_comm_init_rank": [_i32, _i32, _c_u8p, ctypes.POINTER(_vp)],
     "bess_comm_init_all": [_i32, _c_i32p, ctypes.POINTER(_vp)],
@@ -1918,6 +1920,89 @@ def gather_candidate_lists(table_h: torch.Tensor, mask_h: Optional[torch.Tensor]
             n_list, lookup.data_ptr(), n_step, n_shard, T, int(per_part), int(half), n_neg_shard, L,
             int(bool(mask_gather_layout)), ent.data_ptr(), msk.data_ptr() if msk is not None else None)
     return ent, msk
+
+
+def known_triple_mask(index: Sequence[torch.Tensor], kept: torch.Tensor, relation: torch.Tensor, cand: torch.Tensor,
+                      mask: torch.Tensor, n_relation: int, index2: Optional[Sequence[torch.Tensor]] = None,
+                      side: Optional[torch.Tensor] = None, kept_shard: Optional[torch.Tensor] = None,
+                      n_col: Optional[int] = None, ld_cand: Optional[int] = None, n_cand_row: Optional[int] = None,
+                      cand_row: Optional[torch.Tensor] = None, cols_per_block: int = 0, block_stride: int = 0,
+                      cand_shard: int = -1, local_to_global: Optional[torch.Tensor] = None,
+                      ld_mask: Optional[int] = None, and_into: bool = False) -> torch.Tensor:
+    """mask[i, j] = 0 where (kept_i, relation_i, cand_ij) is a known triple, 1 elsewhere (bess_known_triple_mask;
+    with `and_into` bytes are only cleared).  `index` / `index2`: (pair keys int64 [P], offsets int64 [P + 1],
+    completions int32) of `KnownTripleFilter`; rows take `index2` where `side` (uint8 / bool [rows]) is set.
+    `cand`: int32 [rows, columns], or flat with the geometry given (`n_col`, `ld_cand`, `n_cand_row`, blocks of
+    `cols_per_block` columns `block_stride` apart); `mask`: uint8 / bool [rows, ld_mask], or flat with `ld_mask`."""
+    dev = _same_device([("kept", kept), ("relation", relation), ("cand", cand), ("mask", mask), ("side", side),
+                        ("kept_shard", kept_shard), ("cand_row", cand_row), ("local_to_global", local_to_global),
+                        *[(f"index[{k}]", t) for k, t in enumerate(index)],
+                        *[(f"index2[{k}]", t) for k, t in enumerate(index2 or ())]])
+    n_row = int(kept.numel())
+    kp = _int_tensor(kept, "kept", torch.int32)
+    rp = _int_tensor(relation, "relation", torch.int32, n_row)
+    ksp = _int_tensor(kept_shard, "kept_shard", torch.int32, n_row)
+    crp = _int_tensor(cand_row, "cand_row", torch.int32, n_row)
+    sp = 0
+    if side is not None:
+        if side.dtype not in (torch.uint8, torch.bool) or not side.is_contiguous() or side.numel() != n_row:
+            raise ValueError(f"`side` must be contiguous uint8 / bool with {n_row} entries")
+        if index2 is None:
+            raise ValueError("a `side` vector needs the index of both sides (`index2`)")
+        sp = side.data_ptr()
+
+    def index_ptrs(ix: Optional[Sequence[torch.Tensor]], name: str) -> Tuple[int, int, int, int]:
+        if ix is None:
+            return 0, 0, 0, 0
+        keys, off, comp = ix
+        n_pair = int(keys.numel())
+        _int_tensor(keys, f"{name} keys", torch.int64)
+        _int_tensor(off, f"{name} offsets", torch.int64, n_pair + 1)
+        _int_tensor(comp, f"{name} completions", torch.int32)
+        return keys.data_ptr(), off.data_ptr(), n_pair, comp.data_ptr()
+
+    i1, i2 = index_ptrs(index, "index"), index_ptrs(index2, "index2")
+    _int_tensor(cand, "cand", torch.int32)
+    if cand.dim() == 2 and n_col is None:
+        n_cand_row, n_col = (int(x) for x in cand.shape)
+        ld_cand = n_col if ld_cand is None else ld_cand
+    if n_col is None or ld_cand is None or n_cand_row is None:
+        raise ValueError("a flat `cand` needs `n_col`, `ld_cand` and `n_cand_row`")
+    n_col, ld_cand, n_cand_row = int(n_col), int(ld_cand), int(n_cand_row)
+    cpb = int(cols_per_block) if cols_per_block > 0 else max(n_col, 1)
+    stride = int(block_stride) if cols_per_block > 0 else cpb
+    empty = n_row == 0 or n_col == 0  # (nothing is read or written then)
+    if n_col < 0 or ld_cand < 0 or stride < cpb or (n_cand_row < 1 and not empty):
+        raise ValueError("bad candidate geometry")
+    n_block = -(-n_col // cpb)
+    span = (n_block - 1) * stride + (n_col - (n_block - 1) * cpb)  # elements from a candidate row's start to its end
+    if not empty and (n_cand_row - 1 if ld_cand else 0) * ld_cand + span > cand.numel():
+        raise ValueError(f"`cand` has {cand.numel()} elements, the geometry given reaches past them")
+    if not empty and ld_cand and cand_row is None and n_cand_row < n_row:
+        raise ValueError(f"{n_cand_row} candidate rows for {n_row} rows")
+    if mask.dtype not in (torch.uint8, torch.bool) or not mask.is_contiguous():
+        raise ValueError("`mask` must be contiguous uint8 / bool")
+    if ld_mask is None:
+        if mask.dim() != 2:
+            raise ValueError("a flat `mask` needs `ld_mask`")
+        ld_mask = int(mask.shape[1])
+    ld_mask = int(ld_mask)
+    if ld_mask < n_col or (n_row > 0 and n_col > 0 and (n_row - 1) * ld_mask + n_col > mask.numel()):
+        raise ValueError(f"`mask` ({mask.numel()} bytes, ld {ld_mask}) does not hold {n_row} x {n_col}")
+    mp, ld_map, n_map_shard = 0, 0, 0
+    if local_to_global is not None:
+        if local_to_global.dtype != torch.int32 or local_to_global.dim() != 2 or not local_to_global.is_contiguous():
+            raise ValueError("`local_to_global` must be a contiguous int32 [n_shard, rows per shard] tensor")
+        n_map_shard, ld_map = (int(x) for x in local_to_global.shape)
+        if (cand_shard >= n_map_shard) or (cand_shard < 0 and n_block > n_map_shard):
+            raise ValueError("`local_to_global` does not cover the candidates' shards")
+        mp = local_to_global.data_ptr()
+    elif kept_shard is not None:
+        raise ValueError("`kept_shard` needs `local_to_global`")
+    _launch("bess_known_triple_mask", dev, *i1, *i2, kp, ksp, rp, sp, n_row, int(n_relation), cand.data_ptr(), n_col,
+            ld_cand, n_cand_row, crp, cpb, stride, int(cand_shard), mp, ld_map, n_map_shard, mask.data_ptr(), ld_mask,
+            int(bool(and_into)))
+    return mask
 
 
 # --------------------------------------------------------------------------- #

@@ -24,16 +24,22 @@ look-up + layout for the exchange (`negative_sampler.py:422-477`) is one kernel
 `shards=range(r, r + 1)` makes rank `r` of a one-process-per-GPU job produce
 only its own slice `[:, r]` of every tensor (each rank jumps to its part of
 the common stream: no broadcast of indices).
+
+`filter_triples=` (filtered negative sampling, `besskge/negative_filter.py`):
+every batch also carries the `negative_mask` that is False where a drawn
+negative completes a known triple - one kernel per step and shard
+(`bess_known_triple_mask`) against an exact index in HBM.
 """
 
 import dataclasses
-from typing import Any, Dict, Iterator, List, Optional, Sequence
+from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
 
 from besskge import _native as nat
 from besskge.batch_sampler import RandomShardedBatchSampler, RigidShardedBatchSampler, ShardedBatchSampler
+from besskge.negative_filter import SIDE_HEAD, SIDE_TAIL, KnownTripleFilter
 from besskge.negative_sampler import (
     PlaceholderNegativeSampler,
     RandomShardedNegativeSampler,
@@ -128,13 +134,35 @@ class DeviceBatchSampler:
     """Bit-exact device twin of a host `ShardedBatchSampler` (see module docstring)."""
 
     def __init__(self, batch_sampler: ShardedBatchSampler, device: torch.device,
-                 shards: Optional[Sequence[int]] = None) -> None:
+                 shards: Optional[Sequence[int]] = None,
+                 filter_triples: Union[None, KnownTripleFilter, Sequence[np.ndarray]] = None,
+                 negative_sample_sharing: bool = False) -> None:
         """
         :param batch_sampler: configured host sampler (its triples, buckets,
             options and *current generator states* are taken over).
         :param device: HIP device the index tensors are produced on.
         :param shards: contiguous range of shards whose slices are produced
             (default: all).
+        :param filter_triples: filtered negative sampling - a
+            `KnownTripleFilter`, or a list of [n, 3] arrays of known (head,
+            relation, tail) triples in *global* entity ids (with the inverse
+            triples if the sampled set has them) from which one is built.
+            `sample()` then adds `negative_mask`, bool [n_step, own shards, S,
+            n_shard, n_negative] (S: the triples a shard scores per
+            micro-batch, in their flattened order): False where the triple with
+            that negative in the corrupted place is a known one - the mask
+            `BessKGE.forward` takes.  Every other tensor is what it is without
+            the filter.  For the random and the type-based negative sampler;
+            per-triple negatives without negative sample sharing, or the flat
+            format (one candidate row serves every triple, the mask still has a
+            row per triple).  The whole index is held by every rank, about 24 B
+            per distinct triple (`KnownTripleFilter.nbytes`); with `shards` the
+            mask rows of those shards are made.  None (default): no mask,
+            nothing changes.
+        :param negative_sample_sharing: the score function's setting, only
+            read with `filter_triples`: per-triple negatives shared among all
+            triples of the micro-batch would need an S x S * n_shard *
+            n_negative mask and are refused.
         """
         bs = batch_sampler
         ns = bs.negative_sampler
@@ -143,6 +171,18 @@ class DeviceBatchSampler:
         if type(ns) not in (RandomShardedNegativeSampler, TypeBasedShardedNegativeSampler, PlaceholderNegativeSampler,
                             TripleBasedShardedNegativeSampler):
             raise TypeError(f"no device twin for {type(ns).__name__}")
+        if filter_triples is not None:
+            if type(ns) not in (RandomShardedNegativeSampler, TypeBasedShardedNegativeSampler):
+                raise ValueError(f"filter_triples: {type(ns).__name__} draws no random negatives to filter (its candidates "
+                                 "are fixed lists or placeholders); only the random and type-based samplers are filtered")
+            if not ns.flat_negative_format and negative_sample_sharing:
+                raise ValueError("filter_triples: per-triple negatives with negative_sample_sharing=True score every "
+                                 "triple against all S * n_shard * n_negative candidates - the mask would be S x that; "
+                                 "use the flat negative format or turn sharing off")
+            if ns.corruption_scheme not in ("h", "t", "ht"):
+                raise ValueError(f"filter_triples: corruption scheme {ns.corruption_scheme!r}")
+            if bs.dummy in ("head", "tail"):
+                raise ValueError(f"filter_triples: the triples have a dummy {bs.dummy}, there is no triple to look up")
         self.host = bs
         self.device = torch.device(device)
         n = bs.n_shard
@@ -192,6 +232,85 @@ class DeviceBatchSampler:
             self._triple_types = put(ns.triple_types, torch.int32)
             self._type_counts = put(ns.type_counts, torch.int32)
             self._type_offsets = put(ns.type_offsets, torch.int32)
+        self._filter: Optional[KnownTripleFilter] = None
+        if filter_triples is not None:
+            flt = filter_triples
+            if not isinstance(flt, KnownTripleFilter):
+                arrays = [np.asarray(t) for t in flt]
+                n_rel = 1 + max([int(bs.triples[:, 1].max())] + [int(t[:, 1].max()) for t in arrays if t.shape[0]])
+                flt = KnownTripleFilter(arrays, ns.sharding.n_entity, n_rel)
+            elif flt.n_entity != ns.sharding.n_entity:
+                raise ValueError(f"filter_triples indexes {flt.n_entity} entities, the sharding has {ns.sharding.n_entity}")
+            self._filter = flt.to(dev)
+            self._local_to_global = put(ns.sharding.shard_and_idx_to_entity, torch.int32)
+            self._filter_static: Dict[int, Dict[str, Any]] = {}
+
+    # ------------------------------------------------------------------ filter
+    def _filter_tables(self, per_part: int) -> Dict[str, Any]:
+        """What the rows of a shard's mask are, for blocks of `per_part` triples: fixed by the sampler's options.
+        Row (j, p) of scoring shard d is the p-th triple of block (d, j) ("ht_shardpair": its tail lives on shard
+        j) or, with one block per shard, triple p."""
+        if per_part in self._filter_static:
+            return self._filter_static[per_part]
+        bs, n = self.host, self.n_shard
+        mode, scheme = bs.triple_partition_mode, bs.negative_sampler.corruption_scheme
+        pair = mode == "ht_shardpair"
+        S = n * per_part if pair else per_part
+        p, j = np.arange(S) % per_part, np.arange(S) // per_part
+        # 1: the head is replaced (first half of every block under "ht"), the tail is the entity that stays
+        head_side = {"h": np.ones(S, bool), "t": np.zeros(S, bool), "ht": p < per_part // 2}[scheme]
+        d = np.broadcast_to(np.arange(n)[:, None], (n, S))
+        glob = np.full((n, S), -1)  # (ids the partition mode keeps global are used as they are)
+        head_shard = d if mode in ("h_shard", "ht_shardpair") else glob
+        tail_shard = np.broadcast_to(j[None, :], (n, S)) if pair else (d if mode == "t_shard" else glob)
+        dev = self.device
+
+        def put(x: np.ndarray, dtype: torch.dtype) -> torch.Tensor:
+            return torch.from_numpy(np.ascontiguousarray(x)).to(device=dev, dtype=dtype).contiguous()
+
+        tab = dict(S=S, kept_shard=put(np.where(head_side[None, :], tail_shard, head_shard), torch.int32),
+                   side=put(head_side, torch.uint8) if scheme == "ht" else None,
+                   head_side_block=put(head_side[:per_part], torch.bool),
+                   # flat "ht" negatives: row 0 of a block pair holds the heads' candidates, row 1 the tails'
+                   cand_row=put(1 - head_side.astype(np.int32), torch.int32))
+        self._filter_static[per_part] = tab
+        return tab
+
+    def _negative_mask(self, batch: Dict[str, torch.Tensor], negative: torch.Tensor, per_part: int) -> torch.Tensor:
+        """bool [n_step, own shards, S, n_shard, K] from the *whole* step's head / relation / tail [n_step, n_shard,
+        ...] and negatives [n_step, n_shard (source), n_shard (scorer), B, K]: one launch per step and own shard,
+        local rows translated in the kernel."""
+        ns, flt, n = self.host.negative_sampler, self._filter, self.n_shard
+        assert flt is not None and flt.index is not None
+        tab = self._filter_tables(per_part)
+        S, scheme = tab["S"], ns.corruption_scheme
+        head, tail, rel = batch["head"], batch["tail"], batch["relation"]
+        n_step = int(rel.shape[0])
+        tail_rows = tail.transpose(1, 2) if head.dim() == 4 else tail  # [step, scorer, (tail shard,) triple]
+        kept = head if scheme == "t" else (tail_rows if scheme == "h" else torch.where(tab["head_side_block"], tail_rows, head))
+        kept = kept.reshape(n_step, n, S).contiguous()
+        rel = rel.reshape(n_step, n, S)
+        B, K = int(negative.shape[-2]), int(negative.shape[-1])
+        if not ns.flat_negative_format and B != S:
+            raise ValueError(f"per-triple negatives for {B} triples, the shard scores {S}")
+        cand = negative.reshape(-1)
+        local = bool(ns.local_sampling) and n > 1  # block [d, j] serves shard d itself: all columns are rows of d
+        if scheme == "ht":
+            first, second = flt.index[SIDE_TAIL], flt.index[SIDE_HEAD]
+        else:
+            first, second = flt.index[SIDE_HEAD if scheme == "h" else SIDE_TAIL], None
+        rows_apart = B > 1  # (flat "h" / "t": the one candidate row is shared)
+        out = torch.empty((n_step, len(self.shards), S, n, K), dtype=torch.bool, device=self.device)
+        for s in range(n_step):
+            for i, d in enumerate(self.shards):
+                at = ((s * n + d) * n if local else s * n * n + d) * B * K
+                nat.known_triple_mask(
+                    first, kept[s, d], rel[s, d], cand[at:], out[s, i].view(S, n * K), flt.n_relation_type, index2=second,
+                    side=tab["side"], kept_shard=tab["kept_shard"][d], n_col=n * K, ld_cand=K if rows_apart else 0,
+                    n_cand_row=B, cand_row=tab["cand_row"] if (ns.flat_negative_format and B == 2) else None,
+                    cols_per_block=K, block_stride=(1 if local else n) * B * K, cand_shard=d if local else -1,
+                    local_to_global=self._local_to_global)
+        return out
 
     # ------------------------------------------------------------------ streams
     def sync_host(self) -> None:
@@ -228,7 +347,9 @@ class DeviceBatchSampler:
 
         return dict(sample_idx=steps_first(self._padded_idx), triple_mask=steps_first(self._triple_mask))
 
-    def _sample_negatives(self, sample_idx: torch.Tensor) -> Dict[str, torch.Tensor]:
+    def _sample_negatives(self, sample_idx: torch.Tensor, all_sources: bool = False) -> Dict[str, torch.Tensor]:
+        """`all_sources`: draw the blocks of every source shard, not only of `shards` (the filter needs the
+        candidates its shards *score*, which come from all of them; the stream position is the same either way)."""
         ns = self.host.negative_sampler
         if isinstance(ns, PlaceholderNegativeSampler):
             return {}
@@ -252,8 +373,9 @@ class DeviceBatchSampler:
                 half = sample_idx.shape[-1] // 2
                 t = torch.cat([types[..., :half, 0], types[..., half:, 1]], dim=-1)
             wanted = t.reshape(n_step, n, -1).contiguous()
+        src0, n_src = (0, n) if all_sources else (self.shards[0], len(self.shards))
         out = nat.sample_negatives(
-            self._neg_stream.native(), self._neg_table, n_step, n, self.shards[0], len(self.shards), B,
+            self._neg_stream.native(), self._neg_table, n_step, n, src0, n_src, B,
             ns.n_negative, self._shard_counts, wanted,
             getattr(self, "_type_counts", None) if wanted is not None else None,
             getattr(self, "_type_offsets", None) if wanted is not None else None,
@@ -314,7 +436,12 @@ class DeviceBatchSampler:
         want = [k for k in ("head", "relation", "tail") if k != bs.dummy]
         batch: Dict[str, Any] = nat.lookup_triples(self._triples, sample_idx, self._pair_buckets, want)
         batch.update(extras)
-        drawn = self._sample_negatives(sample_idx)
+        drawn = self._sample_negatives(sample_idx, all_sources=self._filter is not None)
+        negative_mask = None
+        if self._filter is not None:
+            negative_mask = self._negative_mask(batch, drawn["negative_entities"], int(sample_idx.shape[-1]))
+            if (lo, hi) != (0, self.n_shard):
+                drawn["negative_entities"] = drawn["negative_entities"][:, lo:hi].contiguous()
         if "negative_entities" in drawn:
             batch["negative"] = drawn.pop("negative_entities")
         batch.update(drawn)  # negative_mask / negative_sort_idx of the triple-based sampler
@@ -331,4 +458,6 @@ class DeviceBatchSampler:
             # or, with mask_on_gather, the gathering - shard of the mask)
             whole = isinstance(bs.negative_sampler, TripleBasedShardedNegativeSampler)
             batch = {k: (v if (k == "negative" and not whole) else v[:, lo:hi].contiguous()) for k, v in batch.items()}
+        if negative_mask is not None:
+            batch["negative_mask"] = negative_mask  # (made for `shards` only)
         return batch

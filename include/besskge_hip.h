@@ -800,6 +800,31 @@ int bess_gather_candidate_lists(const int32_t* table_h, const int32_t* table_t, 
                                 int64_t half, int64_t n_neg_shard, int64_t list_len,
                                 int32_t mask_gather_layout, int32_t* entities, uint8_t* mask, void* stream);
 
+/* Filtered negative sampling: mask[i, j] = 0 iff (kept_i, relation_i, cand_ij) - read as (h, r, t) for side 0 (the
+ * tail is replaced) and as (t, r, h) for side 1 (the head is) - is a known triple, 1 otherwise (with and_into != 0 a
+ * byte is only ever cleared: a mask that marks padding keeps its zeros).  The index of one side is exact:
+ *   pair_keys   int64 [n_pair]       sorted unique  kept * n_relation + relation
+ *   pair_off    int64 [n_pair + 1]   offsets into
+ *   completions int32                sorted unique completions of each pair
+ * side == NULL: every row is looked up in the first index (the second is not read); side uint8 [n_row]: rows with
+ * side 0 take the first index, the others the second, and both must be given.
+ * Candidates: row i reads candidate row cand_row[i] (cand_row NULL: i; ld_cand == 0: one row shared by all) of
+ * n_cand_row rows, ld_cand apart; column j of it sits at  (j / cols_per_block) * block_stride + j % cols_per_block
+ * (cols_per_block <= 0: one block, a plain row).
+ * With local_to_global (int32 [n_map_shard, ld_map]) candidates are local rows - column j of shard cand_shard, or
+ * of shard j / cols_per_block when cand_shard < 0 - and so is kept[i] where kept_shard (nullable) has
+ * kept_shard[i] >= 0; both are translated in the kernel.  An id outside the table it indexes is never loaded
+ * through: its pairs count as unknown.  n_row == 0 or n_col == 0: nothing is written. */
+int bess_known_triple_mask(const int64_t* pair_keys, const int64_t* pair_off, int64_t n_pair,
+                           const int32_t* completions, const int64_t* pair_keys2, const int64_t* pair_off2,
+                           int64_t n_pair2, const int32_t* completions2, const int32_t* kept,
+                           const int32_t* kept_shard, const int32_t* relation, const uint8_t* side,
+                           int64_t n_row, int64_t n_relation, const int32_t* cand, int64_t n_col,
+                           int64_t ld_cand, int64_t n_cand_row, const int32_t* cand_row,
+                           int64_t cols_per_block, int64_t block_stride, int32_t cand_shard,
+                           const int32_t* local_to_global, int64_t ld_map, int64_t n_map_shard, uint8_t* mask,
+                           int64_t ld_mask, int32_t and_into, void* stream);
+
 /* `RandomShardedBatchSampler.sample_triples` (batch_sampler.py:373-399):
  *   out[f] = offsets[b] + rng.integers(1 << 63, size=n_out)[f] % counts[b],
  *   b = (f / inner) % n_bucket   (out flat over [n_step, buckets..., inner]) */
