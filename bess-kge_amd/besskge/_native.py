@@ -201,6 +201,8 @@ SIGNATURES = {
     "bess_gather_candidate_lists": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp],
     "bess_known_triple_mask": [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64,
                                _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _i32, _vp],
+    "bess_known_completions": [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp,
+                               _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "bess_comm_unique_id": [_c_u8p],
     "bess_comm_init_rank": [_i32, _i32, _c_u8p, ctypes.POINTER(_vp)],
     "bess_comm_init_all": [_i32, _c_i32p, ctypes.POINTER(_vp)],
@@ -1922,6 +1924,18 @@ def gather_candidate_lists(table_h: torch.Tensor, mask_h: Optional[torch.Tensor]
     return ent, msk
 
 
+def _index_ptrs(ix: Optional[Sequence[torch.Tensor]], name: str) -> Tuple[int, int, int, int]:
+    """(keys, offsets, n_pair, completions) of one side of a `KnownTripleFilter` index, as C arguments."""
+    if ix is None:
+        return 0, 0, 0, 0
+    keys, off, comp = ix
+    n_pair = int(keys.numel())
+    _int_tensor(keys, f"{name} keys", torch.int64)
+    _int_tensor(off, f"{name} offsets", torch.int64, n_pair + 1)
+    _int_tensor(comp, f"{name} completions", torch.int32)
+    return keys.data_ptr(), off.data_ptr(), n_pair, comp.data_ptr()
+
+
 def known_triple_mask(index: Sequence[torch.Tensor], kept: torch.Tensor, relation: torch.Tensor, cand: torch.Tensor,
                       mask: torch.Tensor, n_relation: int, index2: Optional[Sequence[torch.Tensor]] = None,
                       side: Optional[torch.Tensor] = None, kept_shard: Optional[torch.Tensor] = None,
@@ -1951,17 +1965,7 @@ def known_triple_mask(index: Sequence[torch.Tensor], kept: torch.Tensor, relatio
             raise ValueError("a `side` vector needs the index of both sides (`index2`)")
         sp = side.data_ptr()
 
-    def index_ptrs(ix: Optional[Sequence[torch.Tensor]], name: str) -> Tuple[int, int, int, int]:
-        if ix is None:
-            return 0, 0, 0, 0
-        keys, off, comp = ix
-        n_pair = int(keys.numel())
-        _int_tensor(keys, f"{name} keys", torch.int64)
-        _int_tensor(off, f"{name} offsets", torch.int64, n_pair + 1)
-        _int_tensor(comp, f"{name} completions", torch.int32)
-        return keys.data_ptr(), off.data_ptr(), n_pair, comp.data_ptr()
-
-    i1, i2 = index_ptrs(index, "index"), index_ptrs(index2, "index2")
+    i1, i2 = _index_ptrs(index, "index"), _index_ptrs(index2, "index2")
     _int_tensor(cand, "cand", torch.int32)
     if cand.dim() == 2 and n_col is None:
         n_cand_row, n_col = (int(x) for x in cand.shape)
@@ -2003,6 +2007,71 @@ def known_triple_mask(index: Sequence[torch.Tensor], kept: torch.Tensor, relatio
             ld_cand, n_cand_row, crp, cpb, stride, int(cand_shard), mp, ld_map, n_map_shard, mask.data_ptr(), ld_mask,
             int(bool(and_into)))
     return mask
+
+
+def known_completions(index: Sequence[torch.Tensor], kept: torch.Tensor, relation: torch.Tensor, n_relation: int,
+                      index2: Optional[Sequence[torch.Tensor]] = None, side: Optional[torch.Tensor] = None,
+                      kept_shard: Optional[torch.Tensor] = None, local_to_global: Optional[torch.Tensor] = None,
+                      skip: Optional[torch.Tensor] = None, keep_entity: Optional[torch.Tensor] = None,
+                      counts: Optional[torch.Tensor] = None, dst: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None, out_stride: int = 1,
+                      tag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pass of bess_known_completions over the rows (kept_i, relation_i[, side_i]) of the index of
+    `known_triple_mask`.  Count pass (`counts` int32 [rows]): counts[i] = known completions of row i that are not
+    `skip[i]` (int32 [rows], -1: none) and whose `keep_entity` byte (uint8 / bool [n_entity]) is set.  Fill pass
+    (`dst` int64 [rows], `out` int32 with a multiple of `out_stride` elements): the k-th of them, ascending, goes to
+    out.view(-1, out_stride)[dst[i] + k, -1], and with `out_stride` 2 `tag[i]` to [dst[i] + k, 0].  Returns the
+    tensor written."""
+    dev = _same_device([("kept", kept), ("relation", relation), ("side", side), ("kept_shard", kept_shard),
+                        ("local_to_global", local_to_global), ("skip", skip), ("keep_entity", keep_entity),
+                        ("counts", counts), ("dst", dst), ("out", out), ("tag", tag),
+                        *[(f"index[{k}]", t) for k, t in enumerate(index)],
+                        *[(f"index2[{k}]", t) for k, t in enumerate(index2 or ())]])
+    n_row = int(kept.numel())
+    kp = _int_tensor(kept, "kept", torch.int32)
+    rp = _int_tensor(relation, "relation", torch.int32, n_row)
+    ksp = _int_tensor(kept_shard, "kept_shard", torch.int32, n_row)
+    skp = _int_tensor(skip, "skip", torch.int32, n_row)
+    sp = 0
+    if side is not None:
+        if side.dtype not in (torch.uint8, torch.bool) or not side.is_contiguous() or side.numel() != n_row:
+            raise ValueError(f"`side` must be contiguous uint8 / bool with {n_row} entries")
+        if index2 is None:
+            raise ValueError("a `side` vector needs the index of both sides (`index2`)")
+        sp = side.data_ptr()
+
+    i1, i2 = _index_ptrs(index, "index"), _index_ptrs(index2, "index2")
+    mp, ld_map, n_map_shard = 0, 0, 0
+    if local_to_global is not None:
+        if local_to_global.dtype != torch.int32 or local_to_global.dim() != 2 or not local_to_global.is_contiguous():
+            raise ValueError("`local_to_global` must be a contiguous int32 [n_shard, rows per shard] tensor")
+        n_map_shard, ld_map = (int(x) for x in local_to_global.shape)
+        mp = local_to_global.data_ptr()
+    elif kept_shard is not None:
+        raise ValueError("`kept_shard` needs `local_to_global`")
+    kep, n_entity = 0, 0
+    if keep_entity is not None:
+        if keep_entity.dtype not in (torch.uint8, torch.bool) or not keep_entity.is_contiguous():
+            raise ValueError("`keep_entity` must be contiguous uint8 / bool")
+        kep, n_entity = keep_entity.data_ptr(), int(keep_entity.numel())
+    if (counts is None) == (dst is None and out is None):
+        raise ValueError("exactly one pass per call: `counts`, or `dst` and `out`")
+    cp = _int_tensor(counts, "counts", torch.int32, n_row)
+    dp = _int_tensor(dst, "dst", torch.int64, n_row)
+    op, n_out = 0, 0
+    if counts is None:
+        if dst is None or out is None:
+            raise ValueError("the fill pass needs `dst` and `out`")
+        if out_stride not in (1, 2) or (out_stride == 2 and tag is None):
+            raise ValueError("`out_stride` is 1, or 2 with a `tag` vector")
+        op = _int_tensor(out, "out", torch.int32)
+        if out.numel() % out_stride:
+            raise ValueError(f"`out` has {out.numel()} elements: not a multiple of out_stride {out_stride}")
+        n_out = out.numel() // out_stride
+    tp = _int_tensor(tag, "tag", torch.int32, n_row)
+    _launch("bess_known_completions", dev, *i1, *i2, kp, ksp, rp, sp, n_row, int(n_relation), mp, ld_map, n_map_shard,
+            skp, kep, n_entity, cp, dp, op, n_out, int(out_stride), tp)
+    return counts if counts is not None else out  # type: ignore[return-value]
 
 
 # --------------------------------------------------------------------------- #

@@ -10,6 +10,13 @@ candidate scores `BAD_NEGATIVE_SCORE` and falls out of the loss and its
 gradients.  `DeviceBatchSampler(..., filter_triples=...)` makes that mask for
 every sampled batch.
 
+Filtered evaluation asks the same index the other question - "list the known
+completions of this query": `completions` (two passes of
+`bess_known_completions`) returns them as a CSR pair on the device, and
+`AllScoresPipeline(..., filter_triples=KnownTripleFilter(...))` builds every
+batch's filter from it instead of comparing all queries with all filter triples
+on the host.
+
 The index is exact - no hashing: a mask is reproducible bit for bit.  One CSR
 structure per corruption side:
 
@@ -158,7 +165,108 @@ class KnownTripleFilter:
             out[rows] = ~((flat[at] == q) & (c >= 0) & (c < self.n_entity))
         return out
 
+    def completions_host(self, kept: NDArray, relation: NDArray, side: Union[int, str, NDArray],
+                         skip: Optional[NDArray] = None, keep_entity: Optional[NDArray] = None,
+                         kept_shard: Optional[NDArray] = None, local_to_global: Optional[NDArray] = None
+                         ) -> Tuple[NDArray[np.int64], NDArray[np.int32]]:
+        """The meaning of `completions`, in numpy: `ids[ptr[i]:ptr[i + 1]]` are, in ascending order, the entities
+        e such that (kept[i], relation[i], e) - read as (h, r, t) where side is 0 / "t" and as (t, r, h) where it
+        is 1 / "h" - is a known triple, without `skip[i]` (-1: none) and, with `keep_entity` (bool [n_entity]),
+        without the entities it does not mark.  With `local_to_global` ([n_shard, rows per shard]) `kept[i]` is a
+        local row of shard `kept_shard[i]` where that is >= 0.  A row whose kept id is negative, or whose kept id,
+        shard, local row or relation is outside its range, has no completions."""
+        kept = np.asarray(kept).astype(np.int64).reshape(-1)
+        relation = np.asarray(relation).astype(np.int64).reshape(-1)
+        if isinstance(side, (int, str)):
+            side = np.full(kept.shape, _SIDES[side], dtype=np.uint8)
+        side = np.asarray(side).reshape(-1) != 0
+        ok = kept >= 0
+        if kept_shard is not None:
+            if local_to_global is None:
+                raise ValueError("`kept_shard` needs `local_to_global`")
+            table = np.asarray(local_to_global)
+            shard = np.asarray(kept_shard).astype(np.int64).reshape(-1)
+            local = shard >= 0
+            ok &= ~local | ((shard < table.shape[0]) & (kept < table.shape[1]))
+            at = local & ok
+            kept = np.where(at, table[np.where(at, shard, 0), np.where(at, kept, 0)].astype(np.int64), kept)
+        ok &= (kept < self.n_entity) & (relation >= 0) & (relation < self.n_relation_type)
+        lists = []
+        for i in range(kept.shape[0]):
+            keys, off, comp = self.index_host[int(side[i])]
+            row = comp[:0]
+            if ok[i]:
+                key = kept[i] * self.n_relation_type + relation[i]
+                pair = int(np.searchsorted(keys, key))
+                if pair < keys.shape[0] and keys[pair] == key:
+                    row = comp[off[pair]: off[pair + 1]]
+            if skip is not None:
+                row = row[row != int(np.asarray(skip).reshape(-1)[i])]
+            if keep_entity is not None:
+                row = row[np.asarray(keep_entity).reshape(-1)[row] != 0]
+            lists.append(row)
+        ptr = np.zeros(kept.shape[0] + 1, dtype=np.int64)
+        ptr[1:] = np.cumsum([len(x) for x in lists])
+        return ptr, np.concatenate(lists + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
+
     # ---------------------------------------------------------------- device
+    def _sides(self, side: Union[int, str, torch.Tensor]) -> tuple:
+        """(first index, second index or None, `side` vector or None) as the kernels take them."""
+        if self.index is None:
+            raise RuntimeError("the index is on the host only: call to(device) first")
+        if isinstance(side, torch.Tensor):
+            return self.index[SIDE_TAIL], self.index[SIDE_HEAD], side
+        return self.index[_SIDES[side]], None, None
+
+    def completions(self, kept: torch.Tensor, relation: torch.Tensor, side: Union[int, str, torch.Tensor],
+                    skip: Optional[torch.Tensor] = None, keep_entity: Optional[torch.Tensor] = None,
+                    kept_shard: Optional[torch.Tensor] = None, local_to_global: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`completions_host` on the device (`bess_known_completions`): a count pass, a `cumsum` and a fill pass
+        over the same rows; the one host read - the total - sizes `ids`.
+
+        :param kept: int32 [rows]; :param relation: int32 [rows]; :param side: as for `mask`.
+        :param skip: int32 [rows], an entity left out of every row's list (-1: none).
+        :param keep_entity: bool / uint8 [n_entity], the only entities listed.
+        :param kept_shard / local_to_global: as for `mask`.
+        :return: (ptr int64 [rows + 1], ids int32 [ptr[-1]]) on the device.
+        """
+        query = dict(skip=skip, keep_entity=keep_entity, kept_shard=kept_shard, local_to_global=local_to_global)
+        counts = self.count_completions(kept, relation, side, **query)
+        ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=kept.device)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        ids = torch.empty(int(ptr[-1]), dtype=torch.int32, device=kept.device)
+        if ids.numel():
+            self.fill_completions(kept, relation, side, ptr[:-1], ids, **query)
+        return ptr, ids
+
+    def count_completions(self, kept: torch.Tensor, relation: torch.Tensor, side: Union[int, str, torch.Tensor],
+                          **query: Optional[torch.Tensor]) -> torch.Tensor:
+        """The count pass of `completions` alone: int32 [rows], the length of every row's list (`query`: `skip`,
+        `keep_entity`, `kept_shard`, `local_to_global`)."""
+        from besskge import _native as nat
+
+        first, second, side_t = self._sides(side)
+        keep_entity = query.get("keep_entity")
+        if keep_entity is not None and keep_entity.numel() != self.n_entity:
+            raise ValueError(f"`keep_entity` has {keep_entity.numel()} entries, the index {self.n_entity} entities")
+        counts = torch.empty(int(kept.numel()), dtype=torch.int32, device=kept.device)
+        return nat.known_completions(first, kept, relation, self.n_relation_type, index2=second, side=side_t,
+                                     counts=counts, **query)
+
+    def fill_completions(self, kept: torch.Tensor, relation: torch.Tensor, side: Union[int, str, torch.Tensor],
+                         dst: torch.Tensor, out: torch.Tensor, tag: Optional[torch.Tensor] = None,
+                         **query: Optional[torch.Tensor]) -> torch.Tensor:
+        """The fill pass of `completions` alone, for callers with a layout of their own: row i's list starts at
+        entry `dst[i]` (int64 [rows]) of `out` (int32); with `tag` (int32 [rows]) an entry is the pair
+        (tag[i], entity) - `out` is [entries, 2] then.  Same rows and `query` as the count pass that sized `out`;
+        what `dst` leaves between the lists is not touched."""
+        from besskge import _native as nat
+
+        first, second, side_t = self._sides(side)
+        return nat.known_completions(first, kept, relation, self.n_relation_type, index2=second, side=side_t, dst=dst,
+                                     out=out, out_stride=1 if tag is None else 2, tag=tag, **query)
+
     def mask(self, kept: torch.Tensor, relation: torch.Tensor, side: Union[int, str, torch.Tensor],
              candidates: torch.Tensor, out: Optional[torch.Tensor] = None, and_into: bool = False,
              cand_row: Optional[torch.Tensor] = None, local_to_global: Optional[torch.Tensor] = None,
@@ -181,10 +289,9 @@ class KnownTripleFilter:
             local row of shard `kept_shard[i]` where that is >= 0.
         :return: bool [rows, columns] (or `out`).
         """
-        if self.index is None:
-            raise RuntimeError("the index is on the host only: call to(device) first")
         from besskge import _native as nat
 
+        first, second, side_t = self._sides(side)
         n_row = int(kept.numel())
         if candidates.dim() == 1:
             candidates = candidates[None, :]
@@ -194,10 +301,6 @@ class KnownTripleFilter:
             if and_into:
                 raise ValueError("`and_into` needs the mask to combine with (`out`)")
             out = torch.empty((n_row, n_col), dtype=torch.bool, device=kept.device)
-        if isinstance(side, torch.Tensor):
-            first, second, side_t = self.index[SIDE_TAIL], self.index[SIDE_HEAD], side
-        else:
-            first, second, side_t = self.index[_SIDES[side]], None, None
         nat.known_triple_mask(first, kept, relation, candidates, out, self.n_relation_type, index2=second, side=side_t,
                               kept_shard=kept_shard, n_col=n_col, ld_cand=0 if shared else n_col,
                               n_cand_row=int(candidates.shape[0]), cand_row=cand_row,

@@ -20,6 +20,7 @@ from besskge import _native as nat
 from besskge import runtime
 from besskge.batch_sampler import ShardedBatchSampler
 from besskge.collectives import ReplicaGroup
+from besskge.negative_filter import SIDE_HEAD, SIDE_TAIL, KnownTripleFilter
 from besskge.negative_sampler import PlaceholderNegativeSampler
 from besskge.query import KERNEL_LIST_MAX, AllScoresBESS, topk_merge
 from besskge.scoring import BaseScoreFunction
@@ -104,7 +105,7 @@ class AllScoresPipeline(torch.nn.Module):
         corruption_scheme: str,
         score_fn: BaseScoreFunction,
         evaluation: Optional[Any] = None,
-        filter_triples: Optional[List[Union[torch.Tensor, NDArray[np.int32]]]] = None,
+        filter_triples: Union[None, KnownTripleFilter, List[Union[torch.Tensor, NDArray[np.int32]]]] = None,
         candidate_ents: Optional[Union[torch.Tensor, NDArray[np.int32]]] = None,
         return_scores: bool = False,
         return_topk: bool = False,
@@ -115,13 +116,16 @@ class AllScoresPipeline(torch.nn.Module):
         device: Optional[torch.device] = None,
         fused_ranks: bool = True,
         fused_topk: bool = True,
+        device_filter: bool = False,
     ) -> None:
         """
         :param batch_sampler: sampler over "h_shard" / "t_shard" partitioned queries.
         :param corruption_scheme: "t" scores (h, r, ?), "h" scores (?, r, t).
         :param score_fn: trained scoring function.
         :param evaluation: `besskge.metric.Evaluation`.
-        :param filter_triples: triples (global ids) whose completions are filtered out.
+        :param filter_triples: triples (global ids) whose completions are filtered out: a list of [n, 3] arrays,
+            or a `KnownTripleFilter` built over the same global ids - the filter of every sampler batch is then
+            enumerated on the device from that index (`device_filter`).
         :param candidate_ents: global ids of the only entities to consider.
         :param return_scores: return the filtered `[queries, n_entity]` scores (host memory!).
         :param return_topk: return the k best global ids per query (after filtering).
@@ -146,6 +150,10 @@ class AllScoresPipeline(torch.nn.Module):
             path's order, whose columns are entity ids.  The same `topk_global_id` as the matrix path under the
             condition given for `fused_ranks`; scorers with a kernel descriptor and k <= 128.
             `fused_topk=False` forces the matrix path.
+        :param device_filter: build a `KnownTripleFilter` once from a list-valued `filter_triples` and make every
+            batch's filter on the device from it (`bess_known_completions`): the same pairs as the host path
+            (`utils.get_entity_filter` + `rank_filter_pairs`), whose cost is queries x filter triples per batch.
+            Neither `return_triple_idx=True` on the sampler nor a host copy of its triples is needed then.
         """
         super().__init__()
         if not (evaluation or return_scores):
@@ -172,7 +180,20 @@ class AllScoresPipeline(torch.nn.Module):
             device=device)
         sharding = self.bess_module.sharding
         self.filter_triples: Optional[torch.Tensor] = None
-        if filter_triples:
+        self.known_filter: Optional[KnownTripleFilter] = None
+        if isinstance(filter_triples, KnownTripleFilter) or (filter_triples and device_filter):
+            flt = filter_triples
+            if not isinstance(flt, KnownTripleFilter):
+                arrays = [t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in flt]
+                flt = KnownTripleFilter(arrays, sharding.n_entity, int(score_fn.relation_embedding.shape[0]))
+            elif flt.n_entity != sharding.n_entity:
+                raise ValueError(f"filter_triples indexes {flt.n_entity} entities, the sharding has {sharding.n_entity}")
+            dev = self.runner.device
+            self.known_filter = flt.to(dev)
+            self._local_to_global = torch.from_numpy(
+                np.ascontiguousarray(sharding.shard_and_idx_to_entity)).to(device=dev, dtype=torch.int32)
+            self._slot_tables: Dict[Any, Any] = {}
+        elif filter_triples:
             # global ids of the sampler's (locally indexed) triples
             col = 0 if batch_sampler.triple_partition_mode == "h_shard" else 2
             glob = np.copy(batch_sampler.triples)
@@ -197,6 +218,8 @@ class AllScoresPipeline(torch.nn.Module):
             self.candidate_mask = torch.from_numpy(np.setdiff1d(np.arange(sharding.n_entity), candidate_ents))
             self._is_candidate = torch.ones(sharding.n_entity, dtype=torch.bool)
             self._is_candidate[self.candidate_mask] = False
+            if self.known_filter is not None:
+                self._is_candidate_dev = self._is_candidate.to(self.runner.device)
         # column order of the assembled scores -> global entity id (first occurrence of every entity)
         ws, n_step, M = self.window_size, self.bess_module.n_step, sharding.max_entity_per_shard
         cols = []
@@ -205,9 +228,58 @@ class AllScoresPipeline(torch.nn.Module):
             cols.append(sharding.shard_and_idx_to_entity[:, ent_slice].flatten())
         self._first = torch.from_numpy(np.unique(np.concatenate(cols), return_index=True)[1])
 
+    def _device_queries(self, batch: Dict[str, torch.Tensor], triple_mask: torch.Tensor) -> Dict[str, Any]:
+        """The sampler batch as rows of `KnownTripleFilter.completions`, one per slot of the flat [rows * shard_bs]
+        batch: the entity that stays is a local row of the slot's shard (translated in the kernel), slots that the
+        triple mask drops get -1 and so list nothing."""
+        dev = self.runner.device
+        rows, shard_bs = triple_mask.flatten(end_dim=1).shape  # [micro-batches * n_shard, shard_bs]
+        if (rows, shard_bs) not in self._slot_tables:
+            slot = torch.arange(rows * shard_bs, device=dev)
+            n = self.bess_module.sharding.n_shard
+            self._slot_tables[(rows, shard_bs)] = (((slot // shard_bs) % n).to(torch.int32),  # the slot's shard
+                                                   (slot % shard_bs).to(torch.int32))  # its place in the micro-batch
+        shard, place = self._slot_tables[(rows, shard_bs)]
+        kept = batch["head" if self.corruption_scheme == "t" else "tail"]
+        kept = torch.where(triple_mask.flatten(), kept.flatten(), torch.full_like(kept.flatten(), -1))
+        return dict(kept=kept.to(dev), relation=batch["relation"].flatten().to(dev), kept_shard=shard, place=place,
+                    side=SIDE_TAIL if self.corruption_scheme == "t" else SIDE_HEAD)
+
+    def _device_filter_pairs(self, batch: Dict[str, torch.Tensor], ground_truth: Optional[torch.Tensor],
+                             triple_mask: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
+        """`rank_filter_pairs(get_entity_filter(...))` of one sampler batch, element for element, made on the device
+        from the index: a count pass sizes the padded [rows, P, 2] tensor (one host read, for P), the fill pass
+        writes every slot's (place, entity) pairs where the exclusive sum of the counts of its row puts them -
+        slots ascending, entities ascending inside a slot: the order `torch.unique` gives the host path."""
+        flt = self.known_filter
+        assert flt is not None
+        q = self._device_queries(batch, triple_mask)
+        dev = q["kept"].device
+        rows, shard_bs = triple_mask.flatten(end_dim=1).shape
+        place = q.pop("place")
+        q["local_to_global"] = self._local_to_global
+        if ground_truth is not None:
+            q["skip"] = ground_truth.flatten().to(device=dev, dtype=torch.int32)
+        if self._is_candidate is not None:
+            q["keep_entity"] = self._is_candidate_dev
+        counts = flt.count_completions(**q).view(rows, shard_bs).long()
+        P = int(counts.sum(1).max())  # the batch's one host read
+        filt = torch.full((rows, max(P, 1), 2), -1, dtype=torch.int32, device=dev)
+        if P:
+            first = torch.cumsum(counts, 1) - counts + torch.arange(rows, device=dev)[:, None] * P
+            flt.fill_completions(dst=first.flatten(), out=filt, tag=place, **q)
+        kept_slots = triple_mask.flatten().nonzero().flatten().to(dev)  # (found on the host: no second read)
+        return filt, counts.flatten()[kept_slots]
+
     def _filter_pairs(self, ground_truth: Optional[torch.Tensor], triple_mask: torch.Tensor,
-                      triple_id: Optional[torch.Tensor]) -> "Optional[tuple[torch.Tensor, torch.Tensor]]":
-        """(`rank_filter` input, filtered completions per kept triple) of one sampler batch; None without a filter."""
+                      triple_id: Optional[torch.Tensor], batch: Optional[Dict[str, torch.Tensor]] = None
+                      ) -> "Optional[tuple[torch.Tensor, torch.Tensor]]":
+        """(`rank_filter` input, filtered completions per kept triple) of one sampler batch; None without a filter.
+        `batch`: the sampler's index tensors, [micro-batches, n_shard, shard_bs] or flattened to rows (the device
+        filter reads them)."""
+        if self.known_filter is not None:
+            assert batch is not None
+            return self._device_filter_pairs(batch, ground_truth, triple_mask)
         if self.filter_triples is None:
             return None
         if triple_id is None:
@@ -230,9 +302,9 @@ class AllScoresPipeline(torch.nn.Module):
         keep = triple_mask.flatten()
         extra = dict(rank_truth=ground_truth.flatten(end_dim=1).to(torch.int32))
         n_masked = torch.ones(int(keep.sum()), dtype=torch.int64)  # entries the reference sets to -inf, per kept row
-        if self.filter_triples is not None:
-            filt, per_kept = pairs if pairs is not None else self._filter_pairs(ground_truth, triple_mask, triple_id)
-            n_masked += per_kept
+        if self.filter_triples is not None or self.known_filter is not None:
+            filt, per_kept = pairs if pairs is not None else self._filter_pairs(ground_truth, triple_mask, triple_id, inp)
+            n_masked = n_masked.to(per_kept.device) + per_kept
             extra["rank_filter"] = filt
         if self._is_candidate is not None:
             # entities outside the subset are -inf in the reference's matrix too (pipeline.py:247-250): they tie
@@ -281,7 +353,7 @@ class AllScoresPipeline(torch.nn.Module):
             inp = {k: v.flatten(end_dim=1) for k, v in batch.items()}
             if self.fused_ranks or self.fused_topk:
                 # nothing of this batch needs the score matrix - unless a product leaves the fp16 range
-                pairs = self._filter_pairs(ground_truth, triple_mask, triple_id)
+                pairs = self._filter_pairs(ground_truth, triple_mask, triple_id, batch)
                 r = t = None
                 if self.fused_ranks:
                     assert ground_truth is not None, "Evaluation requires providing ground truth entities"
@@ -310,7 +382,14 @@ class AllScoresPipeline(torch.nn.Module):
             if ground_truth is not None:
                 truth = ground_truth[triple_mask].to(dev).long()
                 true_scores = sc[rows, truth].clone()
-            if self.filter_triples is not None:
+            if self.known_filter is not None:
+                q = self._device_queries(batch, triple_mask)
+                ptr, ents = self.known_filter.completions(q["kept"][keep], q["relation"][keep], q["side"],
+                                                          kept_shard=q["kept_shard"][keep],
+                                                          local_to_global=self._local_to_global)
+                of_row = torch.repeat_interleave(rows, ptr[1:] - ptr[:-1], output_size=ents.numel())
+                sc[of_row, ents.long()] = -torch.inf
+            elif self.filter_triples is not None:
                 if triple_id is None:
                     raise ValueError("filtering needs a batch sampler with return_triple_idx=True")
                 flt = get_entity_filter(self.triples[triple_id[triple_mask]], self.filter_triples,

@@ -124,6 +124,7 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_lookup_triples),
     BESS_PLAN_FN(bess_gather_candidate_lists),
     BESS_PLAN_FN(bess_known_triple_mask),
+    BESS_PLAN_FN(bess_known_completions),
     BESS_PLAN_FN(bess_alltoall),
     BESS_PLAN_FN(bess_allgather),
     BESS_PLAN_FN(bess_allreduce_sum_f32),

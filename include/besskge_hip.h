@@ -825,6 +825,29 @@ int bess_known_triple_mask(const int64_t* pair_keys, const int64_t* pair_off, in
                            const int32_t* local_to_global, int64_t ld_map, int64_t n_map_shard, uint8_t* mask,
                            int64_t ld_mask, int32_t and_into, void* stream);
 
+/* Filtered evaluation: the known completions of every query row, enumerated from the index of
+ * bess_known_triple_mask (same index arrays, same query description - kept / kept_shard + local_to_global /
+ * relation / side / n_relation - and the same validity rules: a row with kept < 0, or with a relation, shard or
+ * local row outside its table, has no completions and nothing is loaded through the bad id).  Two per-call
+ * filters on what is emitted (either may be NULL): skip int32 [n_row] - an entity left out of row i's list (the
+ * query's true completion; -1: none); keep_entity uint8 [n_entity] - only entities with a non-zero byte pass.
+ * Exactly one of two passes per call:
+ *   count  (counts != NULL; dst == out == NULL): counts[i] = completions of row i's pair that pass both filters.
+ *   fill   (dst and out != NULL; counts == NULL): the k-th passing completion of row i, in ascending entity id,
+ *          goes to out[(dst[i] + k) * out_stride + (out_stride - 1)]; with out_stride == 2 (tag int32 [n_row]
+ *          required) tag[i] goes to out[(dst[i] + k) * 2].  out_stride is 1 or 2; nothing else of out is
+ *          touched, and an entry at or past n_out (the entries `out` holds) or below 0 is dropped, not written.
+ *          dst int64 [n_row] is the caller's exclusive prefix sum of the counts (plus any gaps it wants).
+ * n_row == 0: nothing is read or written. */
+int bess_known_completions(const int64_t* pair_keys, const int64_t* pair_off, int64_t n_pair,
+                           const int32_t* completions, const int64_t* pair_keys2, const int64_t* pair_off2,
+                           int64_t n_pair2, const int32_t* completions2, const int32_t* kept,
+                           const int32_t* kept_shard, const int32_t* relation, const uint8_t* side,
+                           int64_t n_row, int64_t n_relation, const int32_t* local_to_global, int64_t ld_map,
+                           int64_t n_map_shard, const int32_t* skip, const uint8_t* keep_entity,
+                           int64_t n_entity, int32_t* counts, const int64_t* dst, int32_t* out, int64_t n_out,
+                           int64_t out_stride, const int32_t* tag, void* stream);
+
 /* `RandomShardedBatchSampler.sample_triples` (batch_sampler.py:373-399):
  *   out[f] = offsets[b] + rng.integers(1 << 63, size=n_out)[f] % counts[b],
  *   b = (f / inner) % n_bucket   (out flat over [n_step, buckets..., inner]) */
