@@ -870,9 +870,14 @@ extern "C" int bess_neg_score_pertriple_fwd_dq_masked(const bess_model_desc* d, 
     BESS_REQUIRE(pos || l->kind == BESS_LOSS_LOGSIGMOID, "neg_score_pertriple_fwd_dq: this loss needs the positive scores");
     FuseArgs f = fuse_args(l, pos, state_ml, state_acc);
     if (mask) {
-        BESS_REQUIRE(mask_cols > 0 && mask_cols <= n_neg && (mask_rows == 1 || mask_rows == n_query),
-                     "neg_score_pertriple_fwd_dq_masked: mask [%lld, %lld] for %lld queries x %lld negatives",
-                     (long long)mask_rows, (long long)mask_cols, (long long)n_query, (long long)n_neg);
+        BESS_REQUIRE(mask_rows > 0 && mask_cols > 0, "neg_score_pertriple_fwd_dq_masked: mask [%lld, %lld]",
+                     (long long)mask_rows, (long long)mask_cols);
+        // (a mask this pass does not apply - K7's head / tail halves, mask_rows == 2, or more columns than scores - is
+        // "not built", not a bad call: the caller masks with bess_mask_scores and takes the two-pass form)
+        if (mask_cols > n_neg || (mask_rows != 1 && mask_rows != n_query))
+            return fail(BESS_EUNSUPPORTED,
+                        "neg_score_pertriple_fwd_dq_masked: mask [%lld, %lld] for %lld queries x %lld negatives",
+                        (long long)mask_rows, (long long)mask_cols, (long long)n_query, (long long)n_neg);
         f.mask = mask;
         f.mask_rows = mask_rows;
         f.mask_cols = static_cast<int>(mask_cols);

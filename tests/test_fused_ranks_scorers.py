@@ -92,6 +92,9 @@ CASES = [  # name, p, dtype, indexed, d
     ("InterHT", 1, torch.float16, True, 52),
     ("BoxE", 1, torch.float32, False, 64),
     ("BoxEnt", 2, torch.float16, True, 64),
+    ("PairRE", 2, torch.float16, False, 128),   # the table form at p = 2: one part, both table types ...
+    ("PairRE", 2, torch.float32, True, 64),
+    ("TranS", 2, torch.float16, True, 64),      # ... and two parts on an fp16 table (tests/test_fused_step_kernels.py)
 ]
 
 
