@@ -223,6 +223,22 @@ __device__ __forceinline__ bool last_workgroup_ticket(int32_t* counters) {
     __hip_atomic_store(counters, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return true;
 }
+// The last workgroup's share of the fixed-order sum: thread `tid` of `threads` adds the terms i = tid + threads * j
+// of p[0 .. n), j ascending, starting from 0 (the caller's LDS tree over the threads follows).  The terms come in
+// groups of 16 agent-scope loads issued before the first is added: the sum is one memory round trip per group, not
+// one per term - the loads are served beyond L2 while every other CU stands idle.  Terms past n load p[n - 1] (a
+// valid address: a branch around a load would wait for it alone) and are not added.
+__device__ __forceinline__ float strided_sum_agent(const float* p, int64_t n, int tid, int threads) {
+    float acc = 0.f;
+    for (int64_t i0 = tid; i0 < n; i0 += 16ll * threads) {
+        float v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = load_agent(p + min(i0 + static_cast<int64_t>(j) * threads, n - 1));
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc = (i0 + static_cast<int64_t>(j) * threads < n) ? acc + v[j] : acc;
+    }
+    return acc;
+}
 
 
 // sgn(x - y) for operands pre-scaled by 2^100 (exact: power of two): the

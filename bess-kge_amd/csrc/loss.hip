@@ -68,9 +68,7 @@ __global__ __launch_bounds__(256) void k_loss_rows(bess_loss_desc l, const float
     if (threadIdx.x == 0) last = last_workgroup_ticket(counter);
     __syncthreads();
     if (!last) return;
-    float acc = 0.f;
-    for (int64_t i = threadIdx.x; i < n_triple; i += 256) acc += load_agent(row_loss + i);
-    part[threadIdx.x] = acc;
+    part[threadIdx.x] = strided_sum_agent(row_loss, n_triple, threadIdx.x, 256);
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
         if (threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];

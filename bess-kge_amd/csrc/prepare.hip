@@ -31,48 +31,187 @@ struct TripleArgs {
 };
 
 // ------------------------------------------------------------------ forward
-template <typename T, int SCORER>
-__device__ __forceinline__ void triple_fwd_body(const TripleArgs& a, int64_t s, int lane, float* __restrict__ out) {
-    const T* h = row_ptr(static_cast<const T*>(a.head_base), a.head_idx, s, a.W);
-    const T* t = row_ptr(static_cast<const T*>(a.tail_base), a.tail_idx, s, a.W);
-    const T* r = static_cast<const T*>(a.rel_table) + static_cast<int64_t>(a.rel_idx[s]) * a.Wr;
-    float acc = 0.f;
+// The arithmetic of one lane element, stated once for the looped and the register forms below.  TransE / DistMult:
+// one scalar of each row (the "1" operands are unused); RotatE / ComplEx: the pair (re at e, im at d + e) - RotatE's
+// relation is the phase r0 alone.
+constexpr bool is_complex_scorer(int scorer) { return scorer == BESS_ROTATE || scorer == BESS_COMPLEX; }
+
+// the term of the positive score that element adds to the lane's sum
+template <int SCORER>
+__device__ __forceinline__ float triple_term(float hr, float hi, float tr, float ti, float r0, float r1, int norm_p) {
     if (SCORER == BESS_TRANSE) {
-        for (int e = lane; e < a.W; e += 64) {
-            const float x = to_f32(h[e]) + to_f32(r[e]) - to_f32(t[e]);
-            acc += (a.norm_p == 1) ? fabsf(x) : lp_term(x, static_cast<float>(a.norm_p));
-        }
+        const float x = hr + r0 - tr;
+        return (norm_p == 1) ? fabsf(x) : lp_term(x, static_cast<float>(norm_p));
     } else if (SCORER == BESS_DISTMULT) {
-        for (int e = lane; e < a.W; e += 64) acc += to_f32(h[e]) * to_f32(r[e]) * to_f32(t[e]);
+        return hr * r0 * tr;
     } else {
-        const int d = a.W / 2;
-        for (int e = lane; e < d; e += 64) {
-            const float hr = to_f32(h[e]), hi = to_f32(h[d + e]);
-            const float tr = to_f32(t[e]), ti = to_f32(t[d + e]);
-            float rr, ri;
-            if (SCORER == BESS_ROTATE) {
-                const float ph = to_f32(r[e]);
-                rr = cosf(ph);
-                ri = sinf(ph);
-            } else {
-                rr = to_f32(r[e]);
-                ri = to_f32(r[d + e]);
+        float rr, ri;
+        if (SCORER == BESS_ROTATE) {
+            rr = cosf(r0);
+            ri = sinf(r0);
+        } else {
+            rr = r0;
+            ri = r1;
+        }
+        const float qr = hr * rr - hi * ri;
+        const float qi = hr * ri + hi * rr;
+        if (SCORER == BESS_ROTATE) {
+            const float xr = qr - tr, xi = qi - ti;
+            return (norm_p == 1) ? (fabsf(xr) + fabsf(xi))
+                                 : (lp_term(xr, static_cast<float>(norm_p)) + lp_term(xi, static_cast<float>(norm_p)));
+        }
+        return qr * tr + qi * ti;
+    }
+}
+
+// that element of the query row (o1: the imaginary part, complex scorers only)
+template <int SCORER>
+__device__ __forceinline__ void query_elem(float xr, float xi, float r0, float r1, bool tail, float& o0, float& o1) {
+    if (SCORER == BESS_TRANSE) {
+        o0 = tail ? (xr + r0) : (xr - r0);
+    } else if (SCORER == BESS_DISTMULT) {
+        o0 = xr * r0;
+    } else {
+        float rr, ri;
+        if (SCORER == BESS_ROTATE) {
+            // heads: rotate the tail by -r (scoring.py:446-448)
+            const float ph = tail ? r0 : -r0;
+            rr = cosf(ph);
+            ri = sinf(ph);
+        } else {
+            // heads: conjugate relation times tail (scoring.py:928-932)
+            rr = r0;
+            ri = tail ? r1 : -r1;
+        }
+        o0 = xr * rr - xi * ri;
+        o1 = xr * ri + xi * rr;
+    }
+}
+
+__device__ __forceinline__ float finish_triple_score(int scorer, float acc, int norm_p) {
+    acc = wave_allreduce_sum(acc);
+    if (scorer == BESS_TRANSE || scorer == BESS_ROTATE)
+        acc = -((norm_p == 1) ? acc : lp_root(acc, static_cast<float>(norm_p)));
+    return acc;
+}
+
+// Row id of entry s of a launch: idx[s], or s itself where the rows come without a list.  The load is unconditional
+// (from `other`, a list every launch has, when idx is NULL): a branch around it would put a wait of its own between
+// this index load and the next, and the indices of an entry are to be in flight together.
+__device__ __forceinline__ int64_t row_id(const int32_t* __restrict__ idx, const int32_t* __restrict__ other, int64_t s) {
+    const int32_t v = (idx ? idx : other)[s];
+    return idx ? static_cast<int64_t>(v) : s;
+}
+
+// Rows of at most 16 elements per lane (W <= 1024) are taken whole into registers: every load of the head, tail and
+// relation rows is issued before the first is used, so a wave pays one memory round trip for its rows instead of one
+// per 64 elements (a wave per triple, all waves resident: the launch lasts as long as one wave's chain of round
+// trips).  The element a lane holds in trip k is e = lane + 64 k, as in the loops that wider rows keep, and its sum
+// adds the terms in the same ascending order.  NK trips are unrolled; lanes past the end of the row load its last
+// element (a valid address, no branch around a load) and neither store nor add.
+// QUERY && TRIPLE: the query is built from h (tail corruption) or t; QUERY alone: from h; the head and relation rows
+// are then read once for both results.
+constexpr int REG_ROW_MAX = 1024;
+template <typename T, int SCORER, int NK, bool QUERY, bool TRIPLE>
+__device__ __forceinline__ void fwd_rows_in_registers(const T* __restrict__ h, const T* __restrict__ t,
+                                                      const T* __restrict__ r, int W, int norm_p, bool tail, int lane,
+                                                      float* __restrict__ o, float* __restrict__ out_s) {
+    constexpr bool CPLX = is_complex_scorer(SCORER);
+    constexpr bool R2 = SCORER == BESS_COMPLEX;  // (RotatE's relation row: d phases)
+    const int lim = CPLX ? W / 2 : W;
+    float h0[NK], h1[NK], t0[NK], t1[NK], r0[NK], r1[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int e = min(lane + 64 * k, lim - 1);
+        h0[k] = to_f32(h[e]);
+        h1[k] = CPLX ? to_f32(h[lim + e]) : 0.f;
+        t0[k] = TRIPLE ? to_f32(t[e]) : 0.f;
+        t1[k] = (TRIPLE && CPLX) ? to_f32(t[lim + e]) : 0.f;
+        r0[k] = to_f32(r[e]);
+        r1[k] = R2 ? to_f32(r[lim + e]) : 0.f;
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int e = lane + 64 * k;
+        const bool live = e < lim;
+        if (QUERY) {
+            const bool from_h = !TRIPLE || tail;
+            float q0, q1 = 0.f;
+            query_elem<SCORER>(from_h ? h0[k] : t0[k], from_h ? h1[k] : t1[k], r0[k], r1[k], tail, q0, q1);
+            if (live) {
+                o[e] = q0;
+                if (CPLX) o[lim + e] = q1;
             }
-            const float qr = hr * rr - hi * ri;
-            const float qi = hr * ri + hi * rr;
-            if (SCORER == BESS_ROTATE) {
-                const float xr = qr - tr, xi = qi - ti;
-                acc += (a.norm_p == 1) ? (fabsf(xr) + fabsf(xi))
-                                       : (lp_term(xr, static_cast<float>(a.norm_p)) + lp_term(xi, static_cast<float>(a.norm_p)));
-            } else {
-                acc += qr * tr + qi * ti;
-            }
+        }
+        if (TRIPLE) {
+            const float term = triple_term<SCORER>(h0[k], h1[k], t0[k], t1[k], r0[k], r1[k], norm_p);
+            acc = live ? acc + term : acc;
         }
     }
-    acc = wave_allreduce_sum(acc);
-    if (SCORER == BESS_TRANSE || SCORER == BESS_ROTATE)
-        acc = -((a.norm_p == 1) ? acc : lp_root(acc, static_cast<float>(a.norm_p)));
-    if (lane == 0) out[s] = acc;
+    if (TRIPLE) {
+        acc = finish_triple_score(SCORER, acc, norm_p);
+        if (lane == 0) *out_s = acc;
+    }
+}
+// ... with the trips a row of W scalars needs (wave-uniform: W is a launch argument), rounded up to 4, 8 or 16
+template <typename T, int SCORER, bool QUERY, bool TRIPLE>
+__device__ __forceinline__ void fwd_rows_by_trips(const T* __restrict__ h, const T* __restrict__ t, const T* __restrict__ r,
+                                                  int W, int norm_p, bool tail, int lane, float* __restrict__ o,
+                                                  float* __restrict__ out_s) {
+    const int lim = is_complex_scorer(SCORER) ? W / 2 : W;
+    if (lim <= 256) {
+        fwd_rows_in_registers<T, SCORER, 4, QUERY, TRIPLE>(h, t, r, W, norm_p, tail, lane, o, out_s);
+    } else if (is_complex_scorer(SCORER) || lim <= 512) {
+        fwd_rows_in_registers<T, SCORER, 8, QUERY, TRIPLE>(h, t, r, W, norm_p, tail, lane, o, out_s);
+    } else {
+        if constexpr (!is_complex_scorer(SCORER))
+            fwd_rows_in_registers<T, SCORER, 16, QUERY, TRIPLE>(h, t, r, W, norm_p, tail, lane, o, out_s);
+    }
+}
+
+// the looped forms, for wider rows: 64 elements per trip, each trip waiting for its own loads
+template <typename T, int SCORER>
+__device__ __forceinline__ void triple_fwd_loops(const T* __restrict__ h, const T* __restrict__ t, const T* __restrict__ r,
+                                                 int W, int norm_p, int lane, float* __restrict__ out_s) {
+    float acc = 0.f;
+    if (!is_complex_scorer(SCORER)) {
+        for (int e = lane; e < W; e += 64)
+            acc += triple_term<SCORER>(to_f32(h[e]), 0.f, to_f32(t[e]), 0.f, to_f32(r[e]), 0.f, norm_p);
+    } else {
+        const int d = W / 2;
+        for (int e = lane; e < d; e += 64)
+            acc += triple_term<SCORER>(to_f32(h[e]), to_f32(h[d + e]), to_f32(t[e]), to_f32(t[d + e]), to_f32(r[e]),
+                                       SCORER == BESS_COMPLEX ? to_f32(r[d + e]) : 0.f, norm_p);
+    }
+    acc = finish_triple_score(SCORER, acc, norm_p);
+    if (lane == 0) *out_s = acc;
+}
+template <typename T, int SCORER>
+__device__ __forceinline__ void query_fwd_loops(const T* __restrict__ x, const T* __restrict__ r, int W, bool tail, int lane,
+                                                float* __restrict__ o) {
+    if (!is_complex_scorer(SCORER)) {
+        for (int e = lane; e < W; e += 64) {
+            float o1;
+            query_elem<SCORER>(to_f32(x[e]), 0.f, to_f32(r[e]), 0.f, tail, o[e], o1);
+        }
+    } else {
+        const int d = W / 2;
+        for (int e = lane; e < d; e += 64)
+            query_elem<SCORER>(to_f32(x[e]), to_f32(x[d + e]), to_f32(r[e]), SCORER == BESS_COMPLEX ? to_f32(r[d + e]) : 0.f,
+                               tail, o[e], o[d + e]);
+    }
+}
+
+template <typename T, int SCORER>
+__device__ __forceinline__ void triple_fwd_body(const TripleArgs& a, int64_t s, int lane, float* __restrict__ out) {
+    const int64_t hid = row_id(a.head_idx, a.rel_idx, s), tid = row_id(a.tail_idx, a.rel_idx, s);
+    const int64_t rid = a.rel_idx[s];
+    const T* h = static_cast<const T*>(a.head_base) + hid * a.W;
+    const T* t = static_cast<const T*>(a.tail_base) + tid * a.W;
+    const T* r = static_cast<const T*>(a.rel_table) + rid * a.Wr;
+    if (a.W <= REG_ROW_MAX) fwd_rows_by_trips<T, SCORER, false, true>(h, t, r, a.W, a.norm_p, false, lane, nullptr, out + s);
+    else triple_fwd_loops<T, SCORER>(h, t, r, a.W, a.norm_p, lane, out + s);
 }
 
 template <typename T, int SCORER>
@@ -96,33 +235,33 @@ struct QueryArgs {
 
 template <typename T, int SCORER>
 __device__ __forceinline__ void query_fwd_body(const QueryArgs& a, int64_t q, int lane, float* __restrict__ query) {
-    const T* x = row_ptr(static_cast<const T*>(a.ent_base), a.ent_idx, q, a.W);
-    const T* r = static_cast<const T*>(a.rel_table) + static_cast<int64_t>(a.rel_idx[q]) * a.Wr;
+    const int64_t xid = row_id(a.ent_idx, a.rel_idx, q), rid = a.rel_idx[q];
+    const T* x = static_cast<const T*>(a.ent_base) + xid * a.W;
+    const T* r = static_cast<const T*>(a.rel_table) + rid * a.Wr;
     float* o = query + q * a.W;
     const bool tail = a.side == BESS_CORRUPT_TAIL;
-    if (SCORER == BESS_TRANSE) {
-        for (int e = lane; e < a.W; e += 64)
-            o[e] = tail ? (to_f32(x[e]) + to_f32(r[e])) : (to_f32(x[e]) - to_f32(r[e]));
-    } else if (SCORER == BESS_DISTMULT) {
-        for (int e = lane; e < a.W; e += 64) o[e] = to_f32(x[e]) * to_f32(r[e]);
+    if (a.W <= REG_ROW_MAX) fwd_rows_by_trips<T, SCORER, true, false>(x, x, r, a.W, 0, tail, lane, o, nullptr);
+    else query_fwd_loops<T, SCORER>(x, r, a.W, tail, lane, o);
+}
+
+// K2 + K3 + K6 of one triple: its query row (built from the head for tail corruption, else from the tail) and its
+// positive score.  Rows that fit the registers are read once for both; wider rows go through the two loops in turn
+// (the second use hits L1 / L2).
+template <typename T, int SCORER>
+__device__ __forceinline__ void query_triple_fwd_body(const TripleArgs& a, int side, int64_t s, int lane,
+                                                      float* __restrict__ query, float* __restrict__ out) {
+    const int64_t hid = row_id(a.head_idx, a.rel_idx, s), tid = row_id(a.tail_idx, a.rel_idx, s);
+    const int64_t rid = a.rel_idx[s];
+    const T* h = static_cast<const T*>(a.head_base) + hid * a.W;
+    const T* t = static_cast<const T*>(a.tail_base) + tid * a.W;
+    const T* r = static_cast<const T*>(a.rel_table) + rid * a.Wr;
+    const bool tail = side == BESS_CORRUPT_TAIL;
+    float* o = query + s * a.W;
+    if (a.W <= REG_ROW_MAX) {
+        fwd_rows_by_trips<T, SCORER, true, true>(h, t, r, a.W, a.norm_p, tail, lane, o, out + s);
     } else {
-        const int d = a.W / 2;
-        for (int e = lane; e < d; e += 64) {
-            const float xr = to_f32(x[e]), xi = to_f32(x[d + e]);
-            float rr, ri;
-            if (SCORER == BESS_ROTATE) {
-                // heads: rotate the tail by -r (scoring.py:446-448)
-                const float ph = tail ? to_f32(r[e]) : -to_f32(r[e]);
-                rr = cosf(ph);
-                ri = sinf(ph);
-            } else {
-                // heads: conjugate relation times tail (scoring.py:928-932)
-                rr = to_f32(r[e]);
-                ri = tail ? to_f32(r[d + e]) : -to_f32(r[d + e]);
-            }
-            o[e] = xr * rr - xi * ri;
-            o[d + e] = xr * ri + xi * rr;
-        }
+        query_fwd_loops<T, SCORER>(tail ? h : t, r, a.W, tail, lane, o);
+        triple_fwd_loops<T, SCORER>(h, t, r, a.W, a.norm_p, lane, out + s);
     }
 }
 
@@ -135,15 +274,14 @@ __global__ __launch_bounds__(256) void k_query_fwd(QueryArgs a, float* __restric
 }
 
 // K2 + K3 + K6 of one replica's micro-batch in one launch: the positive score of every triple and the query
-// row in front of its negatives (the same wave reads h, r, t once from HBM; the second use hits L1 / L2)
+// row in front of its negatives (the same wave reads h, r, t once: query_triple_fwd_body)
 template <typename T, int SCORER>
 __global__ __launch_bounds__(256) void k_query_triple_fwd(TripleArgs a, QueryArgs qa, float* __restrict__ query,
                                                           float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t s = blockIdx.x * 4ll + (threadIdx.x >> 6);
     if (s >= a.n) return;
-    query_fwd_body<T, SCORER>(qa, s, lane, query);
-    triple_fwd_body<T, SCORER>(a, s, lane, out);
+    query_triple_fwd_body<T, SCORER>(a, qa.side, s, lane, query, out);
 }
 
 // the same launch with copy / fill jobs in spare workgroups behind the triples' (a training step's prologue - the
@@ -159,8 +297,7 @@ __global__ __launch_bounds__(256) void k_query_triple_fwd_jobs(TripleArgs a, Que
     const int lane = threadIdx.x & 63;
     const int64_t s = blockIdx.x * 4ll + (threadIdx.x >> 6);
     if (s >= a.n) return;
-    query_fwd_body<T, SCORER>(qa, s, lane, query);
-    triple_fwd_body<T, SCORER>(a, s, lane, out);
+    query_triple_fwd_body<T, SCORER>(a, qa.side, s, lane, query, out);
 }
 
 // ----------------------------------------------------------------- backward
@@ -527,9 +664,7 @@ __global__ __launch_bounds__(1024) void k_pertriple_tail(TripleArgs a, QueryArgs
     if (threadIdx.x == 0) last = last_workgroup_ticket(t.counter);
     __syncthreads();
     if (!last) return;
-    float acc = 0.f;
-    for (int64_t i = threadIdx.x; i < a.n; i += blockDim.x) acc += load_agent(t.row_loss + i);
-    tail_lds[threadIdx.x] = acc;
+    tail_lds[threadIdx.x] = strided_sum_agent(t.row_loss, a.n, threadIdx.x, blockDim.x);
     __syncthreads();
     for (int h = blockDim.x >> 1; h > 0; h >>= 1) {
         if (static_cast<int>(threadIdx.x) < h) tail_lds[threadIdx.x] += tail_lds[threadIdx.x + h];
