@@ -196,6 +196,7 @@ SIGNATURES = {
     "bess_normalize_rows": [_i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp],
     "bess_normalize_rows_bwd": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp],
     "bess_sample_negatives": [_PG, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "bess_sample_negatives_weighted": [_PG, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
     "bess_sample_bucket_indices": [_PG, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "bess_lookup_triples": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
     "bess_gather_candidate_lists": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp],
@@ -1842,6 +1843,26 @@ def sample_negatives(gen: Pcg64State, jump_table: torch.Tensor, n_step: int, n_s
     out = torch.empty((n_step, src_count, n_shard, B, K), dtype=torch.int32, device=dev)
     _launch("bess_sample_negatives", dev, ctypes.byref(gen), tp, n_step, n_shard, src_begin, src_count, B, K, cp, wp, tcp,
             top, n_type, int(local_sampling), out.data_ptr())
+    return out
+
+
+def sample_negatives_weighted(gen: Pcg64State, jump_table: torch.Tensor, n_step: int, n_shard: int, src_begin: int,
+                              src_count: int, B: int, K: int, cum_weights: torch.Tensor,
+                              shard_counts: torch.Tensor) -> torch.Tensor:
+    """`WeightedShardedNegativeSampler.__call__` for source shards [src_begin, src_begin + src_count): int32
+    [n_step, src_count, n_shard, B, K].  cum_weights int64 [src_count, ld]: the running sums of those shards' rows
+    (row s - src_begin for shard s); shard_counts int32 [n_shard]."""
+    dev = _same_device([("jump_table", jump_table), ("cum_weights", cum_weights), ("shard_counts", shard_counts)])
+    tp = _int_tensor(jump_table, "jump_table", torch.int64, 64 * 4)
+    cp = _int_tensor(shard_counts, "shard_counts", torch.int32, n_shard)
+    if src_begin < 0 or src_count < 0 or src_begin + src_count > n_shard:
+        raise ValueError(f"source shards [{src_begin}, {src_begin + src_count}) outside {n_shard} shards")
+    if cum_weights.dim() != 2 or cum_weights.shape[0] != src_count or cum_weights.shape[1] < 1:
+        raise ValueError(f"`cum_weights` must be [src_count = {src_count}, ld >= 1], got {tuple(cum_weights.shape)}")
+    wp = _int_tensor(cum_weights, "cum_weights", torch.int64)
+    out = torch.empty((n_step, src_count, n_shard, B, K), dtype=torch.int32, device=dev)
+    _launch("bess_sample_negatives_weighted", dev, ctypes.byref(gen), tp, n_step, n_shard, src_begin, src_count, B, K, wp,
+            int(cum_weights.shape[1]), cp, out.data_ptr())
     return out
 
 

@@ -14,7 +14,9 @@ host sampler's generators, so the two can be interleaved.
 
 Supported: `RandomShardedBatchSampler`, `RigidShardedBatchSampler`;
 `RandomShardedNegativeSampler`, `TypeBasedShardedNegativeSampler`,
-`PlaceholderNegativeSampler`, and `TripleBasedShardedNegativeSampler`: its
+`WeightedShardedNegativeSampler` (64-bit draws and an upper-bound search over
+the shard's running weight sums, which are kept in HBM:
+`bess_sample_negatives_weighted`), `PlaceholderNegativeSampler`, and `TripleBasedShardedNegativeSampler`: its
 fixed candidate lists (sharded, sorted and padded once by the host class,
 reference `negative_sampler.py:385-540`) are kept in HBM and every step's
 look-up + layout for the exchange (`negative_sampler.py:422-477`) is one kernel
@@ -45,6 +47,7 @@ from besskge.negative_sampler import (
     RandomShardedNegativeSampler,
     TripleBasedShardedNegativeSampler,
     TypeBasedShardedNegativeSampler,
+    WeightedShardedNegativeSampler,
 )
 
 _M128 = (1 << 128) - 1
@@ -152,7 +155,7 @@ class DeviceBatchSampler:
             micro-batch, in their flattened order): False where the triple with
             that negative in the corrupted place is a known one - the mask
             `BessKGE.forward` takes.  Every other tensor is what it is without
-            the filter.  For the random and the type-based negative sampler;
+            the filter.  For the random, the weighted and the type-based negative sampler;
             per-triple negatives without negative sample sharing, or the flat
             format (one candidate row serves every triple, the mask still has a
             row per triple).  The whole index is held by every rank, about 24 B
@@ -169,12 +172,14 @@ class DeviceBatchSampler:
         if type(bs) not in (RandomShardedBatchSampler, RigidShardedBatchSampler):
             raise TypeError(f"no device twin for {type(bs).__name__}")
         if type(ns) not in (RandomShardedNegativeSampler, TypeBasedShardedNegativeSampler, PlaceholderNegativeSampler,
-                            TripleBasedShardedNegativeSampler):
+                            TripleBasedShardedNegativeSampler, WeightedShardedNegativeSampler):
             raise TypeError(f"no device twin for {type(ns).__name__}")
         if filter_triples is not None:
-            if type(ns) not in (RandomShardedNegativeSampler, TypeBasedShardedNegativeSampler):
+            if type(ns) not in (RandomShardedNegativeSampler, TypeBasedShardedNegativeSampler,
+                                WeightedShardedNegativeSampler):
                 raise ValueError(f"filter_triples: {type(ns).__name__} draws no random negatives to filter (its candidates "
-                                 "are fixed lists or placeholders); only the random and type-based samplers are filtered")
+                                 "are fixed lists or placeholders); only the random, weighted and type-based samplers "
+                                 "are filtered")
             if not ns.flat_negative_format and negative_sample_sharing:
                 raise ValueError("filter_triples: per-triple negatives with negative_sample_sharing=True score every "
                                  "triple against all S * n_shard * n_negative candidates - the mask would be S x that; "
@@ -228,6 +233,11 @@ class DeviceBatchSampler:
                     if ns.return_sort_idx else None
         elif not isinstance(ns, PlaceholderNegativeSampler):
             self._shard_counts = put(ns.shard_counts, torch.int32)
+        if isinstance(ns, WeightedShardedNegativeSampler):
+            # running weight sums of the own shards' rows (8 B per row: a rank never uploads the other shards' unless
+            # the filter makes it draw their blocks too, see _sample_negatives)
+            self._cum_weights = put(ns.cum_weights[self.shards], torch.int64)
+            self._cum_weights_all: Optional[torch.Tensor] = self._cum_weights if len(self.shards) == n else None
         if isinstance(ns, TypeBasedShardedNegativeSampler):
             self._triple_types = put(ns.triple_types, torch.int32)
             self._type_counts = put(ns.type_counts, torch.int32)
@@ -374,6 +384,16 @@ class DeviceBatchSampler:
                 t = torch.cat([types[..., :half, 0], types[..., half:, 1]], dim=-1)
             wanted = t.reshape(n_step, n, -1).contiguous()
         src0, n_src = (0, n) if all_sources else (self.shards[0], len(self.shards))
+        if isinstance(ns, WeightedShardedNegativeSampler):
+            cum = self._cum_weights
+            if n_src != len(self.shards):
+                if self._cum_weights_all is None:  # first filtered step of a rank: the other shards' rows
+                    self._cum_weights_all = torch.from_numpy(np.ascontiguousarray(ns.cum_weights)).to(self.device)
+                cum = self._cum_weights_all
+            out = nat.sample_negatives_weighted(self._neg_stream.native(), self._neg_table, n_step, n, src0, n_src, B,
+                                                ns.n_negative, cum, self._shard_counts)
+            self._neg_stream.skip64(n_step * n * n * B * ns.n_negative)
+            return dict(negative_entities=out)
         out = nat.sample_negatives(
             self._neg_stream.native(), self._neg_table, n_step, n, src0, n_src, B,
             ns.n_negative, self._shard_counts, wanted,

@@ -13,10 +13,14 @@ Bit-identical to the reference for the same arguments and RNG state (pinned by
   * `TypeBasedShardedNegativeSampler`   <- `negative_sampler.py:135-230`
   * `TripleBasedShardedNegativeSampler` <- `negative_sampler.py:233-540`
   * `PlaceholderNegativeSampler`        <- `negative_sampler.py:543-574`
+
+`WeightedShardedNegativeSampler` (negatives in proportion to integer entity
+weights, e.g. `degree_weights`: degree ** 0.75) has no counterpart in the
+reference; its definition is the numpy formula in its docstring.
 """
 
 from abc import ABC, abstractmethod
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 from numpy.typing import NDArray
@@ -109,6 +113,150 @@ class RandomShardedNegativeSampler(ShardedNegativeSampler):
         raw = self.rng.integers(1 << 31, size=shape).astype(np.int32)
         # rows of the *source* shard (axis 1)
         rows = raw % self.shard_counts.reshape(1, -1, 1, 1, 1)
+        return dict(negative_entities=rows)
+
+
+def degree_weights(
+    triples: Sequence[NDArray],
+    n_entity: int,
+    alpha: float = 0.75,
+    scale: int = 1024,
+    min_weight: int = 1,
+    side: str = "both",
+) -> NDArray[np.int64]:
+    """Integer entity weights `max(min_weight, floor(degree ** alpha * scale))`
+    for :class:`WeightedShardedNegativeSampler` (word2vec's unigram ** 0.75,
+    the degree-based negatives of DGL-KE).
+
+    The power is taken once, here, in float64; the samplers on the host and on
+    the device only ever see the resulting integers.
+
+    :param triples: list of [n, 3] arrays of (head, relation, tail) in global
+        entity ids.
+    :param n_entity: number of entities.
+    :param alpha: exponent of the degree.
+    :param scale: weight of an entity of degree 1 (resolution of the rounding).
+    :param min_weight: floor of every weight; 0 excludes entities that never
+        occur, 1 (default) keeps every entity reachable.
+    :param side: occurrences counted: "h" (as head), "t" (as tail) or "both".
+    :return: int64 [n_entity].
+    """
+    if side not in ("h", "t", "both"):
+        raise ValueError(f"side must be 'h', 't' or 'both', got {side!r}")
+    if min_weight < 0 or scale < 1:
+        raise ValueError("degree_weights needs min_weight >= 0 and scale >= 1")
+    degree = np.zeros(n_entity, dtype=np.int64)
+    for part in triples:
+        part = np.asarray(part)
+        if side in ("h", "both"):
+            degree += np.bincount(part[:, 0], minlength=n_entity)
+        if side in ("t", "both"):
+            degree += np.bincount(part[:, 2], minlength=n_entity)
+    weights = np.floor(degree.astype(np.float64) ** alpha * scale).astype(np.int64)
+    return np.maximum(weights, np.int64(min_weight))
+
+
+class WeightedShardedNegativeSampler(RandomShardedNegativeSampler):
+    """Random negatives drawn from every shard in proportion to integer
+    entity weights (see :func:`degree_weights`).
+
+    Per call, with `source` the shard the rows are gathered from (axis 1)::
+
+        raw  = rng.integers(1 << 63, size=shape)        # one whole PCG64 output each
+        u    = raw % shard_totals[source]
+        rows = searchsorted(cum_weights[source, :shard_counts[source]], u, side="right")
+
+    i.e. the first local row whose inclusive running sum of weights exceeds
+    `u`: row `i` is drawn with probability `weight[i] / shard_totals[source]`
+    (up to the 2^-63 * total bias of the modulo), and a row of weight 0 or a
+    padding row is never returned.  Only integers are involved, so
+    `DeviceBatchSampler` reproduces the draws bit for bit.
+
+    The draws are 64-bit: totals may exceed 2^31, and whole outputs leave
+    numpy's buffered 32-bit half-word alone, so the stream position is a plain
+    count.  With all weights equal to 1 the sampler is uniform, but it does
+    **not** return the rows of :class:`RandomShardedNegativeSampler` for the
+    same seed, which takes 32-bit draws.
+
+    Meant for `LogSigmoidLoss` / `MarginRankingLoss` (e.g. with
+    `negative_adversarial_sampling=True`).  `SampledSoftmaxCrossEntropyLoss`
+    keeps its uniform-proposal correction `log(n_entity - 1) - log(N)`: no
+    per-candidate `-log q_j` is applied for these non-uniform negatives.
+    """
+
+    def __init__(
+        self,
+        entity_weights: NDArray,
+        n_negative: int,
+        sharding: Sharding,
+        seed: int,
+        corruption_scheme: str,
+        local_sampling: bool,
+        flat_negative_format: bool = False,
+    ) -> None:
+        """
+        :param entity_weights: [n_entity] integers >= 0, indexed by global
+            entity id; every shard needs a positive total below 2^62.
+        (other parameters: see :class:`RandomShardedNegativeSampler`)
+        """
+        super().__init__(
+            n_negative,
+            sharding,
+            seed,
+            corruption_scheme,
+            local_sampling,
+            flat_negative_format=flat_negative_format,
+        )
+        weights = np.asarray(entity_weights)
+        if weights.shape != (sharding.n_entity,):
+            raise ValueError(
+                f"entity_weights has shape {weights.shape}, expected ({sharding.n_entity},)"
+            )
+        if not np.issubdtype(weights.dtype, np.integer):
+            raise ValueError(f"entity_weights must be integers, got {weights.dtype}")
+        if weights.dtype == np.uint64 and weights.size and int(weights.max()) >= 1 << 62:
+            raise ValueError("entity_weights: a shard's total must stay below 2**62")
+        weights = weights.astype(np.int64)
+        if weights.size and int(weights.min()) < 0:
+            raise ValueError("entity_weights must be >= 0")
+        self.entity_weights = weights
+        n_shard, width = sharding.n_shard, sharding.max_entity_per_shard
+        real = np.arange(width)[None, :] < self.shard_counts.reshape(-1, 1)
+        local = np.where(
+            real, weights[np.where(real, sharding.shard_and_idx_to_entity, 0)], 0
+        )
+        # exact totals first (Python ints from the sums of two 31-bit halves,
+        # which cannot wrap for fewer than 2^31 rows), then the int64 running sum
+        high, low = (local >> 31).sum(axis=1), (local & ((1 << 31) - 1)).sum(axis=1)
+        totals = [(int(h) << 31) + int(l) for h, l in zip(high, low)]
+        for s, total in enumerate(totals):
+            if total == 0:
+                raise ValueError(f"entity_weights: shard {s} has total weight 0")
+            if total >= 1 << 62:
+                raise ValueError(
+                    f"entity_weights: shard {s} has total weight {total} >= 2**62"
+                )
+        #: inclusive running sum of the weights of a shard's rows (padding
+        #: rows weigh 0: flat after the last real row), int64 [n_shard, width]
+        self.cum_weights = np.cumsum(local, axis=1, dtype=np.int64)
+        #: int64 [n_shard]
+        self.shard_totals = np.array(totals, dtype=np.int64)
+
+    def __call__(self, sample_idx: NDArray[np.int64]) -> _SamplerOutput:
+        n_step, n_shard = sample_idx.shape[:2]
+        shape = (
+            n_step,
+            n_shard,
+            n_shard,
+            self._negative_batch_dim(sample_idx),
+            self.n_negative,
+        )
+        raw = self.rng.integers(1 << 63, size=shape)
+        u = raw % self.shard_totals.reshape(1, -1, 1, 1, 1)
+        rows = np.empty(shape, dtype=np.int32)
+        for source in range(n_shard):
+            cum = self.cum_weights[source, : self.shard_counts[source]]
+            rows[:, source] = np.searchsorted(cum, u[:, source], side="right")
         return dict(negative_entities=rows)
 
 

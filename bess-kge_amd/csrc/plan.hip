@@ -120,6 +120,7 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_normalize_rows),
     BESS_PLAN_FN(bess_normalize_rows_bwd),
     BESS_PLAN_FN(bess_sample_negatives),
+    BESS_PLAN_FN(bess_sample_negatives_weighted),
     BESS_PLAN_FN(bess_sample_bucket_indices),
     BESS_PLAN_FN(bess_lookup_triples),
     BESS_PLAN_FN(bess_gather_candidate_lists),

@@ -161,6 +161,82 @@ __global__ __launch_bounds__(256) void k_sample_bucket_idx(U128 state, U128 inc,
     }
 }
 
+// WeightedShardedNegativeSampler.__call__ (besskge/negative_sampler.py):
+//     u   = rng.integers(1 << 63, size=[step, n, n, B, K]) % shard_totals[src]
+//     row = searchsorted(cum_weights[src, :shard_counts[src]], u, side="right")
+// Logical element f of the full tensor is stream step f (64-bit draws: whole outputs, no buffered half-word).
+struct WeightedArgs {
+    U128 state, inc;
+    const uint64_t* table;
+    int64_t chunk_len;     // elements per step that are produced (src_count * n * B * K)
+    int64_t chunk_stride;  // elements per step (n * n * B * K)
+    int64_t chunk_off;     // src_begin * n * B * K
+    int64_t block;         // n * B * K   (elements per source shard)
+    int32_t src_begin;
+    const int64_t* cum;           // [src_count, ld_cum]: row s - src_begin is the running sum of source shard s
+    int64_t ld_cum;
+    const int32_t* shard_counts;  // [n_shard]
+    int32_t* out;
+};
+
+// grid.y = step; a thread owns DRAWS_PER_THREAD consecutive elements of the step's chunk.  It draws them all first and
+// then walks their upper-bound searches level by level together: the loads of one level are independent, so a thread
+// keeps DRAWS_PER_THREAD scattered 8-byte reads in flight instead of one (the first levels hit the same few lines).
+__global__ __launch_bounds__(256) void k_sample_negatives_weighted(WeightedArgs a) {
+    const int64_t step = blockIdx.y;
+    const int64_t rel0 = (blockIdx.x * 256ll + threadIdx.x) * DRAWS_PER_THREAD;
+    if (rel0 >= a.chunk_len) return;
+    U128 s = pcg_advance(a.state, static_cast<uint64_t>(step * a.chunk_stride + a.chunk_off + rel0), a.table);
+    const U128 mult = pcg_mult();
+    uint64_t u[DRAWS_PER_THREAD];
+    const int64_t* cum[DRAWS_PER_THREAD];
+    int32_t lo[DRAWS_PER_THREAD], hi[DRAWS_PER_THREAD];
+    int64_t src_prev = -1;
+    int32_t count = 0;
+    uint64_t total = 0;
+    const int64_t* row_prev = a.cum;
+#pragma unroll
+    for (int i = 0; i < DRAWS_PER_THREAD; ++i) {
+        s = add128(mul128(s, mult), a.inc);
+        const uint64_t x = pcg_output(s) >> 1;
+        const int64_t rel = rel0 + i;
+        const int64_t src = (rel < a.chunk_len ? rel : a.chunk_len - 1) / a.block;  // 0 .. src_count - 1
+        if (src != src_prev) {
+            src_prev = src;
+            row_prev = a.cum + src * a.ld_cum;
+            count = a.shard_counts[a.src_begin + src];
+            if (count > a.ld_cum) count = static_cast<int32_t>(a.ld_cum);  // never read past the row
+            total = count > 0 ? static_cast<uint64_t>(row_prev[count - 1]) : 0ull;
+        }
+        cum[i] = row_prev;
+        // an empty shard or a total of 0 (the host class refuses both) gives row 0, as x % 0 == 0 in numpy
+        u[i] = total ? x % total : 0ull;
+        lo[i] = 0;
+        hi[i] = (total && rel < a.chunk_len) ? count : 0;
+    }
+    bool more;
+    do {
+        more = false;
+        int64_t v[DRAWS_PER_THREAD];
+#pragma unroll
+        for (int i = 0; i < DRAWS_PER_THREAD; ++i) v[i] = cum[i][lo[i] < hi[i] ? lo[i] + ((hi[i] - lo[i]) >> 1) : 0];
+#pragma unroll
+        for (int i = 0; i < DRAWS_PER_THREAD; ++i) {
+            if (lo[i] < hi[i]) {
+                const int32_t mid = lo[i] + ((hi[i] - lo[i]) >> 1);
+                if (static_cast<uint64_t>(v[i]) <= u[i]) lo[i] = mid + 1;
+                else hi[i] = mid;
+                more |= lo[i] < hi[i];
+            }
+        }
+    } while (more);
+    // first row whose running sum exceeds u: u < total = cum[count - 1] keeps it below count
+    int32_t* out = a.out + step * a.chunk_len + rel0;
+#pragma unroll
+    for (int i = 0; i < DRAWS_PER_THREAD; ++i)
+        if (rel0 + i < a.chunk_len) out[i] = lo[i];
+}
+
 // head/relation/tail lookup; sample_idx [step, n, n2, ppp]; tail written as [step, n2, n, ppp] when swap
 __global__ __launch_bounds__(256) void k_lookup_triples(const int32_t* __restrict__ triples, int64_t n_triple,
                                                         const int64_t* __restrict__ sample_idx, int64_t n_out,
@@ -271,6 +347,39 @@ extern "C" int bess_sample_negatives(const bess_pcg64_state* gen, const uint64_t
     dim3 grid(static_cast<unsigned>(ceil_div(threads, 256)), static_cast<unsigned>(n_step));
     k_sample_negatives<<<grid, 256, 0, as_stream(stream)>>>(a);
     return check_launch("sample_negatives");
+}
+
+extern "C" int bess_sample_negatives_weighted(const bess_pcg64_state* gen, const uint64_t* jump_table, int64_t n_step,
+                                              int32_t n_shard, int32_t src_begin, int32_t src_count, int64_t B,
+                                              int64_t K, const int64_t* cum_weights, int64_t ld_cum,
+                                              const int32_t* shard_counts, int32_t* out, void* stream) {
+    BESS_REQUIRE(n_step >= 0 && n_shard >= 0 && src_count >= 0 && B >= 0 && K >= 0,
+                 "sample_negatives_weighted: bad shape");
+    BESS_REQUIRE(src_begin >= 0 && static_cast<int64_t>(src_begin) + src_count <= n_shard,
+                 "sample_negatives_weighted: shard range [%d, %lld) outside %d shards", src_begin,
+                 static_cast<long long>(src_begin) + src_count, n_shard);
+    if (n_step == 0 || n_shard == 0 || src_count == 0 || B == 0 || K == 0) return BESS_OK;
+    BESS_REQUIRE(gen && jump_table && cum_weights && shard_counts && out, "sample_negatives_weighted: NULL pointer");
+    BESS_REQUIRE(ld_cum >= 1, "sample_negatives_weighted: ld_cum = %lld", static_cast<long long>(ld_cum));
+    BESS_REQUIRE(n_step <= 65535, "sample_negatives_weighted: more than 65535 steps per call");
+    WeightedArgs a;
+    a.state = U128{gen->state_hi, gen->state_lo};
+    a.inc = U128{gen->inc_hi, gen->inc_lo};
+    a.table = jump_table;
+    a.block = static_cast<int64_t>(n_shard) * B * K;
+    a.chunk_stride = static_cast<int64_t>(n_shard) * a.block;
+    a.chunk_len = static_cast<int64_t>(src_count) * a.block;
+    a.chunk_off = static_cast<int64_t>(src_begin) * a.block;
+    a.src_begin = src_begin;
+    a.cum = cum_weights;
+    a.ld_cum = ld_cum;
+    a.shard_counts = shard_counts;
+    a.out = out;
+    const int64_t blocks = ceil_div(ceil_div(a.chunk_len, DRAWS_PER_THREAD), 256);
+    BESS_REQUIRE(blocks < (1ll << 31), "sample_negatives_weighted: output too large");
+    dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_step));
+    k_sample_negatives_weighted<<<grid, 256, 0, as_stream(stream)>>>(a);
+    return check_launch("sample_negatives_weighted");
 }
 
 extern "C" int bess_sample_bucket_indices(const bess_pcg64_state* gen, const uint64_t* jump_table, int64_t n_out,

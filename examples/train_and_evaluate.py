@@ -4,7 +4,7 @@ shard a knowledge graph, train with BESS on the device (device-side samplers,
 fused forward + backward + sparse update), then rank every entity for held-out
 queries and report filtered-free MRR / hits@10.
 
-    python examples/train_and_evaluate.py [--n-shard 1] [--steps 400] [--scorer TransE]
+    python examples/train_and_evaluate.py [--n-shard 1] [--steps 400] [--scorer TransE] [--negative-weights degree]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -31,7 +31,12 @@ from besskge.dataset import KGDataset  # noqa: E402
 from besskge.device_sampler import DeviceBatchSampler  # noqa: E402
 from besskge.loss import LogSigmoidLoss  # noqa: E402
 from besskge.metric import Evaluation  # noqa: E402
-from besskge.negative_sampler import PlaceholderNegativeSampler, RandomShardedNegativeSampler  # noqa: E402
+from besskge.negative_sampler import (  # noqa: E402
+    PlaceholderNegativeSampler,
+    RandomShardedNegativeSampler,
+    WeightedShardedNegativeSampler,
+    degree_weights,
+)
 from besskge.pipeline import AllScoresPipeline  # noqa: E402
 from besskge.sharding import PartitionedTripleSet, Sharding  # noqa: E402
 
@@ -62,6 +67,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--scorer", default="TransE", choices=["TransE", "RotatE", "DistMult", "ComplEx", "PairRE", "TranS"])
     ap.add_argument("--embedding-size", type=int, default=32)
     ap.add_argument("--lr", type=float, default=0.05)
+    ap.add_argument("--negative-weights", default="uniform", choices=["uniform", "degree"],
+                    help="degree: negatives in proportion to (occurrences in the training triples) ** 0.75")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -80,8 +87,13 @@ def main(argv=None) -> dict:
 
     # ---- training: shared ("flat") random negatives, log-sigmoid loss, Adam
     pts = PartitionedTripleSet.create_from_dataset(ds, "train", sharding, partition_mode="ht_shardpair")
-    ns = RandomShardedNegativeSampler(n_negative=64, sharding=sharding, seed=1, corruption_scheme="t",
-                                      local_sampling=False, flat_negative_format=True)
+    if args.negative_weights == "degree":
+        ns = WeightedShardedNegativeSampler(degree_weights([train], args.n_entity), n_negative=64, sharding=sharding,
+                                            seed=1, corruption_scheme="t", local_sampling=False,
+                                            flat_negative_format=True)
+    else:
+        ns = RandomShardedNegativeSampler(n_negative=64, sharding=sharding, seed=1, corruption_scheme="t",
+                                          local_sampling=False, flat_negative_format=True)
     bs = RandomShardedBatchSampler(pts, ns, shard_bs=512, batches_per_step=4, seed=2)
     model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn,
                                    loss_fn=LogSigmoidLoss(margin=6.0, negative_adversarial_sampling=True))

@@ -785,6 +785,21 @@ int bess_sample_negatives(const bess_pcg64_state* gen, const uint64_t* jump_tabl
                           const int32_t* type_counts, const int32_t* type_offsets, int32_t n_type,
                           int32_t local_sampling, int32_t* out, void* stream);
 
+/* `WeightedShardedNegativeSampler.__call__` (besskge/negative_sampler.py; the reference has no such sampler):
+ * negatives in proportion to integer entity weights,
+ *   u   = rng.integers(1 << 63, size=[n_step, n_shard, n_shard, B, K]) % total[src]
+ *   out = searchsorted(cum[src, :shard_counts[src]], u, side="right")     (first row whose running sum exceeds u)
+ * restricted to source shards [src_begin, src_begin + src_count): out is [n_step, src_count, n_shard, B, K].
+ * cum_weights int64 [src_count, ld_cum]: row s - src_begin is the inclusive running sum of the weights (>= 0) of
+ * source shard s in local-row order, total[s] = cum[s][shard_counts[s] - 1] (< 2^62); shard_counts int32 [n_shard]
+ * is indexed by the shard itself.  Element f of the full tensor is draw f of the stream (whole 64-bit outputs,
+ * value = output >> 1): gen->has_uint32 / uinteger are neither read nor changed.  A row of weight 0 is never
+ * returned; a shard with no rows or a total of 0 gives row 0.  Any size 0: nothing is read or written. */
+int bess_sample_negatives_weighted(const bess_pcg64_state* gen, const uint64_t* jump_table, int64_t n_step,
+                                   int32_t n_shard, int32_t src_begin, int32_t src_count, int64_t B, int64_t K,
+                                   const int64_t* cum_weights, int64_t ld_cum, const int32_t* shard_counts,
+                                   int32_t* out, void* stream);
+
 /* `TripleBasedShardedNegativeSampler.__call__` (negative_sampler.py:422-477): per-step look-up of the fixed
  * candidate lists and their layout for the exchange.  table_h (int32 [n_list, n_neg_shard, list_len]: local
  * rows per owning shard, padded; mask_h uint8 of the same shape marks the real entries) is made once by the
