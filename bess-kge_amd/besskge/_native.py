@@ -159,6 +159,8 @@ SIGNATURES = {
     "bess_loss_fwd_bwd": [_LD, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
     "bess_loss_fwd_bwd_norm": [_LD, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp],
     "bess_loss_fwd_bwd_one_launch": [_LD, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "bess_loss_fwd_bwd_logq": [_LD, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64,
+                               _i64, _i32, _f32, _vp],
     "bess_scatter_add_rows": [_vp, _i32, _vp, _vp, _i64, _f32, _vp],
     "bess_sparse_sgd": [_i32, _i32, _vp, _vp, _vp, _i64, _f32, _vp],
     "bess_dense_sgd": [_i32, _vp, _vp, _i64, _f32, _vp],
@@ -197,6 +199,7 @@ SIGNATURES = {
     "bess_normalize_rows_bwd": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp],
     "bess_sample_negatives": [_PG, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp],
     "bess_sample_negatives_weighted": [_PG, _vp, _i64, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
+    "bess_gather_negative_logq": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i32, _vp, _vp],
     "bess_sample_bucket_indices": [_PG, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     "bess_lookup_triples": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
     "bess_gather_candidate_lists": [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp],
@@ -1143,15 +1146,25 @@ _loss_counters: dict = {}  # (device, raw stream) -> int32 [TICKET_INTS], zero b
 
 
 def loss_fwd_bwd(l: LossDesc, pos: torch.Tensor, neg: torch.Tensor, weight: torch.Tensor, want_grad: bool,
-                 want_norm: bool = False) -> Tuple[Any, ...]:
+                 want_norm: bool = False, logq: Optional[torch.Tensor] = None, ppp: int = 0,
+                 lead_logq: float = 0.0) -> Tuple[Any, ...]:
     """Returns (loss [] f32, d_pos [S] | None, d_neg [S, N] | None) - and, with `want_norm`, a fourth item:
-    (m, L / C) of every row's softmax, [S, 2] (what `combine_dq_partials` takes; include/besskge_hip.h)."""
-    dev = _same_device([("positive_score", pos), ("negative_score", neg), ("triple_weight", weight)])
+    (m, L / C) of every row's softmax, [S, 2] (what `combine_dq_partials` takes; include/besskge_hip.h).
+
+    `logq` (sampled softmax only, `bess_loss_fwd_bwd_logq`): float32 [1 | 2 | S, C <= N] log-proposals of the last C
+    columns, subtracted from their scores inside the kernel (`neg` is not modified); the columns in front of them
+    take `lead_logq`.  Two rows are the heads' / tails' halves of every block of `ppp` triples (flat "ht")."""
+    dev = _same_device([("positive_score", pos), ("negative_score", neg), ("triple_weight", weight),
+                        ("negative_logq", logq)])
     for t, nm in ((pos, "positive_score"), (neg, "negative_score"), (weight, "triple_weight")):
         _f32(t, nm)
     S, N = int(neg.shape[0]), int(neg.shape[1])
     if pos.numel() != S or weight.numel() not in (1, S):
         raise ValueError("loss: shapes of positive_score / triple_weight do not match negative_score")
+    if logq is not None:
+        _f32(logq, "negative_logq")
+        if logq.dim() != 2:
+            raise ValueError("negative_logq must be 2-D")
     row_loss = torch.empty((S,), dtype=torch.float32, device=dev)
     loss = torch.empty((1,), dtype=torch.float32, device=dev)
     dp = torch.empty((S,), dtype=torch.float32, device=dev) if want_grad else None
@@ -1167,9 +1180,14 @@ def loss_fwd_bwd(l: LossDesc, pos: torch.Tensor, neg: torch.Tensor, weight: torc
             # the counter of recorded steps exists before any recording starts (a tensor made while a
             # stream is capturing would be cleared by a fill node at every replay: one more dispatch)
             _loss_counters[(dev, "capture")] = torch.zeros((TICKET_INTS,), dtype=torch.int32, device=dev)
-    _launch("bess_loss_fwd_bwd_one_launch", dev, ctypes.byref(l), pos.data_ptr(), neg.data_ptr(), S, N, N,
-            weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(), dp.data_ptr() if want_grad else 0,
-            dn.data_ptr() if want_grad else 0, N, norm.data_ptr() if want_norm else 0, counter.data_ptr())
+    common = (ctypes.byref(l), pos.data_ptr(), neg.data_ptr(), S, N, N, weight.data_ptr(), weight.numel(),
+              row_loss.data_ptr(), loss.data_ptr(), dp.data_ptr() if want_grad else 0,
+              dn.data_ptr() if want_grad else 0, N, norm.data_ptr() if want_norm else 0, counter.data_ptr())
+    if logq is not None:
+        _launch("bess_loss_fwd_bwd_logq", dev, *common, logq.data_ptr(), int(logq.shape[0]), int(logq.shape[1]),
+                int(ppp), float(lead_logq))
+    else:
+        _launch("bess_loss_fwd_bwd_one_launch", dev, *common)
     if want_norm:
         return loss.reshape(()), dp, dn, norm
     return loss.reshape(()), dp, dn
@@ -1863,6 +1881,24 @@ def sample_negatives_weighted(gen: Pcg64State, jump_table: torch.Tensor, n_step:
     out = torch.empty((n_step, src_count, n_shard, B, K), dtype=torch.int32, device=dev)
     _launch("bess_sample_negatives_weighted", dev, ctypes.byref(gen), tp, n_step, n_shard, src_begin, src_count, B, K, wp,
             int(cum_weights.shape[1]), cp, out.data_ptr())
+    return out
+
+
+def gather_negative_logq(negatives: torch.Tensor, log_q: torch.Tensor, src_begin: int, dst_begin: int, dst_count: int,
+                         local_sampling: bool) -> torch.Tensor:
+    """Log-proposals of drawn negatives in the layout of their scores (`bess_gather_negative_logq`): negatives int32
+    [n_step, src_count, n_shard, B, K] (source shards from `src_begin`), log_q float32 [n_shard, ld] -> float32
+    [n_step, dst_count, B, n_shard, K] for scoring shards [dst_begin, dst_begin + dst_count)."""
+    dev = _same_device([("negatives", negatives), ("log_q", log_q)])
+    if negatives.dim() != 5 or log_q.dim() != 2 or log_q.shape[0] != negatives.shape[2] or log_q.shape[1] < 1:
+        raise ValueError(f"negatives must be [n_step, src_count, n_shard, B, K] and log_q [n_shard, ld >= 1], got "
+                         f"{tuple(negatives.shape)} and {tuple(log_q.shape)}")
+    n_step, src_count, n, B, K = (int(x) for x in negatives.shape)
+    np_ = _int_tensor(negatives, "negatives", torch.int32)
+    _f32(log_q, "log_q")
+    out = torch.empty((n_step, dst_count, B, n, K), dtype=torch.float32, device=dev)
+    _launch("bess_gather_negative_logq", dev, np_, log_q.data_ptr(), int(log_q.shape[1]), n_step, n, src_begin,
+            src_count, dst_begin, dst_count, B, K, int(local_sampling), out.data_ptr())
     return out
 
 

@@ -333,6 +333,7 @@ class BessKGE(torch.nn.Module, ABC):
         triple_mask: Optional[torch.Tensor] = None,
         triple_weight: Optional[torch.Tensor] = None,
         negative_mask: Optional[torch.Tensor] = None,
+        negative_logq: Optional[torch.Tensor] = None,
     ) -> Dict[str, Any]:
         """One micro-batch of one replica (this process must host exactly one).
 
@@ -346,12 +347,17 @@ class BessKGE(torch.nn.Module, ABC):
         :param triple_weight: (1, n_shard * positive_per_partition) or (1,).
         :param negative_mask: (1, B, n_shard, padded_negative) real (non
             padding) negatives.
+        :param negative_logq: (1, B, n_shard, n_negative) log-proposal of every
+            sampled negative, in the layout of `negative_mask`
+            (`WeightedShardedNegativeSampler(return_logq=True)`): required by,
+            and only taken with, `SampledSoftmaxCrossEntropyLoss(
+            proposal_correction=True)`.
         :return: dict with `loss`, `positive_score`, `negative_score`,
             `ranks`, `metrics` as configured.
         """
         batch = dict(head=head, relation=relation, tail=tail, negative=negative)
         for k, v in (("triple_mask", triple_mask), ("triple_weight", triple_weight),
-                     ("negative_mask", negative_mask)):
+                     ("negative_mask", negative_mask), ("negative_logq", negative_logq)):
             if v is not None:
                 batch[k] = v
         if len(self._group().local_shards) != 1:
@@ -363,6 +369,8 @@ class BessKGE(torch.nn.Module, ABC):
 
     def forward_replicas(self, batches: List[_Batch]) -> List[Dict[str, Any]]:
         """Lock-step forward of all replicas hosted by this process."""
+        for b in batches:
+            self._logq_rows(b)  # (refused before anything is scored)
         steps = self._score_replicas(batches, _StepContext(batches))
         return [self._finish(st, b, want_grad=False)[0] for st, b in zip(steps, batches)]
 
@@ -426,7 +434,14 @@ class BessKGE(torch.nn.Module, ABC):
         if self.loss_fn:
             w = self._triple_weight(batch, dev, scale)
             ld = self.loss_fn.kernel_desc(int(neg.shape[1]))
-            if st.loss_pre is not None and not want_norm:  # the scoring call has done K8 already
+            logq = self._logq_rows(batch, int(pos.shape[0]), int(neg.shape[1]), dev)
+            if logq is not None:
+                # sampled softmax over a non-uniform proposal: the two-pass route, the log-proposals are subtracted
+                # where the loss kernel loads the scores (which stay as they were scored)
+                loss, d_pos, d_neg = nat.loss_fwd_bwd(
+                    ld, pos, neg, w, want_grad, logq=logq, lead_logq=self.loss_fn.lead_logq,
+                    ppp=ppp if flat_ht else (2 if logq.shape[0] == 2 else 0))
+            elif st.loss_pre is not None and not want_norm:  # the scoring call has done K8 already
                 loss, d_pos, d_neg = st.loss_pre
             elif want_norm:  # ScoreMoving's fused training forward: the softmax normalisation goes back to the shards
                 loss, d_pos, d_neg, st.loss_norm = nat.loss_fwd_bwd(ld, pos, neg, w, want_grad, want_norm=True)
@@ -435,7 +450,7 @@ class BessKGE(torch.nn.Module, ABC):
             # (gradients averaged over accumulated micro-batches / replicas travel as a scaled triple weight;
             # the value handed back stays the micro-batch's own loss)
             out["loss"] = loss if scale == 1.0 else loss / scale
-            if isinstance(self.loss_fn, SampledSoftmaxCrossEntropyLoss) and self.return_scores \
+            if isinstance(self.loss_fn, SampledSoftmaxCrossEntropyLoss) and self.return_scores and logq is None \
                     and self.score_fn.relation_embedding.dtype == torch.float32:
                 # the reference shifts fp32 negative scores in place before the
                 # cross entropy (loss.py:233-237) and returns that same tensor
@@ -453,6 +468,45 @@ class BessKGE(torch.nn.Module, ABC):
                     out["ranks"] = ranks
                 out["metrics"] = self.evaluation.stacked_metrics_from_ranks(ranks, tm)
         return out, d_pos, d_neg
+
+    def _proposal_correction(self) -> bool:
+        """Does the loss lower every negative's logit by its log-proposal (`negative_logq`)?  Such a step takes the
+        two-pass route: scores, K7, then `bess_loss_fwd_bwd_logq`."""
+        return bool(getattr(self.loss_fn, "proposal_correction", False))
+
+    def _logq_rows(self, batch: _Batch, S: Optional[int] = None, n_neg: Optional[int] = None,
+                   dev: Optional[torch.device] = None) -> Optional[torch.Tensor]:
+        """`negative_logq` of the micro-batch as the rows `bess_loss_fwd_bwd_logq` takes, float32 [1 | 2 | S, n_shard *
+        n_negative] for the LAST columns of the scores (augmented candidates come first), or None without proposal
+        correction.  Refuses what the correction does not cover; with `S`, `n_neg` also against the scores."""
+        lq = batch.get("negative_logq")
+        if not self._proposal_correction():
+            if lq is not None:
+                raise ValueError("`negative_logq` is only taken by SampledSoftmaxCrossEntropyLoss(proposal_correction="
+                                 f"True), the loss is {type(self.loss_fn).__name__} without it")
+            return None
+        if lq is None:
+            raise ValueError("proposal_correction=True: the batch has no `negative_logq` (the negative sampler's "
+                             "`return_logq=True` adds it)")
+        ns = self.negative_sampler
+        if not ns.flat_negative_format and self.score_fn.negative_sample_sharing:
+            raise ValueError("proposal_correction: per-triple negatives with negative_sample_sharing=True score every "
+                             "triple against all S * n_shard * n_negative candidates - negative_logq would be S x "
+                             "that; use the flat negative format or turn sharing off")
+        neg = batch["negative"]
+        n, B, K = (int(x) for x in neg.shape[-3:])
+        if lq.dim() != 4 or tuple(lq.shape) != (1, B, n, K):
+            raise ValueError(f"negative_logq has shape {tuple(lq.shape)}, the negatives {tuple(neg.shape)} need "
+                             f"(1, {B}, {n}, {K})")
+        if S is None:
+            return None
+        rows = lq.squeeze(0).flatten(start_dim=-2).to(device=dev, dtype=torch.float32).contiguous()
+        flat_ht = ns.flat_negative_format and ns.corruption_scheme == "ht"
+        if rows.shape[0] not in (1, S) and not (rows.shape[0] == 2 and flat_ht):
+            raise ValueError(f"negative_logq has {rows.shape[0]} rows for {S} triples")
+        if rows.shape[1] > n_neg or (rows.shape[1] != n_neg and not self.augment_negative):
+            raise ValueError(f"negative_logq covers {rows.shape[1]} candidates per triple, {n_neg} were scored")
+        return rows
 
     def _kill_spec(self, batch: _Batch, n: int, ppp: int, S: int, dev: torch.device
                    ) -> Optional[Tuple[int, bool, int, Optional[torch.Tensor]]]:
@@ -1103,6 +1157,8 @@ class BessKGE(torch.nn.Module, ABC):
         of its own per call or None: the step adds the triples' weights to it as `weight` (`_training_context`)."""
         if self.loss_fn is None or not self.score_fn.supports_fused_forward or self.augment_negative:
             return None
+        if self._proposal_correction():
+            return None  # (a per-candidate shift inside the fused forwards is not built: two-pass path)
         if not hasattr(self.loss_fn, "kernel_desc") or not nat.row_fits_registers(self.score_fn.kernel_desc()):
             return None  # (rows wider than a group's registers are scored in column windows: two-pass path)
         # a negative_mask (the padding of triple-specific negatives) is applied inside the fused pass when it
@@ -1116,6 +1172,8 @@ class BessKGE(torch.nn.Module, ABC):
         of every replica's batch plus the triples' weights in the loss (times the gradient scale)."""
         if self.loss_fn is None:
             raise RuntimeError("train_step needs a loss function")
+        for b in batches:
+            self._logq_rows(b)  # (refused before anything is scored)
         ctx = _StepContext(batches, training=True, grad_scale=grad_scale)
         ctx.optimizer = optimizer
         ctx.fuse = [self._fusable(b) for b in batches]
@@ -1188,7 +1246,7 @@ class EmbeddingMovingBessKGE(BessKGE):
         desc = fn.kernel_desc()
         rel_table = fn.relation_embedding.data
         k8_in_scoring = (ctx.training and self.loss_fn is not None and hasattr(self.loss_fn, "kernel_desc")
-                         and not self.evaluation)
+                         and not self.evaluation and not self._proposal_correction())
         for i, st in enumerate(steps):
             self._build_groups(st, exchange_negatives)
             src = ctx.batches[i] if ctx.batches is not None else None  # the caller's batch: masks, weights

@@ -16,7 +16,9 @@ Supported: `RandomShardedBatchSampler`, `RigidShardedBatchSampler`;
 `RandomShardedNegativeSampler`, `TypeBasedShardedNegativeSampler`,
 `WeightedShardedNegativeSampler` (64-bit draws and an upper-bound search over
 the shard's running weight sums, which are kept in HBM:
-`bess_sample_negatives_weighted`), `PlaceholderNegativeSampler`, and `TripleBasedShardedNegativeSampler`: its
+`bess_sample_negatives_weighted`; with `return_logq` the batch also carries
+`negative_logq`, gathered from the same float32 table as on the host by
+`bess_gather_negative_logq`), `PlaceholderNegativeSampler`, and `TripleBasedShardedNegativeSampler`: its
 fixed candidate lists (sharded, sorted and padded once by the host class,
 reference `negative_sampler.py:385-540`) are kept in HBM and every step's
 look-up + layout for the exchange (`negative_sampler.py:422-477`) is one kernel
@@ -238,6 +240,7 @@ class DeviceBatchSampler:
             # the filter makes it draw their blocks too, see _sample_negatives)
             self._cum_weights = put(ns.cum_weights[self.shards], torch.int64)
             self._cum_weights_all: Optional[torch.Tensor] = self._cum_weights if len(self.shards) == n else None
+            self._log_q: Optional[torch.Tensor] = None  # `return_logq`: float32 [n, width], uploaded by the first step
         if isinstance(ns, TypeBasedShardedNegativeSampler):
             self._triple_types = put(ns.triple_types, torch.int32)
             self._type_counts = put(ns.type_counts, torch.int32)
@@ -456,12 +459,21 @@ class DeviceBatchSampler:
         want = [k for k in ("head", "relation", "tail") if k != bs.dummy]
         batch: Dict[str, Any] = nat.lookup_triples(self._triples, sample_idx, self._pair_buckets, want)
         batch.update(extras)
-        drawn = self._sample_negatives(sample_idx, all_sources=self._filter is not None)
-        negative_mask = None
+        ns = bs.negative_sampler
+        # a rank scores candidates from every source shard: their log-proposals need all the blocks, like the filter
+        logq_wanted = bool(getattr(ns, "return_logq", False))
+        all_sources = self._filter is not None or (logq_wanted and not ns.local_sampling)
+        drawn = self._sample_negatives(sample_idx, all_sources=all_sources)
+        negative_mask = negative_logq = None
         if self._filter is not None:
             negative_mask = self._negative_mask(batch, drawn["negative_entities"], int(sample_idx.shape[-1]))
-            if (lo, hi) != (0, self.n_shard):
-                drawn["negative_entities"] = drawn["negative_entities"][:, lo:hi].contiguous()
+        if logq_wanted:
+            if self._log_q is None:  # first step: the whole table, 4 B per row of every shard
+                self._log_q = torch.from_numpy(np.ascontiguousarray(ns.log_q)).to(self.device)
+            negative_logq = nat.gather_negative_logq(drawn["negative_entities"], self._log_q,
+                                                     0 if all_sources else lo, lo, hi - lo, bool(ns.local_sampling))
+        if all_sources and (lo, hi) != (0, self.n_shard):
+            drawn["negative_entities"] = drawn["negative_entities"][:, lo:hi].contiguous()
         if "negative_entities" in drawn:
             batch["negative"] = drawn.pop("negative_entities")
         batch.update(drawn)  # negative_mask / negative_sort_idx of the triple-based sampler
@@ -480,4 +492,6 @@ class DeviceBatchSampler:
             batch = {k: (v if (k == "negative" and not whole) else v[:, lo:hi].contiguous()) for k, v in batch.items()}
         if negative_mask is not None:
             batch["negative_mask"] = negative_mask  # (made for `shards` only)
+        if negative_logq is not None:
+            batch["negative_logq"] = negative_logq  # (likewise)
         return batch

@@ -8,6 +8,7 @@ triple_weight)`; always fp32, *summed* over the micro-batch.
     MarginRankingLoss    sum_i w_i sum_j a_ij relu(neg_ij - pos_i + m)
     SampledSoftmaxCrossEntropyLoss
                          sum_i w_i CE([pos_i, neg_i + log(nE-1) - log N], class 0)
+                         (proposal_correction: neg_ij - logq_ij - log N)
 
 with a_ij = softmax_j(alpha * neg_ij) (detached) for self-adversarial
 weighting, else 1/N; everything multiplied by `loss_scale`.
@@ -66,18 +67,35 @@ class BaseLossFunction(torch.nn.Module, ABC):
         positive_score: torch.Tensor,
         negative_score: torch.Tensor,
         triple_weight: torch.Tensor,
+        negative_logq: Optional[torch.Tensor] = None,
     ) -> torch.Tensor:
         """Batch loss.
 
         :param positive_score: [batch].
         :param negative_score: [batch, n_negative].
         :param triple_weight: [batch] or [1] weights of the positive triples.
+        :param negative_logq: [batch | 1, n_negative] log-proposal of every
+            negative: required by (and only taken by)
+            `SampledSoftmaxCrossEntropyLoss(proposal_correction=True)`.
         """
+        corrected = bool(getattr(self, "proposal_correction", False))
+        if corrected and negative_logq is None:
+            raise ValueError("proposal_correction=True: the loss needs `negative_logq` (the log-proposal of every "
+                             "negative, `WeightedShardedNegativeSampler(return_logq=True)`)")
+        if negative_logq is not None:
+            if not corrected:
+                raise ValueError(f"`negative_logq` given to {type(self).__name__} without proposal_correction=True")
+            negative_logq = negative_logq.float().reshape(-1, negative_logq.shape[-1]).contiguous()
+            if negative_logq.shape[0] not in (1, negative_score.shape[0]) \
+                    or negative_logq.shape[1] != negative_score.shape[-1]:
+                raise ValueError(f"negative_logq {tuple(negative_logq.shape)} does not match the negative scores "
+                                 f"{tuple(negative_score.shape)}")
         return ops.Loss.apply(
             self.kernel_desc(int(negative_score.shape[-1])),
             positive_score.float(),
             negative_score.float(),
             triple_weight,
+            negative_logq,
         )
 
 
@@ -130,18 +148,39 @@ class MarginRankingLoss(MarginBasedLossFunction):
 
 
 class SampledSoftmaxCrossEntropyLoss(BaseLossFunction):
-    """Sampled-softmax cross entropy (reference loss.py:198-251)."""
+    """Sampled-softmax cross entropy (reference loss.py:198-251).
+
+    `proposal_correction=True` (no counterpart in the reference): the negatives
+    come from a non-uniform proposal and every logit is lowered by the log of
+    its candidate's expected count among the N candidates,
+
+        CE([pos_i, neg_ij - logq_ij - log N], class 0),
+
+    `logq_ij` being the `negative_logq` the sampler returns
+    (`WeightedShardedNegativeSampler(return_logq=True)`); augmented in-batch
+    candidates take `lead_logq` = -log(n_entity - 1), the reference's uniform
+    value.  With a uniform proposal this is the reference's loss.
+    """
 
     _kind = nat.LOSS_SSCE
 
-    def __init__(self, n_entity: int, loss_scale: float = 1.0) -> None:
+    def __init__(self, n_entity: int, loss_scale: float = 1.0, proposal_correction: bool = False) -> None:
         super().__init__()
         self.negative_adversarial_sampling = False
         self.negative_adversarial_scale = torch.tensor(0.0, dtype=torch.float32)
         self.loss_scale = torch.tensor(loss_scale, dtype=torch.float32)
         self.n_entity = n_entity
+        self.proposal_correction = bool(proposal_correction)
+
+    @property
+    def lead_logq(self) -> float:
+        """Log-proposal of the candidates the sampler did not draw (augmented negatives): uniform."""
+        return -float(np.log(self.n_entity - 1))
 
     def score_shift(self, n_negative: int) -> float:
         # log(1 / E[count(candidate == class)]): constant over the negatives,
-        # zero for the target (loss.py:230-237)
+        # zero for the target (loss.py:230-237); with proposal_correction the
+        # per-candidate part comes from negative_logq
+        if self.proposal_correction:
+            return -float(np.log(n_negative))
         return float(np.log(self.n_entity - 1) - np.log(n_negative))

@@ -27,7 +27,7 @@ from numpy.typing import NDArray
 
 from besskge.sharding import Sharding
 
-_SamplerOutput = Dict[str, Union[NDArray[np.int32], NDArray[np.bool_]]]
+_SamplerOutput = Dict[str, Union[NDArray[np.int32], NDArray[np.bool_], NDArray[np.float32]]]
 
 
 def _fold_triple_axes(x: NDArray, n_tail: int) -> NDArray:
@@ -178,10 +178,30 @@ class WeightedShardedNegativeSampler(RandomShardedNegativeSampler):
     **not** return the rows of :class:`RandomShardedNegativeSampler` for the
     same seed, which takes 32-bit draws.
 
-    Meant for `LogSigmoidLoss` / `MarginRankingLoss` (e.g. with
-    `negative_adversarial_sampling=True`).  `SampledSoftmaxCrossEntropyLoss`
-    keeps its uniform-proposal correction `log(n_entity - 1) - log(N)`: no
-    per-candidate `-log q_j` is applied for these non-uniform negatives.
+    For `LogSigmoidLoss` / `MarginRankingLoss` (e.g. with
+    `negative_adversarial_sampling=True`) the negatives are used as they are.
+    The sampled softmax is only a consistent estimate of the full softmax when
+    every candidate's logit is lowered by the log of its expected count among
+    the candidates: `return_logq=True` makes the log-proposal travel with the
+    draws, for `SampledSoftmaxCrossEntropyLoss(proposal_correction=True)`.
+    The table, made once in float64 and kept as float32::
+
+        log_q[s, i] = log(weight of local row i of shard s / shard_totals[s])
+                      - (0 if local_sampling else log(n_shard))
+
+    (0.0 for rows of weight 0 and padding rows, which are never drawn):
+    `exp(log_q)` is the probability that one candidate slot of a triple holds
+    that entity - the model scores a triple against all `n_shard` blocks of a
+    shard pair.  Every call then also returns `negative_logq`, float32 in the
+    *scoring* layout `[step, scoring shard d, B, n_shard, n_negative]`::
+
+        negative_logq[step, d, b, s, k] = log_q[s, negative_entities[step, s, d, b, k]]
+        local_sampling:  [step, d, b, j, k] = log_q[d, negative_entities[step, d, j, b, k]]
+
+    `negative_entities` and the stream position do not depend on the option.
+    Without it (default) `SampledSoftmaxCrossEntropyLoss` keeps its
+    uniform-proposal shift `log(n_entity - 1) - log(N)`, which is biased for
+    non-uniform weights.
     """
 
     def __init__(
@@ -193,10 +213,13 @@ class WeightedShardedNegativeSampler(RandomShardedNegativeSampler):
         corruption_scheme: str,
         local_sampling: bool,
         flat_negative_format: bool = False,
+        return_logq: bool = False,
     ) -> None:
         """
         :param entity_weights: [n_entity] integers >= 0, indexed by global
             entity id; every shard needs a positive total below 2^62.
+        :param return_logq: also return `negative_logq`, the log-proposal of
+            every drawn negative (see the class docstring).
         (other parameters: see :class:`RandomShardedNegativeSampler`)
         """
         super().__init__(
@@ -241,6 +264,14 @@ class WeightedShardedNegativeSampler(RandomShardedNegativeSampler):
         self.cum_weights = np.cumsum(local, axis=1, dtype=np.int64)
         #: int64 [n_shard]
         self.shard_totals = np.array(totals, dtype=np.int64)
+        self.return_logq = bool(return_logq)
+        if self.return_logq:
+            with np.errstate(divide="ignore"):
+                log_q = np.log(local.astype(np.float64) / np.array(totals, dtype=np.float64)[:, None])
+            if not local_sampling:
+                log_q -= np.log(float(n_shard))
+            #: float32 [n_shard, width]: log-probability that one candidate slot holds the row
+            self.log_q = np.where(local > 0, log_q, 0.0).astype(np.float32)
 
     def __call__(self, sample_idx: NDArray[np.int64]) -> _SamplerOutput:
         n_step, n_shard = sample_idx.shape[:2]
@@ -257,7 +288,13 @@ class WeightedShardedNegativeSampler(RandomShardedNegativeSampler):
         for source in range(n_shard):
             cum = self.cum_weights[source, : self.shard_counts[source]]
             rows[:, source] = np.searchsorted(cum, u[:, source], side="right")
-        return dict(negative_entities=rows)
+        out: _SamplerOutput = dict(negative_entities=rows)
+        if self.return_logq:
+            # [step, shard the rows are of, other shard, B, K] -> [step, scoring shard, B, block, K]
+            logq = self.log_q[np.arange(n_shard).reshape(1, -1, 1, 1, 1), rows]
+            order = (0, 1, 3, 2, 4) if self.local_sampling else (0, 2, 3, 1, 4)
+            out["negative_logq"] = np.ascontiguousarray(logq.transpose(order))
+        return out
 
 
 class TypeBasedShardedNegativeSampler(RandomShardedNegativeSampler):

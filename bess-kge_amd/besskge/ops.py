@@ -153,14 +153,15 @@ class ReduceNegatives(torch.autograd.Function):
 
 
 class Loss(torch.autograd.Function):
-    """K8 fused loss + score gradients."""
+    """K8 fused loss + score gradients (`logq`: the sampled softmax's per-candidate log-proposals, see
+    `nat.loss_fwd_bwd`)."""
 
     @staticmethod
     def forward(ctx: Any, ldesc: nat.LossDesc, pos: torch.Tensor, neg: torch.Tensor,  # type: ignore
-                weight: torch.Tensor) -> torch.Tensor:
+                weight: torch.Tensor, logq: Optional[torch.Tensor] = None) -> torch.Tensor:
         need = pos.requires_grad or neg.requires_grad
         loss, dp, dn = nat.loss_fwd_bwd(ldesc, pos.contiguous(), neg.contiguous(),
-                                        weight.reshape(-1).float().contiguous(), True)
+                                        weight.reshape(-1).float().contiguous(), True, logq=logq)
         ctx.save_for_backward(dp, dn)
         del need
         return loss
@@ -168,4 +169,4 @@ class Loss(torch.autograd.Function):
     @staticmethod
     def backward(ctx: Any, g: torch.Tensor):  # type: ignore
         dp, dn = ctx.saved_tensors
-        return None, g * dp, g * dn, None
+        return None, g * dp, g * dn, None, None

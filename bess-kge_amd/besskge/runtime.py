@@ -26,8 +26,8 @@ from besskge.collectives import DistributedGroup, MultiDeviceGroup, NativeGroup,
 
 _MULTI_PROCESS = (DistributedGroup, NativeGroup)
 
-_BATCH_KEYS = ("head", "relation", "tail", "negative", "triple_mask", "triple_weight", "negative_mask", "step",
-               "rank_truth", "rank_filter", "topk_k")  # (the last three: AllScoresBESS counting ranks / keeping top-k lists)
+_BATCH_KEYS = ("head", "relation", "tail", "negative", "triple_mask", "triple_weight", "negative_mask", "negative_logq",
+               "step", "rank_truth", "rank_filter", "topk_k")  # (the last three: AllScoresBESS counting ranks / keeping top-k lists)
 
 
 @dataclasses.dataclass

@@ -44,6 +44,26 @@ __global__ __launch_bounds__(256) void k_mask_scores(float* __restrict__ neg, in
     }
 }
 
+// One launch: the workgroup that finishes last sums the row terms, in a fixed order (bitwise reproducible
+// whatever the order the workgroups ran in), and leaves the counter at zero for the next call.
+__device__ __forceinline__ void sum_rows_in_last_workgroup(const float* __restrict__ row_loss, int64_t n_triple,
+                                                           int32_t* __restrict__ counter, float* __restrict__ loss) {
+    __shared__ float part[256];
+    __shared__ int last;
+    release_to_agent();
+    __syncthreads();
+    if (threadIdx.x == 0) last = last_workgroup_ticket(counter);
+    __syncthreads();
+    if (!last) return;
+    part[threadIdx.x] = strided_sum_agent(row_loss, n_triple, threadIdx.x, 256);
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[0] = part[0];
+}
+
 template <int KIND, bool ADV, bool GRAD, int CH>
 __global__ __launch_bounds__(256) void k_loss_rows(bess_loss_desc l, const float* __restrict__ pos,
                                                    const float* __restrict__ neg, int64_t n_triple,
@@ -59,22 +79,39 @@ __global__ __launch_bounds__(256) void k_loss_rows(bess_loss_desc l, const float
         loss_row<KIND, ADV, GRAD, CH>(l, pos, neg, s, n_neg, ld_neg, weight, weight_len, row_loss, d_pos, d_neg, ld_dneg,
                                       row_norm);
     if (!counter) return;  // (uniform: the sum is a second launch, k_sum_rows)
-    // One launch: the workgroup that finishes last sums the row terms, in a fixed order (bitwise reproducible
-    // whatever the order the workgroups ran in), and leaves the counter at zero for the next call.
-    __shared__ float part[256];
-    __shared__ int last;
-    release_to_agent();
-    __syncthreads();
-    if (threadIdx.x == 0) last = last_workgroup_ticket(counter);
-    __syncthreads();
-    if (!last) return;
-    part[threadIdx.x] = strided_sum_agent(row_loss, n_triple, threadIdx.x, 256);
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-        __syncthreads();
+    sum_rows_in_last_workgroup(row_loss, n_triple, counter, loss);
+}
+
+// The sampled-softmax rows with a per-candidate log-proposal (bess_loss_fwd_bwd_logq): score j of triple s is lowered by
+// logq[mrow(s), j - lead] (lead = n_neg - cols; lead_logq in front of it) where it is loaded, the rest is k_loss_rows.
+struct LogqRows {
+    const float* logq;  // [rows, cols]
+    int64_t rows, cols;
+    int32_t ppp;
+    float lead_logq;
+};
+
+template <bool GRAD, int CH>
+__global__ __launch_bounds__(256) void k_loss_rows_logq(bess_loss_desc l, const float* __restrict__ pos,
+                                                        const float* __restrict__ neg, int64_t n_triple,
+                                                        int64_t n_neg, int64_t ld_neg,
+                                                        const float* __restrict__ weight,
+                                                        int64_t weight_len, float* __restrict__ row_loss,
+                                                        float* __restrict__ d_pos,
+                                                        float* __restrict__ d_neg, int64_t ld_dneg,
+                                                        float* __restrict__ row_norm, LogqRows q,
+                                                        int32_t* __restrict__ counter, float* __restrict__ loss) {
+    const int64_t s = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (s < n_triple) {
+        int64_t mrow = s;  // (the rule of k_mask_scores)
+        if (q.rows == 1) mrow = 0;
+        else if (q.rows == 2) mrow = (s % q.ppp >= q.ppp / 2) ? 1 : 0;
+        loss_row_impl<BESS_LOSS_SSCE, false, GRAD, CH, true>(l, pos, neg, s, n_neg, ld_neg, weight, weight_len, row_loss,
+                                                             d_pos, d_neg, ld_dneg, row_norm, q.logq + mrow * q.cols,
+                                                             static_cast<int>(n_neg - q.cols), q.lead_logq);
     }
-    if (threadIdx.x == 0) loss[0] = part[0];
+    if (!counter) return;
+    sum_rows_in_last_workgroup(row_loss, n_triple, counter, loss);
 }
 
 // Prediction rank of the positive among its candidates (reference metric.py:129-182):
@@ -187,9 +224,11 @@ extern "C" int bess_loss_fwd_bwd(const bess_loss_desc* l, const float* pos, cons
                                   ld_dneg, nullptr, stream);
 }
 
+// `lq`: the log-proposal rows of bess_loss_fwd_bwd_logq (checked there), NULL for every other entry point
 static int loss_impl(const bess_loss_desc* l, const float* pos, const float* neg, int64_t n_triple, int64_t n_neg,
                      int64_t ld_neg, const float* weight, int64_t weight_len, float* row_loss, float* loss,
-                     float* d_pos, float* d_neg, int64_t ld_dneg, float* row_norm, int32_t* counter, void* stream) {
+                     float* d_pos, float* d_neg, int64_t ld_dneg, float* row_norm, int32_t* counter, void* stream,
+                     const LogqRows* lq = nullptr) {
     BESS_REQUIRE(l, "loss: NULL descriptor");
     BESS_REQUIRE(l->kind >= BESS_LOSS_LOGSIGMOID && l->kind <= BESS_LOSS_SSCE, "loss: unknown kind %d", l->kind);
     BESS_REQUIRE(n_triple > 0 && n_neg > 0 && n_neg < (1ll << 31), "loss: bad sizes");
@@ -213,10 +252,24 @@ static int loss_impl(const bess_loss_desc* l, const float* pos, const float* neg
             });
         });
     };
-    with_constant<BESS_LOSS_LOGSIGMOID, BESS_LOSS_MARGIN, BESS_LOSS_SSCE>(l->kind, [&](auto kind) {
-        if constexpr (decltype(kind)::value == BESS_LOSS_SSCE) launch(kind, std::false_type{});
-        else with_flag(adv, [&](auto a) { launch(kind, a); });
-    });
+    if (lq) {
+        // the 16-byte classes read the log-proposals as they read the scores: aligned rows, a whole number of
+        // 4-column groups in front of them.  Anything else takes the 4-byte class.
+        const bool vec = reinterpret_cast<uintptr_t>(lq->logq) % 16 == 0 && lq->cols % 4 == 0 && (n_neg - lq->cols) % 4 == 0;
+        const int chunks = vec ? loss_chunks(grad, neg, n_neg, ld_neg, d_neg, ld_dneg) : 0;
+        with_constant<0, -1, 4, 12, 24>(chunks, [&](auto ch) {
+            with_flag(grad, [&](auto g) {
+                k_loss_rows_logq<decltype(g)::value, decltype(ch)::value><<<grid, 256, 0, st>>>(
+                    *l, pos, neg, n_triple, n_neg, ld_neg, weight, weight_len, row_loss, d_pos, d_neg, ld_dneg, row_norm,
+                    *lq, counter, loss);
+            });
+        });
+    } else {
+        with_constant<BESS_LOSS_LOGSIGMOID, BESS_LOSS_MARGIN, BESS_LOSS_SSCE>(l->kind, [&](auto kind) {
+            if constexpr (decltype(kind)::value == BESS_LOSS_SSCE) launch(kind, std::false_type{});
+            else with_flag(adv, [&](auto a) { launch(kind, a); });
+        });
+    }
     if (int e = check_launch("loss rows")) return e;
     if (counter) return BESS_OK;  // summed by the launch's last workgroup
     k_sum_rows<<<1, 1024, 0, st>>>(row_loss, n_triple, loss);
@@ -240,6 +293,26 @@ extern "C" int bess_loss_fwd_bwd_one_launch(const bess_loss_desc* l, const float
     BESS_REQUIRE(counter, "loss_one_launch: NULL counter");
     return loss_impl(l, pos, neg, n_triple, n_neg, ld_neg, weight, weight_len, row_loss, loss, d_pos, d_neg, ld_dneg,
                      row_norm, counter, stream);
+}
+
+extern "C" int bess_loss_fwd_bwd_logq(const bess_loss_desc* l, const float* pos, const float* neg, int64_t n_triple,
+                                      int64_t n_neg, int64_t ld_neg, const float* weight, int64_t weight_len,
+                                      float* row_loss, float* loss, float* d_pos, float* d_neg, int64_t ld_dneg,
+                                      float* row_norm, int32_t* counter, const float* logq, int64_t logq_rows,
+                                      int64_t logq_cols, int32_t ppp, float lead_logq, void* stream) {
+    BESS_REQUIRE(l, "loss_logq: NULL descriptor");
+    BESS_REQUIRE(l->kind == BESS_LOSS_SSCE, "loss_logq: only the sampled-softmax loss takes log-proposals, got kind %d",
+                 l->kind);
+    BESS_REQUIRE(logq, "loss_logq: NULL logq");
+    BESS_REQUIRE(logq_cols > 0 && logq_cols <= n_neg, "loss_logq: logq_cols %lld not in (0, n_neg]", (long long)logq_cols);
+    BESS_REQUIRE(logq_rows == 1 || logq_rows == 2 || logq_rows == n_triple,
+                 "loss_logq: logq_rows %lld not 1, 2 or n_triple", (long long)logq_rows);
+    if (logq_rows == 2)
+        BESS_REQUIRE(ppp >= 2 && (ppp % 2) == 0 && (n_triple % ppp) == 0,
+                     "loss_logq: 2 rows ('ht') need an even block size dividing n_triple");
+    const LogqRows lq{logq, logq_rows, logq_cols, ppp, lead_logq};
+    return loss_impl(l, pos, neg, n_triple, n_neg, ld_neg, weight, weight_len, row_loss, loss, d_pos, d_neg, ld_dneg,
+                     row_norm, counter, stream, &lq);
 }
 
 extern "C" int bess_ranks_from_scores(const float* pos, const float* cand, int64_t n_row, int64_t n_cand,

@@ -17,12 +17,17 @@ __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x
 // with 16-byte stores; CH = 0: any shape, the row is streamed from memory (cache) in each of the passes, 4 bytes per
 // lane; CH = -1: the same with 16-byte accesses (longer rows of the 16-byte-aligned shapes).
 // Returns d loss / d positive score (what d_pos[s] gets; in every lane - the fused S-row tail hands it on in registers).
-template <int KIND, bool ADV, bool GRAD, int CH>
+// LOGQ (sampled softmax over a non-uniform proposal, bess_loss_fwd_bwd_logq): every score is lowered by the log-proposal
+// of its candidate WHERE IT IS LOADED - lq[j - lead] for the columns j >= lead (lq: the triple's row of the table,
+// n_neg - lead entries), lead_logq for the leading ones - so everything after the load is shared; the loads of lq are
+// issued together with the score loads they belong to.  The 16-byte classes need lq 16-byte aligned and lead % 4 == 0.
+template <int KIND, bool ADV, bool GRAD, int CH, bool LOGQ = false>
 __device__ __forceinline__ float loss_row_impl(const bess_loss_desc& l, const float* __restrict__ pos,
                                               const float* __restrict__ neg, int64_t s, int64_t n_neg, int64_t ld_neg,
                                               const float* __restrict__ weight, int64_t weight_len,
                                               float* __restrict__ row_loss, float* __restrict__ d_pos,
-                                              float* __restrict__ d_neg, int64_t ld_dneg, float* __restrict__ row_norm) {
+                                              float* __restrict__ d_neg, int64_t ld_dneg, float* __restrict__ row_norm,
+                                              const float* __restrict__ lq = nullptr, int lead = 0, float lead_logq = 0.f) {
     const int lane = threadIdx.x & 63;
     const float* nr = neg + s * ld_neg;
     float* dn = GRAD ? d_neg + s * ld_dneg : nullptr;
@@ -38,6 +43,29 @@ __device__ __forceinline__ float loss_row_impl(const bess_loss_desc& l, const fl
             v[c] = j < n ? *reinterpret_cast<const float4*>(nr + j) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
+    // log-proposals of columns j .. j + 3 (j % 4 == 0, j < n)
+    auto lq4 = [&](int j) {
+        return j >= lead ? *reinterpret_cast<const float4*>(lq + (j - lead))
+                         : make_float4(lead_logq, lead_logq, lead_logq, lead_logq);
+    };
+    auto lowered = [](float4 x, float4 q) { return make_float4(x.x - q.x, x.y - q.y, x.z - q.z, x.w - q.w); };
+    // score j of the 4-byte class (both loads are issued whatever the column: the index stays inside the row of lq)
+    auto score1 = [&](int j) {
+        const float x = nr[j];
+        if (!LOGQ) return x;
+        const float q = lq[j >= lead ? j - lead : 0];
+        return x - (j >= lead ? q : lead_logq);
+    };
+    if (LOGQ && CH > 0) {
+        float4 q[CH > 0 ? CH : 1];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int j = (c * 64 + lane) * 4;
+            q[c] = j < n ? lq4(j) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[c] = lowered(v[c], q[c]);
+    }
     // f(score) for every score of the row
     auto sweep = [&](auto&& f) {
         if (CH > 0) {
@@ -52,14 +80,15 @@ __device__ __forceinline__ float loss_row_impl(const bess_loss_desc& l, const fl
             }
         } else if (CH < 0) {  // streamed, 16 bytes per lane
             for (int j = lane * 4; j < n; j += 256) {
-                const float4 x = *reinterpret_cast<const float4*>(nr + j);
+                float4 x = *reinterpret_cast<const float4*>(nr + j);
+                if (LOGQ) x = lowered(x, lq4(j));
                 f(x.x);
                 f(x.y);
                 f(x.z);
                 f(x.w);
             }
         } else {
-            for (int j = lane; j < n; j += 64) f(nr[j]);
+            for (int j = lane; j < n; j += 64) f(score1(j));
         }
     };
     // d_neg[j] = f(score[j])
@@ -72,11 +101,12 @@ __device__ __forceinline__ float loss_row_impl(const bess_loss_desc& l, const fl
             }
         } else if (CH < 0) {
             for (int j = lane * 4; j < n; j += 256) {
-                const float4 x = *reinterpret_cast<const float4*>(nr + j);
+                float4 x = *reinterpret_cast<const float4*>(nr + j);
+                if (LOGQ) x = lowered(x, lq4(j));
                 *reinterpret_cast<float4*>(dn + j) = make_float4(f(x.x), f(x.y), f(x.z), f(x.w));
             }
         } else {
-            for (int j = lane; j < n; j += 64) dn[j] = f(nr[j]);
+            for (int j = lane; j < n; j += 64) dn[j] = f(score1(j));
         }
     };
 

@@ -93,6 +93,7 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_loss_fwd_bwd),
     BESS_PLAN_FN(bess_loss_fwd_bwd_norm),
     BESS_PLAN_FN(bess_loss_fwd_bwd_one_launch),
+    BESS_PLAN_FN(bess_loss_fwd_bwd_logq),
     BESS_PLAN_FN(bess_topk_update),
     BESS_PLAN_FN(bess_topk_update_flagged),
     BESS_PLAN_FN(bess_topk_update_excl),
@@ -121,6 +122,7 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_normalize_rows_bwd),
     BESS_PLAN_FN(bess_sample_negatives),
     BESS_PLAN_FN(bess_sample_negatives_weighted),
+    BESS_PLAN_FN(bess_gather_negative_logq),
     BESS_PLAN_FN(bess_sample_bucket_indices),
     BESS_PLAN_FN(bess_lookup_triples),
     BESS_PLAN_FN(bess_gather_candidate_lists),

@@ -263,6 +263,31 @@ __global__ __launch_bounds__(256) void k_lookup_triples(const int32_t* __restric
     }
 }
 
+// `WeightedShardedNegativeSampler(return_logq=True)`: the log-proposal of every drawn negative, in the layout of the
+// scores it belongs to.  neg [step, src_count, n, B, K] are the drawn rows of source shards [src_begin, ...), block
+// [s, d] gathered from shard s; table [n, ld] = log_q.  For scoring shard d = dst_begin + i:
+//   out[step, i, b, j, k] = table[j, neg[step, j, d, b, k]]      (block [j, d] is scored on d)
+//   local sampling:       = table[d, neg[step, d, j, b, k]]      (block [d, j] is scored on d itself)
+// One thread per output element, 4-byte loads and stores; row ids are clamped into [0, ld).
+__global__ __launch_bounds__(256) void k_gather_negative_logq(const int32_t* __restrict__ neg,
+                                                              const float* __restrict__ table, int64_t ld, int64_t total,
+                                                              int64_t n, int64_t src_begin, int64_t src_count,
+                                                              int64_t dst_begin, int64_t dst_count, int64_t B, int64_t K,
+                                                              int local_sampling, float* __restrict__ out) {
+    for (int64_t o = blockIdx.x * 256ll + threadIdx.x; o < total; o += 256ll * gridDim.x) {
+        int64_t r = o;
+        const int64_t k = r % K; r /= K;
+        const int64_t j = r % n; r /= n;
+        const int64_t b = r % B; r /= B;
+        const int64_t d = dst_begin + r % dst_count;
+        const int64_t step = r / dst_count;
+        const int64_t src = local_sampling ? d : j, dst = local_sampling ? j : d;
+        int64_t row = neg[(((step * src_count + (src - src_begin)) * n + dst) * B + b) * K + k];
+        row = row < 0 ? 0 : (row >= ld ? ld - 1 : row);
+        out[o] = table[src * ld + row];
+    }
+}
+
 static inline U128 u128(const uint64_t* p) { return U128{p[0], p[1]}; }
 
 // `TripleBasedShardedNegativeSampler.__call__` (reference negative_sampler.py:422-477): the candidate lists
@@ -380,6 +405,35 @@ extern "C" int bess_sample_negatives_weighted(const bess_pcg64_state* gen, const
     dim3 grid(static_cast<unsigned>(blocks), static_cast<unsigned>(n_step));
     k_sample_negatives_weighted<<<grid, 256, 0, as_stream(stream)>>>(a);
     return check_launch("sample_negatives_weighted");
+}
+
+extern "C" int bess_gather_negative_logq(const int32_t* negatives, const float* log_q, int64_t ld_logq, int64_t n_step,
+                                         int32_t n_shard, int32_t src_begin, int32_t src_count, int32_t dst_begin,
+                                         int32_t dst_count, int64_t B, int64_t K, int32_t local_sampling, float* out,
+                                         void* stream) {
+    BESS_REQUIRE(n_step >= 0 && n_shard >= 0 && src_count >= 0 && dst_count >= 0 && B >= 0 && K >= 0,
+                 "gather_negative_logq: bad shape");
+    BESS_REQUIRE(src_begin >= 0 && static_cast<int64_t>(src_begin) + src_count <= n_shard && dst_begin >= 0 &&
+                     static_cast<int64_t>(dst_begin) + dst_count <= n_shard,
+                 "gather_negative_logq: shard ranges [%d, %lld) / [%d, %lld) outside %d shards", src_begin,
+                 static_cast<long long>(src_begin) + src_count, dst_begin, static_cast<long long>(dst_begin) + dst_count,
+                 n_shard);
+    if (n_step == 0 || n_shard == 0 || dst_count == 0 || B == 0 || K == 0) return BESS_OK;
+    // the blocks that are read: every source shard, or (local sampling) those of the scoring shards themselves
+    if (local_sampling)
+        BESS_REQUIRE(src_begin <= dst_begin && dst_begin + dst_count <= src_begin + src_count,
+                     "gather_negative_logq: local sampling needs the blocks of the scoring shards");
+    else
+        BESS_REQUIRE(src_begin == 0 && src_count == n_shard, "gather_negative_logq: needs the blocks of every source shard");
+    BESS_REQUIRE(negatives && log_q && out, "gather_negative_logq: NULL pointer");
+    BESS_REQUIRE(ld_logq >= 1, "gather_negative_logq: ld_logq = %lld", static_cast<long long>(ld_logq));
+    const int64_t total = n_step * dst_count * B * n_shard * K;
+    BESS_REQUIRE(total < (1ll << 40), "gather_negative_logq: output too large");
+    const unsigned blocks = static_cast<unsigned>(std::min<int64_t>(ceil_div(total, 256), 8192));
+    k_gather_negative_logq<<<blocks, 256, 0, as_stream(stream)>>>(negatives, log_q, ld_logq, total, n_shard, src_begin,
+                                                                  src_count, dst_begin, dst_count, B, K, local_sampling,
+                                                                  out);
+    return check_launch("gather_negative_logq");
 }
 
 extern "C" int bess_sample_bucket_indices(const bess_pcg64_state* gen, const uint64_t* jump_table, int64_t n_out,

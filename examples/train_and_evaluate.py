@@ -5,6 +5,7 @@ fused forward + backward + sparse update), then rank every entity for held-out
 queries and report filtered-free MRR / hits@10.
 
     python examples/train_and_evaluate.py [--n-shard 1] [--steps 400] [--scorer TransE] [--negative-weights degree]
+                                             [--loss ssce --proposal-correction]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -29,7 +30,7 @@ from besskge.batch_sampler import RandomShardedBatchSampler, RigidShardedBatchSa
 from besskge.bess import EmbeddingMovingBessKGE  # noqa: E402
 from besskge.dataset import KGDataset  # noqa: E402
 from besskge.device_sampler import DeviceBatchSampler  # noqa: E402
-from besskge.loss import LogSigmoidLoss  # noqa: E402
+from besskge.loss import LogSigmoidLoss, SampledSoftmaxCrossEntropyLoss  # noqa: E402
 from besskge.metric import Evaluation  # noqa: E402
 from besskge.negative_sampler import (  # noqa: E402
     PlaceholderNegativeSampler,
@@ -69,7 +70,14 @@ def main(argv=None) -> dict:
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--negative-weights", default="uniform", choices=["uniform", "degree"],
                     help="degree: negatives in proportion to (occurrences in the training triples) ** 0.75")
+    ap.add_argument("--loss", default="logsigmoid", choices=["logsigmoid", "ssce"],
+                    help="ssce: sampled-softmax cross entropy")
+    ap.add_argument("--proposal-correction", action="store_true",
+                    help="sampled softmax over degree-weighted negatives: lower every negative's logit by its "
+                         "log-proposal (needs --negative-weights degree and --loss ssce)")
     args = ap.parse_args(argv)
+    if args.proposal_correction and (args.negative_weights != "degree" or args.loss != "ssce"):
+        ap.error("--proposal-correction needs --negative-weights degree and --loss ssce")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
 
@@ -85,18 +93,21 @@ def main(argv=None) -> dict:
     else:
         fn = getattr(scoring, args.scorer)(True, sharding, args.n_relation, d)
 
-    # ---- training: shared ("flat") random negatives, log-sigmoid loss, Adam
+    # ---- training: shared ("flat") random negatives, log-sigmoid (or sampled-softmax) loss, Adam
     pts = PartitionedTripleSet.create_from_dataset(ds, "train", sharding, partition_mode="ht_shardpair")
     if args.negative_weights == "degree":
         ns = WeightedShardedNegativeSampler(degree_weights([train], args.n_entity), n_negative=64, sharding=sharding,
                                             seed=1, corruption_scheme="t", local_sampling=False,
-                                            flat_negative_format=True)
+                                            flat_negative_format=True, return_logq=args.proposal_correction)
     else:
         ns = RandomShardedNegativeSampler(n_negative=64, sharding=sharding, seed=1, corruption_scheme="t",
                                           local_sampling=False, flat_negative_format=True)
     bs = RandomShardedBatchSampler(pts, ns, shard_bs=512, batches_per_step=4, seed=2)
-    model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn,
-                                   loss_fn=LogSigmoidLoss(margin=6.0, negative_adversarial_sampling=True))
+    if args.loss == "ssce":
+        loss_fn = SampledSoftmaxCrossEntropyLoss(args.n_entity, proposal_correction=args.proposal_correction)
+    else:
+        loss_fn = LogSigmoidLoss(margin=6.0, negative_adversarial_sampling=True)
+    model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn)
     trainer = runtime.training_model(model, runtime.Options(device_iterations=bs.batches_per_step),
                                      runtime.Adam(lr=args.lr), device=dev)
     feed = DeviceBatchSampler(bs, dev)  # the numpy streams of `bs`, continued in HBM

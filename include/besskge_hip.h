@@ -443,6 +443,22 @@ int bess_loss_fwd_bwd_one_launch(const bess_loss_desc* l, const float* pos, cons
                                  float* loss, float* d_pos, float* d_neg, int64_t ld_dneg,
                                  float* row_norm, int32_t* counter, void* stream);
 
+/* Sampled softmax over a NON-UNIFORM proposal (negatives of `WeightedShardedNegativeSampler(return_logq=True)`;
+ * the reference has no such form): bess_loss_fwd_bwd_one_launch over the logits
+ *   [pos_s, neg[s, j] - lq(s, j) + l->ssce_shift],   lq(s, j) = logq[mrow(s), j - (n_neg - logq_cols)]
+ * for the LAST logq_cols columns and lead_logq for the columns in front of them (augmented in-batch candidates).
+ * logq is float [logq_rows, logq_cols], logq_rows = 1, 2 or n_triple and mrow(s) the rule of bess_mask_scores
+ * (ppp is read with 2 rows only); 0 < logq_cols <= n_neg.  Nothing outside [logq_rows, logq_cols] is read, neg is
+ * not modified, d_neg is the gradient w.r.t. neg.  Only l->kind == BESS_LOSS_SSCE.  counter may be NULL: two
+ * launches.  16-byte accesses when the scores allow them and logq, logq_cols and n_neg - logq_cols are 16-byte /
+ * 4-element aligned, 4-byte accesses otherwise. */
+int bess_loss_fwd_bwd_logq(const bess_loss_desc* l, const float* pos, const float* neg,
+                           int64_t n_triple, int64_t n_neg, int64_t ld_neg,
+                           const float* weight, int64_t weight_len, float* row_loss,
+                           float* loss, float* d_pos, float* d_neg, int64_t ld_dneg,
+                           float* row_norm, int32_t* counter, const float* logq, int64_t logq_rows,
+                           int64_t logq_cols, int32_t ppp, float lead_logq, void* stream);
+
 /* next-1 / K11 - streaming top-k (reference bess.py:771-822 loop body, 889-894):
  * merge the n_col candidates of every row into its running list of the kk best
  * (best_score / best_id [n_row, kk], sorted by descending score, in place).
@@ -799,6 +815,21 @@ int bess_sample_negatives_weighted(const bess_pcg64_state* gen, const uint64_t* 
                                    int32_t n_shard, int32_t src_begin, int32_t src_count, int64_t B, int64_t K,
                                    const int64_t* cum_weights, int64_t ld_cum, const int32_t* shard_counts,
                                    int32_t* out, void* stream);
+
+/* `WeightedShardedNegativeSampler(return_logq=True)`: the log-proposal of every drawn negative in the layout of
+ * the scores (what bess_loss_fwd_bwd_logq takes), a transposing gather in one launch for all steps.
+ * negatives int32 [n_step, src_count, n_shard, B, K]: the drawn rows of source shards [src_begin, src_begin +
+ * src_count) (bess_sample_negatives_weighted); log_q float [n_shard, ld_logq]: log(weight / shard total)
+ * (- log(n_shard) without local sampling) of every local row, 0 for rows that are never drawn.
+ * out float [n_step, dst_count, B, n_shard, K], for scoring shard d = dst_begin + i:
+ *   out[step, i, b, j, k] = log_q[j, negatives[step, j, d, b, k]]   (needs every source shard: src_begin = 0,
+ *                                                                    src_count = n_shard)
+ *   local_sampling:       = log_q[d, negatives[step, d, j, b, k]]   (needs the blocks of shards dst_begin ...)
+ * A row id outside [0, ld_logq) is clamped.  Any size 0: nothing is read or written. */
+int bess_gather_negative_logq(const int32_t* negatives, const float* log_q, int64_t ld_logq, int64_t n_step,
+                              int32_t n_shard, int32_t src_begin, int32_t src_count, int32_t dst_begin,
+                              int32_t dst_count, int64_t B, int64_t K, int32_t local_sampling, float* out,
+                              void* stream);
 
 /* `TripleBasedShardedNegativeSampler.__call__` (negative_sampler.py:422-477): per-step look-up of the fixed
  * candidate lists and their layout for the exchange.  table_h (int32 [n_list, n_neg_shard, list_len]: local
