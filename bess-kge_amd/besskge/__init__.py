@@ -37,6 +37,7 @@ from . import (  # noqa: E402,F401
     negative_sampler,
     pipeline,
     query,
+    regularizer,
     runtime,
     scoring,
     sharding,
@@ -56,6 +57,7 @@ __all__ = [
     "negative_sampler",
     "pipeline",
     "query",
+    "regularizer",
     "runtime",
     "scoring",
     "sharding",

@@ -233,6 +233,8 @@ SIGNATURES = {
     "bess_pertriple_tail_supported": [_MD, _i64],
     "bess_pertriple_tail": [_MD, _LD, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp,
                             _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "bess_regularize_triples": [_MD, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _f32, _vp, _vp],
     "bess_query_triple_fwd_jobs": [_MD, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, ctypes.POINTER(_vp),
                                    ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_i64), _vp],
     "bess_neg_score_shared_fwd_loss": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(KillDesc), _LD, _vp, _vp, _i64,
@@ -770,6 +772,64 @@ def pertriple_tail(d: ModelDesc, l: LossDesc, side: int, head: RowSource, tail: 
             d_rel_table.data_ptr(), counter.data_ptr())
     res = (loss.reshape(()), dp, dn, rows[0], rows[1])
     return res + (rows[2],) if want_d_query else res
+
+
+REG_ENTITY_MODULUS = 1  # BESS_REG_ENTITY_MODULUS
+REG_RELATION_MODULUS = 2  # BESS_REG_RELATION_MODULUS
+
+
+def regularize_triples(head: RowSource, tail: RowSource, rel_table: Optional[torch.Tensor],
+                       rel_idx: Optional[torch.Tensor], weight: torch.Tensor, p: float, entity_coef: float,
+                       relation_coef: float, loss_scale: float = 1.0, flags: int = 0,
+                       d_head: Optional[torch.Tensor] = None, d_tail: Optional[torch.Tensor] = None,
+                       d_rel_table: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
+                       loss_factor: float = 1.0) -> torch.Tensor:
+    """Lp / N3 penalty on the rows of the triples (`bess_regularize_triples`, one launch): returns the penalty [] f32;
+    its gradient is ADDED into `d_head`, `d_tail` [n, W] f32 and (atomically) `d_rel_table` - both None: the value
+    only - and `loss_factor` times the penalty into the scalar `loss`, if given.  `rel_table`, `rel_idx` and
+    `d_rel_table` may be None with `relation_coef == 0`."""
+    dev = _same_device([("head", head.base), ("head_idx", head.idx), ("tail", tail.base), ("tail_idx", tail.idx),
+                        ("relation_embedding", rel_table), ("relation", rel_idx), ("triple_weight", weight),
+                        ("d_head", d_head), ("d_tail", d_tail), ("d_rel_table", d_rel_table), ("loss", loss)])
+    W = int(head.base.shape[-1])
+    _rows(head.base, "head rows", W)
+    _rows(tail.base, "tail rows", W)
+    if tail.base.dtype != head.base.dtype:
+        raise TypeError("regularize_triples: head and tail rows differ in dtype")
+    n = len(head)
+    if len(tail) != n:
+        raise ValueError(f"{n} head rows but {len(tail)} tail rows")
+    d = ModelDesc()
+    d.dtype, d.width, d.rel_width = _dtype_code(head.base), W, W
+    if rel_table is not None:
+        d.rel_width = int(rel_table.shape[-1])
+        _rows(rel_table, "relation_embedding", d.rel_width)
+        if rel_table.dtype != head.base.dtype:
+            raise TypeError("regularize_triples: relation and entity rows differ in dtype")
+        if rel_idx is None:
+            raise ValueError("regularize_triples: relation rows without `rel_idx`")
+        _idx(rel_idx, "relation", n)
+    _f32(weight, "triple_weight")
+    for g, nm, shape in ((d_head, "d_head", (n, W)), (d_tail, "d_tail", (n, W)),
+                         (d_rel_table, "d_rel_table", tuple(rel_table.shape) if rel_table is not None else None)):
+        if g is not None:
+            _f32(g, nm)
+            if tuple(g.shape) != shape:
+                raise ValueError(f"regularize_triples: `{nm}` has shape {tuple(g.shape)}, expected {shape}")
+    if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1):
+        raise ValueError("regularize_triples: `loss` must be one float32")
+    n4 = (n + 3) // 4 * 4
+    small = torch.empty((n4 + 4,), dtype=torch.float32, device=dev)  # row terms | penalty
+    penalty = small[n4: n4 + 1]
+    counter = _counters(dev, 1)
+    _launch("bess_regularize_triples", dev, ctypes.byref(d), head.base.data_ptr(), _idx(head.idx, "head_idx"),
+            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr() if rel_table is not None else 0,
+            _idx(rel_idx, "relation"), n, weight.data_ptr(), weight.numel(), float(p), float(entity_coef),
+            float(relation_coef), float(loss_scale), int(flags), d_head.data_ptr() if d_head is not None else 0,
+            d_tail.data_ptr() if d_tail is not None else 0, d_rel_table.data_ptr() if d_rel_table is not None else 0,
+            small.data_ptr(), penalty.data_ptr(), loss.data_ptr() if loss is not None else 0, float(loss_factor),
+            counter.data_ptr())
+    return penalty.reshape(())
 
 
 def row_fits_registers(d: ModelDesc) -> bool:

@@ -36,6 +36,7 @@ from besskge import _native as nat
 from besskge._native import RowSource
 from besskge.collectives import ReplicaGroup, SingleProcessGroup
 from besskge.loss import BaseLossFunction, SampledSoftmaxCrossEntropyLoss
+from besskge.regularizer import EmbeddingRegularizer
 from besskge.negative_sampler import (
     ShardedNegativeSampler,
     TripleBasedShardedNegativeSampler,
@@ -201,6 +202,7 @@ class BessKGE(torch.nn.Module, ABC):
         evaluation: Optional[Any] = None,
         return_scores: bool = False,
         augment_negative: bool = False,
+        regularizer: Optional[EmbeddingRegularizer] = None,
     ) -> None:
         """
         :param negative_sampler: sampler of corrupting entities (only its
@@ -213,6 +215,10 @@ class BessKGE(torch.nn.Module, ABC):
         :param return_scores: return positive / negative scores.
         :param augment_negative: also use the other positives of the
             micro-batch as negatives (needs negative sample sharing).
+        :param regularizer: Lp / N3 penalty on the embeddings of the positive
+            triples (`besskge.regularizer.EmbeddingRegularizer`), added to the
+            loss of training steps and of `forward`; needs `loss_fn`.  None:
+            no step launches anything for it.
         """
         super().__init__()
         self.sharding = score_fn.sharding
@@ -222,6 +228,12 @@ class BessKGE(torch.nn.Module, ABC):
         self.evaluation = evaluation
         self.return_scores = return_scores
         self.augment_negative = augment_negative
+        self.regularizer = regularizer
+        if regularizer is not None:
+            if loss_fn is None:
+                raise ValueError("a regularizer is a term of the training loss: it needs loss_fn")
+            #: `flags` of `bess_regularize_triples` (refuses moduli on a scorer without [re | im] rows)
+            self._regularizer_flags = regularizer.modulus_flags(score_fn)
         if not (loss_fn or evaluation or return_scores):
             raise ValueError(
                 "Nothing to return. At least one of loss_fn,"
@@ -372,7 +384,11 @@ class BessKGE(torch.nn.Module, ABC):
         for b in batches:
             self._logq_rows(b)  # (refused before anything is scored)
         steps = self._score_replicas(batches, _StepContext(batches))
-        return [self._finish(st, b, want_grad=False)[0] for st, b in zip(steps, batches)]
+        outs = [self._finish(st, b, want_grad=False)[0] for st, b in zip(steps, batches)]
+        if self.regularizer is not None:
+            for st, b, out in zip(steps, batches, outs):
+                self._regularize(st, b, out)  # (the value only)
+        return outs
 
     # Two-phase form of forward_replicas for software pipelining over micro-batches:
     # `forward_begin` issues what the scoring has to wait for (row gathers and the collectives
@@ -468,6 +484,22 @@ class BessKGE(torch.nn.Module, ABC):
                     out["ranks"] = ranks
                 out["metrics"] = self.evaluation.stacked_metrics_from_ranks(ranks, tm)
         return out, d_pos, d_neg
+
+    def _regularize(self, st: _ReplicaStep, batch: _Batch, out: Dict[str, Any], scale: float = 1.0,
+                    dh: Optional[torch.Tensor] = None, dt: Optional[torch.Tensor] = None,
+                    d_rel: Optional[torch.Tensor] = None) -> None:
+        """The regulariser's ONE launch of a replica step (`bess_regularize_triples`), once per positive triple:
+        the penalty of the triples' rows - read where the step read them - weighted as the loss weighs the triples;
+        its gradient is added in place into the positives' gradient rows `dh`, `dt` [S, W] and into `d_rel`, before
+        they are handed to the update (none given: the value only).  The same launch adds the penalty to the loss
+        scalar: `out["loss"]` is fit + penalty, `out["regularization"]` the penalty."""
+        reg = self.regularizer
+        w = self._triple_weight(batch, st.table.device, scale)
+        penalty = nat.regularize_triples(
+            RowSource(st.table, st.head_idx), st.tail, self.score_fn.relation_embedding.data, st.rel_idx, w, reg.p,
+            reg.entity_coef, reg.relation_coef, float(self.loss_fn.loss_scale), self._regularizer_flags, dh, dt,
+            d_rel if dh is not None else None, loss=out["loss"], loss_factor=1.0 / scale)
+        out["regularization"] = penalty if scale == 1.0 else penalty / scale
 
     def _proposal_correction(self) -> bool:
         """Does the loss lower every negative's logit by its log-proposal (`negative_logq`)?  Such a step takes the
@@ -751,7 +783,11 @@ class BessKGE(torch.nn.Module, ABC):
         shared candidates of the own shard, query + positive score fused (so are their backwards), an update that
         coalesces per row (f16 shard or a stateful optimiser - plain SGD on fp32 rows adds its atomics straight to
         the table), full-size optimiser state, a backward that can add its candidate rows by row id, and a shard
-        whose fp32 image fits the scratch budget."""
+        whose fp32 image fits the scratch budget.  Not with a regulariser: its launch adds into the positives'
+        gradient rows `dh`, `dt`, which this path never forms - such steps coalesce their lists as they did before
+        the direct update existed."""
+        if self.regularizer is not None:
+            return False
         if st.n != 1 or len(st.groups) != 1 or not st.fused_qt:
             return False
         g = st.groups[0]
@@ -1487,6 +1523,8 @@ class EmbeddingMovingBessKGE(BessKGE):
             if not st.fused_qt:
                 dh, dt = fn.triple_bwd(RowSource(st.table, st.head_idx), st.tail, st.rel_idx, st.triple_ctx, d_pos,
                                        d_rel)
+                if self.regularizer is not None:
+                    self._regularize(st, b, out, grad_scale, dh, dt, d_rel)
                 sink(RowSource(st.table, st.head_idx), dh)
                 sink(st.tail, dt)
             # K4'/K5' + K6': negative scores
@@ -1539,6 +1577,8 @@ class EmbeddingMovingBessKGE(BessKGE):
                     else:
                         dh, dt = fn.query_triple_bwd(g.side, RowSource(st.table, st.head_idx), st.tail, st.rel_idx,
                                                      d_pos, dq, d_rel)
+                    if self.regularizer is not None and "regularization" not in out:  # once per triple, not per group
+                        self._regularize(st, b, out, grad_scale, dh, dt, d_rel)
                     sink(RowSource(st.table, st.head_idx), dh)
                     sink(st.tail, dt)
                 else:
@@ -1781,6 +1821,8 @@ class ScoreMovingBessKGE(BessKGE):
             d_scores.append(d_sc.contiguous())
             dh, dt = fn.triple_bwd(RowSource(st.table, st.head_idx), st.tail, st.rel_idx, st.triple_ctx, d_pos,
                                    d_rel)
+            if self.regularizer is not None:
+                self._regularize(st, b, out, grad_scale, dh, dt, d_rel)
             local_updates.append([(st.head_idx, dh)])
             d_tails.append(dt.reshape(n, st.ppp, W))
         # gradients of the scores I computed ([n(j), S, Nl]) and of my tail rows (C5'), one all-to-all

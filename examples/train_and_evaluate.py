@@ -6,6 +6,7 @@ queries and report filtered-free MRR / hits@10.
 
     python examples/train_and_evaluate.py [--n-shard 1] [--steps 400] [--scorer TransE] [--negative-weights degree]
                                              [--loss ssce --proposal-correction]
+                                             [--regularizer n3 --reg-coef 1e-3]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -39,6 +40,7 @@ from besskge.negative_sampler import (  # noqa: E402
     degree_weights,
 )
 from besskge.pipeline import AllScoresPipeline  # noqa: E402
+from besskge.regularizer import EmbeddingRegularizer  # noqa: E402
 from besskge.sharding import PartitionedTripleSet, Sharding  # noqa: E402
 
 
@@ -75,6 +77,10 @@ def main(argv=None) -> dict:
     ap.add_argument("--proposal-correction", action="store_true",
                     help="sampled softmax over degree-weighted negatives: lower every negative's logit by its "
                          "log-proposal (needs --negative-weights degree and --loss ssce)")
+    ap.add_argument("--regularizer", default="none", choices=["none", "n3", "l2", "l3"],
+                    help="penalty on the embeddings of the positive triples: n3 = cubed moduli (ComplEx-N3, "
+                         "DistMult-N3), l2 / l3 = squared / cubed coordinates")
+    ap.add_argument("--reg-coef", type=float, default=1e-3, help="coefficient of --regularizer")
     args = ap.parse_args(argv)
     if args.proposal_correction and (args.negative_weights != "degree" or args.loss != "ssce"):
         ap.error("--proposal-correction needs --negative-weights degree and --loss ssce")
@@ -107,7 +113,10 @@ def main(argv=None) -> dict:
         loss_fn = SampledSoftmaxCrossEntropyLoss(args.n_entity, proposal_correction=args.proposal_correction)
     else:
         loss_fn = LogSigmoidLoss(margin=6.0, negative_adversarial_sampling=True)
-    model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn)
+    regularizer = {"none": None, "n3": EmbeddingRegularizer.n3(args.reg_coef),
+                   "l2": EmbeddingRegularizer.lp(2, args.reg_coef), "l3": EmbeddingRegularizer.lp(3, args.reg_coef)
+                   }[args.regularizer]
+    model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)
     trainer = runtime.training_model(model, runtime.Options(device_iterations=bs.batches_per_step),
                                      runtime.Adam(lr=args.lr), device=dev)
     feed = DeviceBatchSampler(bs, dev)  # the numpy streams of `bs`, continued in HBM

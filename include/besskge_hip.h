@@ -751,6 +751,29 @@ int bess_pertriple_tail(const bess_model_desc* d, const bess_loss_desc* l, int32
                         int64_t ld_dneg, float* d_query, float* d_head, float* d_tail, float* d_rel_table,
                         int32_t* counter, void* stream);
 
+/* Embedding regulariser of a training step (the reference has none; Lacroix et al. 2018, "Canonical tensor
+ * decomposition for knowledge base completion": the per-triple, "weighted" nuclear p-norm - N3 is p = 3 on moduli):
+ *   penalty[0] = sum_i term_i,   term_i = c_i * (entity_coef * (Phi(h_i) + Phi(t_i)) + relation_coef * Phi_r(r_i)),
+ *   c_i = loss_scale * weight[weight_len == 1 ? 0 : i],   Phi(x) = sum_k |x_k|^p over the row's scalars, or - with
+ * the row's modulus flag - sum_k (x_k^2 + x_{d+k}^2)^(p/2) over the d = width / 2 pairs of a [re(d) | im(d)] row.
+ * Rows are named as bess_score_triple_bwd names them (idx NULL: row i); of `d` only dtype, width and rel_width are
+ * read (relation rows of any width: PairRE's 2 d, RotatE's d).  The gradient of term_i is ADDED to row i of d_head /
+ * d_tail [n_triple, W] f32 - what a backward of the step has left there - and, with fp32 atomics, to row rel_idx[i]
+ * of d_rel_table [n_rel, Wr]: 0 where a coordinate (a modulus) is 0.  d_head == d_tail == NULL: the value only.
+ * relation_coef == 0: rel_table, rel_idx and d_rel_table are not touched and may be NULL.  p = 1, 2, 3 take no powf.
+ * row_terms: [n_triple] scratch; the launch's last workgroup sums it in a fixed order (penalty[0] is bitwise
+ * reproducible) and, with loss_inout != NULL, does loss_inout[0] += loss_factor * penalty[0].  ticket: int32
+ * [BESS_TICKET_INTS], zero on entry, left zero.  BESS_EINVAL: p < 1 or not finite, a negative coefficient, a modulus
+ * flag on an odd width, weight_len not 1 or n_triple, exactly one of d_head / d_tail. */
+#define BESS_REG_ENTITY_MODULUS 1
+#define BESS_REG_RELATION_MODULUS 2
+int bess_regularize_triples(const bess_model_desc* d, const void* head_base, const int32_t* head_idx,
+                            const void* tail_base, const int32_t* tail_idx, const void* rel_table,
+                            const int32_t* rel_idx, int64_t n_triple, const float* weight, int64_t weight_len,
+                            float p, float entity_coef, float relation_coef, float loss_scale, int32_t flags,
+                            float* d_head, float* d_tail, float* d_rel_table, float* row_terms, float* penalty,
+                            float* loss_inout, float loss_factor, int32_t* ticket, void* stream);
+
 /* The same pass for queries whose negatives are spread over several shards (ScoreMoving: each shard
  * scores the gathered queries against its own rows).  bess_neg_score_pertriple_fwd_partials writes the
  * scores and leaves the per-item partials (m_i, l_i, acc_i) of the online softmax in state_ml / state_acc
