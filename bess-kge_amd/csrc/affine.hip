@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "segment_pass.h"
 
 namespace bess {
 
@@ -553,7 +554,7 @@ struct AffSegArgs {
     int d;
     int nch;
     int normalize;
-    const int32_t* long_segs;    // optional: rows with more than BESS_SEGMENT_CAP references (segments.hip)
+    const int32_t* long_segs;    // optional: rows with more than BESS_SEGMENT_CAP references (segment_pass.h)
     float p;                     // the norm of the P == 2 kernels (any p != 1)
 };
 
@@ -656,7 +657,7 @@ __global__ __launch_bounds__(256) void k_aff_grad_segments(AffSegArgs a, float* 
     }
 }
 
-// Rows with more than BESS_SEGMENT_CAP references, as k_long_segments (segments.hip): slices of the
+// Rows with more than BESS_SEGMENT_CAP references (ticket protocol: segment_pass.h, seg_count_slice): slices of the
 // references are shared by all groups, the partial d score / d c_p meet in long_grad[li, :] through float
 // atomics, and the group that adds a row's last slice reads the sum back, applies the normalisation
 // backward, writes the row out and leaves the scratch row zero.
@@ -700,14 +701,8 @@ __global__ __launch_bounds__(256) void k_aff_long_segments(AffSegArgs a, float* 
                         for (int v = 0; v < VEC; ++v) atomicAdd(sum + p * a.d + c * VEC + v, dc[p][it][v]);
                     }
                 }
-            __threadfence();
-            int old = 0;
-            if (g == 0) old = atomicAdd(long_cnt + li, 1);
-            old = __shfl(old, lane & 48, 64);
-            if ((old + 1) % parts != 0) continue;
-            // the last arriver puts the counter back to zero: the scratch can serve the next launch as it is
-            if (g == 0) __hip_atomic_store(long_cnt + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __threadfence();
+            if ((seg_count_slice(long_cnt + li, lane, g) + 1) % parts != 0) continue;
+            seg_last_slice(long_cnt + li, g);
 #pragma unroll
             for (int p = 0; p < NPART; ++p)
 #pragma unroll
@@ -716,11 +711,7 @@ __global__ __launch_bounds__(256) void k_aff_long_segments(AffSegArgs a, float* 
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) {
                         dc[p][it][v] = 0.f;
-                        if (c < a.nch) {
-                            float* sp = sum + p * a.d + c * VEC + v;
-                            dc[p][it][v] = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(sp, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
+                        if (c < a.nch) dc[p][it][v] = seg_take(sum + p * a.d + c * VEC + v);
                     }
                 }
             aff_seg_finish<T, VEC, IT, NPART>(a, g, ev, inv, dc, seg, row, grad_seg, table_rw, lr);
@@ -728,43 +719,33 @@ __global__ __launch_bounds__(256) void k_aff_long_segments(AffSegArgs a, float* 
     }
 }
 
-int affine_grad_segments(const bess_model_desc* d, const float* query, void* table, int64_t n_neg,
-                         const float* d_out, int64_t ld_dout, const int32_t* refs_sorted, const int32_t* seg_rows,
-                         const int32_t* seg_offsets, const int32_t* n_seg, int64_t max_seg, float* grad_seg,
-                         float fused_sgd_lr, const int32_t* long_segs, int64_t long_cap, float* long_grad,
-                         int32_t* long_count, hipStream_t st) {
+int affine_grad_segments(const bess_model_desc* d, const SegRefs& r, const SegPass& ps, hipStream_t st) {
     const int n_part = d->reserved[0];
     const int dd = d->width / n_part;
     const int vec = part_vec_of(dd);
-    AffSegArgs a{query, table, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg, static_cast<int>(n_neg),
-                 dd, dd / vec, d->reserved[1] & 1, long_segs, static_cast<float>(d->norm_p)};
+    const AffSegArgs a{r.query, r.table, r.d_out, r.ld_dout, r.refs, r.seg_rows, r.seg_offsets, r.n_seg, r.n_neg,
+                       dd, dd / vec, d->reserved[1] & 1, r.long_segs, r.p};
     const int it = static_cast<int>(ceil_div(a.nch, 16));
-    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16));
-    // lgrad: the slices of the long segments (k_aff_long_segments), else one group per row
-    auto launch = [&](unsigned blocks, float* lgrad, int32_t* lcnt, int32_t cap) {
+    return launch_segment_pass(r, ps, 1, "neg_pertriple_grad_segments (affine)", [&](unsigned blocks, bool long_tier) {
         const bool ok = dispatch_row_class<PartRows>(d->dtype, vec, it, [&](auto c) {
             using C = decltype(c);
             using T = typename C::T;
-            T* rw = static_cast<T*>(table);
+            T* rw = static_cast<T*>(r.table);
             with_constant<1, 2>(n_part, [&](auto np) {
                 with_constant<1, 2>(d->norm_p, [&](auto p) {
                     constexpr int NPART = decltype(np)::value, P = decltype(p)::value;
-                    if (lgrad)
-                        k_aff_long_segments<T, C::VEC, C::IT, NPART, P>
-                            <<<blocks, 256, 0, st>>>(a, lgrad, lcnt, cap, grad_seg, rw, fused_sgd_lr);
+                    if (long_tier)
+                        k_aff_long_segments<T, C::VEC, C::IT, NPART, P><<<blocks, 256, 0, st>>>(
+                            a, ps.long_grad, ps.long_count, static_cast<int32_t>(ps.long_cap), ps.grad_seg, rw,
+                            ps.fused_sgd_lr);
                     else
                         k_aff_grad_segments<T, C::VEC, C::IT, NPART, P>
-                            <<<blocks, 256, 0, st>>>(a, grad_seg, rw, fused_sgd_lr);
+                            <<<blocks, 256, 0, st>>>(a, ps.grad_seg, rw, ps.fused_sgd_lr);
                 });
             });
         });
         return ok ? BESS_OK : fail(BESS_EUNSUPPORTED, "affine scorers: part of %d scalars too wide", a.d);
-    };
-    if (int rc = launch(grid, nullptr, nullptr, 0)) return rc;
-    // the rows left out above, by all groups together (usually none)
-    if (long_segs)
-        if (int rc = launch(1024u, long_grad, long_count, static_cast<int32_t>(long_cap))) return rc;
-    return check_launch("neg_pertriple_grad_segments (affine)");
+    });
 }
 
 // ---------------------------------------------------------------------------

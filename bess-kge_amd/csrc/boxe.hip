@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "segment_pass.h"
 
 namespace bess {
 
@@ -353,7 +354,7 @@ int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float*
 // reference (q, k) of the segment contributes d score / d e recomputed from query[q] (its six
 // vectors) and d_out[q, k] - the arithmetic of k_box_bwd's d_neg, summed on chip instead of through
 // an [n_query * n_neg, 2 d] tensor and atomics.  Rows with more than BESS_SEGMENT_CAP references go
-// to the whole grid in slices (k_box_long_segments), as in segments.hip.
+// to the whole grid in slices (k_box_long_segments; the ticket protocol is segment_pass.h: seg_count_slice).
 struct BoxSegArgs {
     const float* query;          // [n_query, 6 d]
     const void* table;
@@ -515,14 +516,8 @@ __global__ __launch_bounds__(256) void k_box_long_segments(BoxSegArgs a, float* 
                         for (int v = 0; v < VEC; ++v) atomicAdd(sum + p * a.d + c * VEC + v, acc[p][it][v]);
                     }
                 }
-            __threadfence();
-            int old = 0;
-            if (g == 0) old = atomicAdd(long_cnt + li, 1);
-            old = __shfl(old, lane & 48, 64);
-            if ((old + 1) % parts != 0) continue;
-            // the last arriver puts the counter back to zero: the scratch can serve the next launch as it is
-            if (g == 0) __hip_atomic_store(long_cnt + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __threadfence();
+            if ((seg_count_slice(long_cnt + li, lane, g) + 1) % parts != 0) continue;
+            seg_last_slice(long_cnt + li, g);
 #pragma unroll
             for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -531,11 +526,7 @@ __global__ __launch_bounds__(256) void k_box_long_segments(BoxSegArgs a, float* 
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) {
                         acc[p][it][v] = 0.f;
-                        if (c < a.nch) {
-                            float* sp = sum + p * a.d + c * VEC + v;
-                            acc[p][it][v] = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            __hip_atomic_store(sp, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
+                        if (c < a.nch) acc[p][it][v] = seg_take(sum + p * a.d + c * VEC + v);
                     }
                 }
             box_seg_store<T, VEC, IT>(a, g, ev, acc, seg, row, grad_seg, table_rw, lr);
@@ -543,42 +534,33 @@ __global__ __launch_bounds__(256) void k_box_long_segments(BoxSegArgs a, float* 
     }
 }
 
-int boxe_grad_segments(const bess_model_desc* d, const float* query, void* table, int64_t n_neg, const float* d_out,
-                       int64_t ld_dout, const int32_t* refs_sorted, const int32_t* seg_rows,
-                       const int32_t* seg_offsets, const int32_t* n_seg, int64_t max_seg, float* grad_seg,
-                       float fused_sgd_lr, const int32_t* long_segs, int64_t long_cap, float* long_grad,
-                       int32_t* long_count, hipStream_t st) {
+int boxe_grad_segments(const bess_model_desc* d, const SegRefs& r, const SegPass& ps, hipStream_t st) {
     const int dd = d->width / 2;
     const int vec = part_vec_of(dd);
-    BoxSegArgs a{query, table, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg, static_cast<int>(n_neg),
-                 dd, dd / vec, long_segs, static_cast<float>(d->norm_p)};
+    const BoxSegArgs a{r.query, r.table, r.d_out, r.ld_dout, r.refs, r.seg_rows, r.seg_offsets, r.n_seg, r.n_neg,
+                       dd, dd / vec, r.long_segs, r.p};
     const int it = static_cast<int>(ceil_div(a.nch, 16));
-    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16));
-    // lgrad: the slices of the long segments (k_box_long_segments), else one group per row
-    auto launch = [&](unsigned blocks, float* lgrad, int32_t* lcnt, int32_t cap) {
+    return launch_segment_pass(r, ps, 1, "neg_pertriple_grad_segments (BoxE)", [&](unsigned blocks, bool long_tier) {
         const bool ok = dispatch_row_class<PartRows>(d->dtype, vec, it, [&](auto c) {
             using C = decltype(c);
             using T = typename C::T;
-            T* rw = static_cast<T*>(table);
+            T* rw = static_cast<T*>(r.table);
             with_constant<1, 2>(d->norm_p, [&](auto p) {
                 with_constant<0, 1, 2, 3>(d->reserved[0] & 3, [&](auto fl) {  // bit 0 = tanh, bit 1 = per dimension
                     constexpr int P = decltype(p)::value;
                     constexpr bool TH = decltype(fl)::value & 1, PD = decltype(fl)::value & 2;
-                    if (lgrad)
-                        k_box_long_segments<T, C::VEC, C::IT, P, TH, PD>
-                            <<<blocks, 256, 0, st>>>(a, lgrad, lcnt, cap, grad_seg, rw, fused_sgd_lr);
+                    if (long_tier)
+                        k_box_long_segments<T, C::VEC, C::IT, P, TH, PD><<<blocks, 256, 0, st>>>(
+                            a, ps.long_grad, ps.long_count, static_cast<int32_t>(ps.long_cap), ps.grad_seg, rw,
+                            ps.fused_sgd_lr);
                     else
                         k_box_grad_segments<T, C::VEC, C::IT, P, TH, PD>
-                            <<<blocks, 256, 0, st>>>(a, grad_seg, rw, fused_sgd_lr);
+                            <<<blocks, 256, 0, st>>>(a, ps.grad_seg, rw, ps.fused_sgd_lr);
                 });
             });
         });
         return ok ? BESS_OK : fail(BESS_EUNSUPPORTED, BOX_TOO_WIDE, a.d);
-    };
-    if (int rc = launch(grid, nullptr, nullptr, 0)) return rc;
-    if (long_segs)
-        if (int rc = launch(1024u, long_grad, long_count, static_cast<int32_t>(long_cap))) return rc;
-    return check_launch("neg_pertriple_grad_segments (BoxE)");
+    });
 }
 
 }  // namespace bess

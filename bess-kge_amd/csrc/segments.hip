@@ -21,6 +21,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.h"
+#include "segment_pass.h"
 
 namespace bess {
 
@@ -249,7 +250,6 @@ static hipError_t cub_sizes(int64_t n, CubSizes* cs) {
 // index - stable sort by row, unique rows, offsets, long-row list - in ONE workgroup and one
 // launch.  The device-wide pipeline above is ~17 launches of 4-5 us each, which is all latency at
 // this size (and sits between backward and update of a step with a stateful optimiser).
-constexpr int SEG_CAP_FOR_SMALL = BESS_SEGMENT_CAP;
 constexpr int SMALL_T = 1024, SMALL_N = SMALL_T * 15;  // up to 15,360 references (2, 4 or 15 per thread)
 
 // The row ids to index may sit in several lists (heads, tails, negatives as the sampler handed them over):
@@ -326,7 +326,7 @@ __device__ __forceinline__ void small_segment_index(SmallIndexTemp<SMALL_I>& sh,
     if (!long_segs) return;
     __syncthreads();  // offsets written by this workgroup are visible to it
     for (int s2 = t; s2 < total; s2 += SMALL_T) {
-        if (seg_offsets[s2 + 1] - seg_offsets[s2] > SEG_CAP_FOR_SMALL) {
+        if (seg_offsets[s2 + 1] - seg_offsets[s2] > SEG_CAP) {
             const int li = atomicAdd(&sh.n_long, 1);
             if (li < long_cap) long_segs[1 + li] = s2;
         }
@@ -470,8 +470,7 @@ struct SegArgs {
 // slower.  Segments longer than SEG_CAP are therefore left out of the per-row pass and handled by the
 // whole grid: every group takes slices of SEG_CAP references, partial sums meet in a scratch row through
 // float atomics, a last small kernel applies / stores the row.  (Rows below the cap stay on the
-// atomic-free, bitwise reproducible path.)
-constexpr int SEG_CAP = BESS_SEGMENT_CAP;
+// atomic-free, bitwise reproducible path.)  SEG_CAP: segment_pass.h
 
 __global__ void k_find_long_segments(const int32_t* __restrict__ seg_offsets, const int32_t* __restrict__ n_seg,
                                      int32_t* __restrict__ long_segs, int32_t capacity) {
@@ -713,15 +712,9 @@ __global__ __launch_bounds__(256) void k_long_segments(SegArgs a, float* __restr
                     for (int v = 0; v < VEC; ++v) atomicAdd(sum + c * VEC + v, acc[it][v]);
                 }
             }
-            __threadfence();  // this group's adds are performed before its slice is counted
-            int old = 0;
-            if (g == 0) old = atomicAdd(long_cnt + li, 1);
-            old = __shfl(old, lane & 48, 64);  // from the first lane of the 16-lane group
-            if ((old + 1) % parts != 0) continue;
-            // the last arriver puts the counter back to zero: the scratch can serve the next launch as it is
-            if (g == 0) __hip_atomic_store(long_cnt + li, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __threadfence();
-            // last slice of the row: every partial sum is in (device-scope loads: past the L1)
+            if ((seg_count_slice(long_cnt + li, lane, g) + 1) % parts != 0) continue;
+            seg_last_slice(long_cnt + li, g);
+            // last slice of the row: every partial sum is in
             float tot[IT][VEC];
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
@@ -729,11 +722,7 @@ __global__ __launch_bounds__(256) void k_long_segments(SegArgs a, float* __restr
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) {
                     tot[it][v] = 0.f;
-                    if (c < a.nch) {
-                        float* sp = sum + c * VEC + v;
-                        tot[it][v] = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(sp, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
+                    if (c < a.nch) tot[it][v] = seg_take(sum + c * VEC + v);
                 }
             }
             seg_finish<T, VEC, IT>(a, g, seg, row, ev, tot, grad_seg, table_rw, lr);
@@ -1232,19 +1221,16 @@ static int grad_segments_impl(const bess_model_desc* d, const float* query, int6
     BESS_REQUIRE(ld_dout >= n_neg && max_seg > 0, "grad_segments: bad leading dimension / max_seg");
     BESS_REQUIRE(opt.o.kind < 0 || d->scorer <= BESS_COMPLEX,
                  "step_segments: the fused optimiser step exists for TransE / RotatE / DistMult / ComplEx");
-    if (d->scorer == BESS_AFFINE)
-        return affine_grad_segments(d, query, table, n_neg, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg,
-                                    max_seg, grad_seg, fused_sgd_lr, long_segs, long_cap, long_grad, long_count,
-                                    as_stream(stream));
-    if (d->scorer == BESS_BOXE)
-        return boxe_grad_segments(d, query, table, n_neg, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg,
-                                  max_seg, grad_seg, fused_sgd_lr, long_segs, long_cap, long_grad, long_count,
-                                  as_stream(stream));
+    hipStream_t st = as_stream(stream);
+    const SegRefs refs{query, table, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg,
+                       static_cast<int>(n_neg), long_segs, static_cast<float>(d->norm_p)};
+    const SegPass pass{max_seg, grad_seg, fused_sgd_lr, long_cap, long_grad, long_count};
+    if (d->scorer == BESS_AFFINE) return affine_grad_segments(d, refs, pass, st);
+    if (d->scorer == BESS_BOXE) return boxe_grad_segments(d, refs, pass, st);
     BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "grad_segments: scorer %d has no segmented form", d->scorer);
     const int W = d->width;
     const int vec = vec_of(d);
     const int red = reduce_of(d);
-    hipStream_t st = as_stream(stream);
     // Every reference re-reads its query row, so the pass streams n_ref * W floats out of an
     // [n_query, W] matrix: 8 MiB for 4096 x 512, twice an XCD's L2 - the rows then come from the
     // Infinity Cache at its ~9 TB/s.  The gradient is elementwise in the column (except the p = 2
@@ -1271,9 +1257,13 @@ static int grad_segments_impl(const bess_model_desc* d, const float* query, int6
     // (1024 f32 / 2048 f16 scalars) are windowed for this reason alone; the p = 2 norm needs the whole row
     if (red != RED_L2 && win > 16 * unit) win = 16 * unit;
     const int64_t sz = scalar_bytes_of(d);
-    // one launch per window of `win` columns (n_conc of them side by side); lgrad: the slices of the long segments
-    auto launch_windows = [&](int win, int n_conc, unsigned grid, float* lgrad, int32_t* lcnt, int32_t cap) {
-        return for_each_window(W, win, vec, n_conc, [&](const ColWindow& w) {
+    // whole rows for the long tier, unless they are wider than a group's registers (windows as above; the scratch rows
+    // and the counters are left zero by every launch, so the windows can share them)
+    const int lwin = (red != RED_L2 && W > 16 * unit) ? 16 * unit : W;
+    // one launch per window of `win` columns (n_conc of them side by side), of `lwin` columns in the long tier
+    return launch_segment_pass(refs, pass, n_conc, "neg_pertriple_grad_segments", [&](unsigned grid, bool long_tier) {
+        const int nc = long_tier ? 1 : n_conc;
+        return for_each_window(W, long_tier ? lwin : win, vec, nc, [&](const ColWindow& w) {
             char* tab = static_cast<char*>(table) + w.col0 * sz;
             SegOpt wopt = opt;  // the window's columns of the state tables and of the extra gradients
             wopt.state1 = w.at(wopt.state1);
@@ -1281,36 +1271,24 @@ static int grad_segments_impl(const bess_model_desc* d, const float* query, int6
             wopt.xsum = w.at(wopt.xsum);
             const SegArgs a{query + w.col0, tab, d_out, ld_dout, refs_sorted, seg_rows, seg_offsets, n_seg,
                             static_cast<int>(n_neg), W, w.nch, is_distance(d->scorer) ? -1.f : 1.f, long_segs, wopt,
-                            static_cast<float>(d->norm_p), n_conc, w.cols / n_conc};
+                            static_cast<float>(d->norm_p), nc, w.cols / nc};
             float* gs = w.at(grad_seg);
-            float* lg = w.at(lgrad);
             const bool ok = dispatch_row_class<NativeRows>(d->dtype, vec, w.it, [&](auto c) {
                 using C = decltype(c);
                 using T = typename C::T;
                 T* rw = reinterpret_cast<T*>(tab);
                 with_constant<RED_DOT, RED_L1, RED_L2>(red, [&](auto r) {
                     constexpr int RED = decltype(r)::value;
-                    if (lg)
-                        k_long_segments<T, C::VEC, C::IT, RED>
-                            <<<grid, 256, 0, st>>>(a, lg, lcnt, cap, gs, rw, fused_sgd_lr);
+                    if (long_tier)
+                        k_long_segments<T, C::VEC, C::IT, RED><<<grid, 256, 0, st>>>(
+                            a, w.at(long_grad), long_count, static_cast<int32_t>(long_cap), gs, rw, fused_sgd_lr);
                     else
                         k_pertriple_grad_segments<T, C::VEC, C::IT, RED><<<grid, 256, 0, st>>>(a, gs, rw, fused_sgd_lr);
                 });
             });
             return ok ? BESS_OK : fail(BESS_EUNSUPPORTED, "grad_segments: row of %d scalars too wide", W);
         });
-    };
-    // 16 segments per 256-thread workgroup; grid-stride over the (device-side) segment count
-    const unsigned grid = static_cast<unsigned>(n_conc * std::min<int64_t>(ceil_div(max_seg, 16), 256 * 16 / n_conc));
-    if (int rc = launch_windows(win, n_conc, grid, nullptr, nullptr, 0)) return rc;
-    if (long_segs) {  // the rows left out above (usually none: one launch that finds nothing to do)
-        // whole rows, unless they are wider than a group's registers (windows as above; the scratch rows and the
-        // counters are left zero by every launch, so the windows can share them)
-        const int lwin = (red != RED_L2 && W > 16 * unit) ? 16 * unit : W;
-        // (1024 workgroups: 16 K groups share the slices)
-        if (int rc = launch_windows(lwin, 1, 1024u, long_grad, long_count, static_cast<int32_t>(long_cap))) return rc;
-    }
-    return check_launch("neg_pertriple_grad_segments");
+    });
 }
 
 static OptArgs opt_args(const bess_opt_desc* o) {
