@@ -42,6 +42,7 @@ from besskge.negative_sampler import (
     TripleBasedShardedNegativeSampler,
 )
 from besskge.scoring import BaseScoreFunction
+from besskge.update_state import UpdateState
 
 BAD_NEGATIVE_SCORE = -50000.0
 
@@ -264,6 +265,8 @@ class BessKGE(torch.nn.Module, ABC):
         #: position of each hosted shard inside `entity_embedding` (dim 0)
         self._shard_slot: Optional[Dict[int, int]] = None
         self._map_cache: Dict[Any, torch.Tensor] = {}
+        #: optimiser state and update scratch kept between training steps (besskge.update_state)
+        self.update_state = UpdateState()
 
     # ------------------------------------------------------------------ setup
     @property
@@ -570,37 +573,15 @@ class BessKGE(torch.nn.Module, ABC):
         plain = not hasattr(optimizer, "kind") or optimizer.is_plain_sgd
         return plain, float(optimizer.lr) if hasattr(optimizer, "lr") else float(optimizer)
 
-    def _opt_state(self, table: torch.Tensor, n_state: int, state_rows: Optional[int] = None) -> Dict[str, Any]:
-        """Lazily allocated per-row optimiser state of one table.  `state_rows` (the optimiser's
-        `state_rows` option; only for tables with more rows than that): paged state - pools of that
-        many rows plus a row -> state-row map, rows get a state row the first time they are stepped
-        (a 128 GB shard cannot carry Adam's two fp32 tables of its own size)."""
-        if not hasattr(self, "_optimizer_state"):
-            self._optimizer_state: Dict[int, Dict[str, Any]] = {}
-        st = self._optimizer_state.setdefault(table.data_ptr(), dict(step=0, s=[]))
-        paged = state_rows is not None and int(state_rows) < table.shape[0]
-        if paged and "slot_map" not in st and n_state > 0:
-            st["capacity"] = int(state_rows)
-            st["slot_map"] = torch.full((table.shape[0],), -1, dtype=torch.int32, device=table.device)
-            st["slot_counter"] = torch.zeros((1,), dtype=torch.int32, device=table.device)
-        shape = (st["capacity"], table.shape[1]) if "slot_map" in st else tuple(table.shape)
-        while len(st["s"]) < n_state:
-            st["s"].append(torch.zeros(shape, dtype=torch.float32, device=table.device))
-        return st
-
     def optimizer_state_rows_used(self) -> Dict[int, Tuple[int, int]]:
         """{table pointer: (state rows asked for so far, capacity)} of the tables with paged optimiser
         state; asked > capacity means rows are being stepped without state (raise `state_rows`)."""
-        out = {}
-        for key, st in getattr(self, "_optimizer_state", {}).items():
-            if "slot_map" in st:
-                out[key] = (int(st["slot_counter"].item()), st["capacity"])
-        return out
+        return self.update_state.rows_used()
 
     def _assign_state_rows(self, table: torch.Tensor, seg: Any, keep: Optional[torch.Tensor] = None) -> None:
-        st = getattr(self, "_optimizer_state", {}).get(table.data_ptr())
-        if st is not None and "slot_map" in st:
-            nat.assign_state_rows(seg, st["slot_map"], st["slot_counter"], st["capacity"], keep)
+        st = self.update_state.get(table)
+        if st is not None and st.paged:
+            nat.assign_state_rows(seg, st.slot_map, st.slot_counter, st.capacity, keep)
 
     def _opt_desc(self, opt: Any, table: torch.Tensor) -> Tuple[Any, Optional[torch.Tensor], Optional[torch.Tensor]]:
         """(descriptor, state1, state2) of one optimiser step on `table` (advances its step count)."""
@@ -608,36 +589,36 @@ class BessKGE(torch.nn.Module, ABC):
             n_state = 1 if opt.momentum != 0.0 else 0
         else:
             n_state = 1 if opt.kind == nat.OPT_ADAGRAD else 2
-        prev = getattr(self, "_optimizer_state", {}).get(table.data_ptr())
-        if prev is not None and prev.get("kind", opt.kind) != opt.kind:
+        prev = self.update_state.get(table)
+        if prev is not None and prev.kind is not None and prev.kind != opt.kind:
             # the table was stepped (or its state loaded from a checkpoint) under another optimiser: state tensors
             # mean something else there (a momentum buffer is not Adam's first moment)
-            if prev["s"]:
+            if prev.s:
                 raise RuntimeError(
-                    f"besskge: this table's optimiser state belongs to optimiser kind {prev['kind']} (0 SGD, 1 Adagrad, "
+                    f"besskge: this table's optimiser state belongs to optimiser kind {prev.kind} (0 SGD, 1 Adagrad, "
                     f"2 Adam; e.g. loaded from a checkpoint), the step is taken with kind {opt.kind}")
-            prev["step"] = 0  # stateless so far (plain SGD): the new optimiser counts its own steps
-            prev.pop("step_dev", None)
-        state = self._opt_state(table, n_state, getattr(opt, "state_rows", None))
-        state["kind"] = opt.kind
-        state["step"] += 1
+            prev.step = 0  # stateless so far (plain SGD): the new optimiser counts its own steps
+            prev.step_dev = None
+        state = self.update_state.table_state(table, n_state, getattr(opt, "state_rows", None))
+        state.kind = opt.kind
+        state.step += 1
         o = nat.OptDesc()
-        o.kind, o.step, o.lr = opt.kind, state["step"], float(opt.lr)
-        if "slot_map" in state:
-            o.slot_map = state["slot_map"].data_ptr()
-        if getattr(self, "_device_step", False) and opt.kind == nat.OPT_ADAM:
+        o.kind, o.step, o.lr = opt.kind, state.step, float(opt.lr)
+        if state.paged:
+            o.slot_map = state.slot_map.data_ptr()
+        if self.update_state.device_step and opt.kind == nat.OPT_ADAM:
             # hipGraph replay (runtime.Options.use_graphs): the launch is recorded once, so the step count of
             # Adam's bias correction lives on the device and the increment is part of the recorded step
-            if "step_dev" not in state:
-                state["step_dev"] = torch.zeros((1,), dtype=torch.int32, device=table.device)
+            if state.step_dev is None:
+                state.step_dev = torch.zeros((1,), dtype=torch.int32, device=table.device)
             # (a call of the library, not a torch operator: the increment is then part of a recorded plan too)
-            nat.step_prologue([(state["step_dev"], state["step_dev"], 1)])
-            o.step_ptr = state["step_dev"].data_ptr()
+            nat.step_prologue([(state.step_dev, state.step_dev, 1)])
+            o.step_ptr = state.step_dev.data_ptr()
         o.momentum = float(getattr(opt, "momentum", 0.0))
         o.beta1, o.beta2 = float(getattr(opt, "beta1", 0.9)), float(getattr(opt, "beta2", 0.999))
         o.eps = float(getattr(opt, "eps", 0.0))
         o.weight_decay = float(getattr(opt, "weight_decay", 0.0))
-        s = state["s"]
+        s = state.s
         return o, (s[0] if n_state > 0 else None), (s[1] if n_state > 1 else None)
 
     def _apply_optimizer(self, opt: Any, table: torch.Tensor, contributions: List[Tuple[torch.Tensor, torch.Tensor]],
@@ -655,7 +636,7 @@ class BessKGE(torch.nn.Module, ABC):
             seg, grads = self._match_ahead(ahead, ids, grads)
         if seg is None:
             seg = nat.SegmentIndex(torch.cat(ids).contiguous(), table.shape[0],
-                                   scratch=self.__dict__.setdefault("_seg_scratch", {}))
+                                   scratch=self.update_state.seg_scratch)
         o, s1, s2 = self._opt_desc(opt, table)
         self._assign_state_rows(table, seg)
         if len(grads) > nat.MAX_ROW_LISTS:
@@ -755,7 +736,7 @@ class BessKGE(torch.nn.Module, ABC):
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 out[id(st)] = (plan, nat.SegmentIndex(torch.cat(plan).contiguous(), st.table.shape[0],
-                                                      scratch=self.__dict__.setdefault("_seg_scratch", {})))
+                                                      scratch=self.update_state.seg_scratch))
         return out
 
     #: row ids the step prologue's single workgroup indexes; longer lists go to the side stream
@@ -772,11 +753,7 @@ class BessKGE(torch.nn.Module, ABC):
     pertriple_tail = True
 
     def _direct_scratch(self, table: torch.Tensor) -> Any:
-        held = self.__dict__.setdefault("_direct_acc", {})
-        key = (table.data_ptr(), tuple(table.shape))
-        if key not in held:
-            held[key] = nat.DirectAccumulator(table)
-        return held[key]
+        return self.update_state.direct_scratch(table)
 
     def _direct_ok(self, st: _ReplicaStep, optimizer: Any, desc: Any) -> bool:
         """Does this step's shard update go through `bess_direct_update`?  One shard in the process, one group of
@@ -851,7 +828,7 @@ class BessKGE(torch.nn.Module, ABC):
         if plan is not None and len(plan) > nat.MAX_ROW_LISTS:
             plan = None
         seg = nat.step_prologue(jobs, plan or (), st.table.shape[0], st.table.shape[1],
-                                self.__dict__.setdefault("_seg_scratch", {}))
+                                self.update_state.seg_scratch)
         st.jobs = None
         return (plan, seg) if plan is not None else None
 
@@ -897,12 +874,9 @@ class BessKGE(torch.nn.Module, ABC):
     def _apply_optimizer_dense(self, opt: Any, table: torch.Tensor, grad: torch.Tensor) -> None:
         """Optimiser step on every row of a small replicated table (relation table, dense parameters):
         the rows are their own segments - nothing to sort or sum."""
-        cache = self.__dict__.setdefault("_dense_segments", {})
-        key = (table.data_ptr(), int(table.shape[0]))
-        if key not in cache:
-            cache[key] = nat.identity_segments(int(table.shape[0]), table.device)
+        segments = self.update_state.identity_segments(table)
         o, s1, s2 = self._opt_desc(opt, table)
-        nat.apply_segments_opt(o, table, cache[key], grad.contiguous(), s1, s2)
+        nat.apply_segments_opt(o, table, segments, grad.contiguous(), s1, s2)
 
     def _apply_optimizer_fused(self, opt: Any, desc: nat.ModelDesc, table: torch.Tensor, g: _NegGroup,
                                go: torch.Tensor, seg: Any, extras: List[Tuple[torch.Tensor, torch.Tensor]],
@@ -940,7 +914,7 @@ class BessKGE(torch.nn.Module, ABC):
         side.wait_stream(torch.cuda.current_stream(dev))  # the row ids are ready; nothing later is waited for
         with torch.cuda.stream(side):
             return nat.SegmentIndex(g.neg.idx, st.table.shape[0], width=st.table.shape[1],
-                                    scratch=self.__dict__.setdefault("_seg_scratch", {}))
+                                    scratch=self.update_state.seg_scratch)
 
     def _prefetch_segment_indices(self, steps: List[_ReplicaStep], ctx: _StepContext) -> Dict[int, Any]:
         """The inverted indices of per-triple negatives only depend on the sampled indices: they are
@@ -979,7 +953,7 @@ class BessKGE(torch.nn.Module, ABC):
                 k = seen.get((table.data_ptr(), g.side), 0)
                 seen[(table.data_ptr(), g.side)] = k + 1
                 by_slot.setdefault((table.data_ptr(), g.side, k), []).append((table, g, go))
-        scratch = self.__dict__.setdefault("_seg_scratch", {})
+        scratch = self.update_state.seg_scratch
         for items in by_slot.values():
             table, g0, go0 = items[0]
             if len(items) == 1:

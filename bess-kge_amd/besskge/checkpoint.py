@@ -26,6 +26,8 @@ from typing import Any, Dict, Union
 import numpy as np
 import torch
 
+from besskge.update_state import TableState, UpdateState
+
 #: bytes moved per copy; one pinned buffer of this size is the only host memory used
 CHUNK_BYTES = 256 << 20
 
@@ -90,96 +92,71 @@ def _write_json(path: str, obj: Dict[str, Any]) -> None:
     os.replace(tmp, path)
 
 
-def _step_of(st: Dict[str, Any]) -> int:
-    """Optimiser steps taken so far.  Under hipGraph replay only the device-side count advances (the host
-    count is restored after the capture): the larger of the two is the truth."""
-    step = int(st["step"])
-    if "step_dev" in st:
-        step = max(step, int(st["step_dev"].item()))
-    return step
-
-
-def _save_table(model: Any, table: torch.Tensor, stem: Path, chunk_bytes: int) -> None:
+def _save_table(states: UpdateState, table: torch.Tensor, stem: Path, chunk_bytes: int) -> None:
     save_rows(table, f"{stem}.npy", chunk_bytes)
-    st = getattr(model, "_optimizer_state", {}).get(table.data_ptr())
+    st = states.get(table)
     meta: Dict[str, Any] = dict(step=0, n_state=0, paged=False)
     if st is not None:
-        meta.update(step=_step_of(st), n_state=len(st["s"]), paged="slot_map" in st)
-        if "kind" in st:
-            meta["kind"] = int(st["kind"])  # BESS_OPT_*: a state tensor means different things to different optimisers
-        for i, s in enumerate(st["s"]):
+        meta.update(step=st.true_step(), n_state=len(st.s), paged=st.paged)
+        if st.kind is not None:
+            meta["kind"] = int(st.kind)  # BESS_OPT_*: a state tensor means different things to different optimisers
+        for i, s in enumerate(st.s):
             save_rows(s, f"{stem}.state{i}.npy", chunk_bytes)
-        if "slot_map" in st:
-            save_rows(st["slot_map"], f"{stem}.slots.npy", chunk_bytes)
-            meta.update(capacity=int(st["capacity"]), counter=int(st["slot_counter"].item()))
-        if "step_dev" in st:
-            meta["step_dev"] = _step_of(st)
+        if st.paged:
+            save_rows(st.slot_map, f"{stem}.slots.npy", chunk_bytes)
+            meta.update(capacity=int(st.capacity), counter=int(st.slot_counter.item()))
+        if st.step_dev is not None:
+            meta["step_dev"] = st.true_step()
     _write_json(f"{stem}.meta.json", meta)
 
 
-def _stale_graphs(model: Any) -> None:
-    """State tensors were replaced: hipGraphs recorded by a Runner hold the old addresses.  Runners compare
-    this counter with the one they recorded under and re-capture (`Runner._call_with_graphs`)."""
-    model.__dict__["_state_generation"] = model.__dict__.get("_state_generation", 0) + 1
-
-
-def _load_table(model: Any, table: torch.Tensor, stem: Path, chunk_bytes: int) -> None:
+def _load_table(states: UpdateState, table: torch.Tensor, stem: Path, chunk_bytes: int) -> None:
     load_rows(f"{stem}.npy", table, chunk_bytes)
     with open(f"{stem}.meta.json") as f:
         meta = json.load(f)
-    states = getattr(model, "_optimizer_state", None)
-    have = states.get(table.data_ptr()) if states is not None else None
+    have = states.get(table)
     dev = table.device
     paged = bool(meta["paged"])
     n_state, step = int(meta["n_state"]), int(meta["step"])
-    shape = (int(meta["capacity"]), table.shape[1]) if paged else tuple(table.shape)
-    if have is not None and n_state > 0 and "kind" in have and "kind" in meta and int(have["kind"]) != int(meta["kind"]):
+    capacity = int(meta["capacity"]) if paged else None
+    shape = (capacity, table.shape[1]) if paged else tuple(table.shape)
+    if have is not None and n_state > 0 and have.kind is not None and "kind" in meta and int(have.kind) != int(meta["kind"]):
         raise ValueError(
             f"{stem}: the checkpoint's optimiser state was written by optimiser kind {meta['kind']}, the live state "
-            f"belongs to kind {have['kind']} (0 SGD, 1 Adagrad, 2 Adam): its tensors mean something else there")
+            f"belongs to kind {have.kind} (0 SGD, 1 Adagrad, 2 Adam): its tensors mean something else there")
     fresh = n_state == 0 and step == 0  # a checkpoint without optimiser history: the live state starts over
-    if have is not None and ("slot_map" in have) == paged and (len(have["s"]) == n_state or fresh) \
-            and all(tuple(x.shape) == shape for x in have["s"]) and (not paged or have["capacity"] == int(meta["capacity"])):
-        # same layout as the live state: read into the existing tensors - a hipGraph recorded on them (tables,
-        # moments, slot map, device-side step count) stays valid.  (Fewer state tensors in the file than live -
-        # a momentum checkpoint under Adam - is NOT the same layout: zeroed moments under the checkpoint's step
-        # count would skip Adam's bias correction, first updates ~30x too large.)
-        for i, x in enumerate(have["s"]):
+    if have is not None and have.same_layout(n_state, paged, capacity, shape, fresh):
+        # read into the existing tensors - a hipGraph recorded on them (tables, moments, slot map, device-side
+        # step count) stays valid
+        for i, x in enumerate(have.s):
             if i < n_state:
                 load_rows(f"{stem}.state{i}.npy", x, chunk_bytes)
             else:
                 x.zero_()
         if paged:
-            load_rows(f"{stem}.slots.npy", have["slot_map"], chunk_bytes)
-            have["slot_counter"].fill_(int(meta["counter"]))
-        have["step"] = step
-        if "step_dev" in have:
-            have["step_dev"].fill_(step)
+            load_rows(f"{stem}.slots.npy", have.slot_map, chunk_bytes)
+            have.slot_counter.fill_(int(meta["counter"]))
+        have.step = step
+        if have.step_dev is not None:
+            have.step_dev.fill_(step)
         elif "step_dev" in meta:
-            have["step_dev"] = torch.full((1,), step, dtype=torch.int32, device=dev)
-            _stale_graphs(model)
+            have.step_dev = torch.full((1,), step, dtype=torch.int32, device=dev)
+            states.stale()
         return
-    if have is not None:
-        states.pop(table.data_ptr(), None)
-        _stale_graphs(model)
-    if n_state == 0 and step == 0:
+    states.drop(table)
+    if fresh:
         return
-    if states is None:
-        model._optimizer_state = states = {}
-    st: Dict[str, Any] = dict(step=step, s=[])
+    st = TableState(step, int(meta["kind"]) if "kind" in meta else None)
     if paged:
-        st["capacity"] = int(meta["capacity"])
-        st["slot_map"] = load_rows(f"{stem}.slots.npy", torch.empty((table.shape[0],), dtype=torch.int32, device=dev),
-                                   chunk_bytes)
-        st["slot_counter"] = torch.full((1,), int(meta["counter"]), dtype=torch.int32, device=dev)
+        st.capacity = capacity
+        st.slot_map = load_rows(f"{stem}.slots.npy", torch.empty((table.shape[0],), dtype=torch.int32, device=dev),
+                                chunk_bytes)
+        st.slot_counter = torch.full((1,), int(meta["counter"]), dtype=torch.int32, device=dev)
     for i in range(n_state):
-        st["s"].append(load_rows(f"{stem}.state{i}.npy", torch.empty(shape, dtype=torch.float32, device=dev), chunk_bytes))
+        st.s.append(load_rows(f"{stem}.state{i}.npy", torch.empty(shape, dtype=torch.float32, device=dev), chunk_bytes))
     if "step_dev" in meta:
-        st["step_dev"] = torch.full((1,), step, dtype=torch.int32, device=dev)
-    if "kind" in meta:
-        st["kind"] = int(meta["kind"])
-    states[table.data_ptr()] = st
-    _stale_graphs(model)
+        st.step_dev = torch.full((1,), step, dtype=torch.int32, device=dev)
+    states.replace(table, st)
 
 
 def _dense_state(model: Any) -> Dict[str, torch.Tensor]:
@@ -200,16 +177,15 @@ def save_checkpoint(model: Any, directory: Union[str, Path], chunk_bytes: int = 
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
     for shard in group.local_shards:
-        _save_table(model, model._local_table(shard), directory / f"entity_shard{shard}", chunk_bytes)
+        _save_table(model.update_state, model._local_table(shard), directory / f"entity_shard{shard}", chunk_bytes)
     if 0 in group.local_shards:
-        _save_table(model, model.score_fn.relation_embedding.data, directory / "relation", chunk_bytes)
-        states = getattr(model, "_optimizer_state", {})
+        _save_table(model.update_state, model.score_fn.relation_embedding.data, directory / "relation", chunk_bytes)
         opt = {}
         for name, p in model.score_fn.named_parameters():
-            st = states.get(p.data_ptr())
+            st = model.update_state.get(p)
             if st is not None and name not in ("entity_embedding", "relation_embedding"):
-                opt[name] = dict(step=_step_of(st), s=[x.detach().cpu() for x in st["s"]],
-                                 step_dev=_step_of(st) if "step_dev" in st else -1)
+                opt[name] = dict(step=st.true_step(), s=[x.detach().cpu() for x in st.s],
+                                 step_dev=st.true_step() if st.step_dev is not None else -1)
         tmp = directory / f"dense.pt.tmp{os.getpid()}"
         torch.save(dict(tensors={k: v.detach().cpu() for k, v in _dense_state(model).items()}, optimizer=opt), tmp)
         os.replace(tmp, directory / "dense.pt")
@@ -223,13 +199,13 @@ def load_checkpoint(model: Any, directory: Union[str, Path], chunk_bytes: int = 
     """Read the shards hosted by this process back in place and restore optimiser state, step counts and paging.
     The tables keep their addresses.  Optimiser state of the same layout as the live one (same number of state
     tensors, same paging) is read into the existing tensors too, so a hipGraph a Runner recorded earlier stays
-    valid; where the layout differs the state objects are replaced and the model's `_state_generation` is bumped
+    valid; where the layout differs the state objects are replaced and `model.update_state.generation` is bumped
     - Runners drop the graphs they recorded under an older generation and capture again on their next call."""
     directory = Path(directory)
     group = model._group()
     for shard in group.local_shards:
-        _load_table(model, model._local_table(shard), directory / f"entity_shard{shard}", chunk_bytes)
-    _load_table(model, model.score_fn.relation_embedding.data, directory / "relation", chunk_bytes)
+        _load_table(model.update_state, model._local_table(shard), directory / f"entity_shard{shard}", chunk_bytes)
+    _load_table(model.update_state, model.score_fn.relation_embedding.data, directory / "relation", chunk_bytes)
     blob = torch.load(directory / "dense.pt", map_location="cpu", weights_only=True)
     dense, own = blob["tensors"], _dense_state(model)
     if set(dense) != set(own):
@@ -240,19 +216,18 @@ def load_checkpoint(model: Any, directory: Union[str, Path], chunk_bytes: int = 
     params = dict(model.score_fn.named_parameters())
     for name, st in blob["optimizer"].items():
         p = params[name]
-        if not hasattr(model, "_optimizer_state"):
-            model._optimizer_state = {}
-        have = model._optimizer_state.get(p.data_ptr())
-        if have is not None and len(have["s"]) == len(st["s"]) and all(
-                a.shape == b.shape for a, b in zip(have["s"], st["s"])) and (("step_dev" in have) == (st["step_dev"] >= 0)):
-            for a, b in zip(have["s"], st["s"]):
+        have = model.update_state.get(p)
+        shape = tuple(st["s"][0].shape) if st["s"] else ()
+        if have is not None and have.same_layout(len(st["s"]), False, None, shape, False) \
+                and ((have.step_dev is not None) == (st["step_dev"] >= 0)):
+            for a, b in zip(have.s, st["s"]):
                 a.copy_(b)
-            have["step"] = int(st["step"])
-            if "step_dev" in have:
-                have["step_dev"].fill_(int(st["step_dev"]))
+            have.step = int(st["step"])
+            if have.step_dev is not None:
+                have.step_dev.fill_(int(st["step_dev"]))
             continue
-        new: Dict[str, Any] = dict(step=int(st["step"]), s=[x.to(p.device) for x in st["s"]])
+        new = TableState(int(st["step"]))
+        new.s = [x.to(p.device) for x in st["s"]]
         if st["step_dev"] >= 0:
-            new["step_dev"] = torch.full((1,), int(st["step_dev"]), dtype=torch.int32, device=p.device)
-        model._optimizer_state[p.data_ptr()] = new
-        _stale_graphs(model)
+            new.step_dev = torch.full((1,), int(st["step_dev"]), dtype=torch.int32, device=p.device)
+        model.update_state.replace(p, new)

@@ -303,7 +303,7 @@ class Runner:
         if stateful:
             # the optimiser state lives in device tables the recorded kernels update in place; Adam's step
             # count moves to the device (BessKGE._opt_desc).  Hyper-parameters are recorded by value.
-            self.model._device_step = True
+            self.model.update_state.device_step = True
         # ONE graph per call: all `device_iterations` micro-batches are recorded back to back (as PopTorch runs
         # its device iterations inside one compiled program), reading their inputs from a static copy of the
         # whole call's batch - so a call costs one copy per input tensor and one graph launch, not one of each
@@ -313,9 +313,11 @@ class Runner:
         cache = self.__dict__.setdefault("_graphs", {})
         # the group destroys these graphs before its communicator goes (ReplicaGroup.release_graphs)
         self.group.register_graph_cache(cache)
-        generation = self.model.__dict__.get("_state_generation", 0)
+        generation = self.model.update_state.generation
         if self.__dict__.get("_graphs_generation", generation) != generation:
-            cache.clear()  # optimiser state tensors were replaced (checkpoint load): recorded addresses are stale
+            # optimiser state tensors were replaced (checkpoint load) or the segment scratch grew (the generation was
+            # noted before the recording: the first recording that grows it is made again): recorded addresses are stale
+            cache.clear()
         self.__dict__["_graphs_generation"] = generation
         if sig not in cache:
             static = {k: torch.empty(v.shape, dtype=v.dtype, device=self.device) for k, v in batch.items()}
@@ -361,12 +363,14 @@ class Runner:
                 "NativeGroup / MultiDeviceGroup (bess_comm_* / RCCL through the C ABI) - not c10d's DistributedGroup")
         stateful = self.optimizer is not None and not getattr(self.optimizer, "is_plain_sgd", True)
         if stateful:
-            self.model._device_step = True  # Adam's step count lives on the device (as under use_graphs)
+            self.model.update_state.device_step = True  # Adam's step count lives on the device (as under use_graphs)
         sig = (iters,) + tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(batch.items()))
         cache = self.__dict__.setdefault("_plans", {})
-        generation = self.model.__dict__.get("_state_generation", 0)
+        generation = self.model.update_state.generation
         if self.__dict__.get("_plans_generation", generation) != generation:
-            cache.clear()  # optimiser state tensors were replaced (checkpoint load): recorded addresses are stale
+            # optimiser state tensors were replaced (checkpoint load) or the segment scratch grew (the generation was
+            # noted before the recording: the first recording that grows it is made again): recorded addresses are stale
+            cache.clear()
         self.__dict__["_plans_generation"] = generation
         if sig not in cache:
             cache[sig] = self._record_plan(batch, iters)
@@ -533,12 +537,7 @@ class Runner:
         snap: Dict[str, Any] = dict(
             entity=fn.entity_embedding.data.clone(), relation=fn.relation_embedding.data.clone(),
             dense=[(p, p.data.clone()) for p in fn.dense_parameters()],
-            buffers=[(b, b.clone()) for b in fn.buffers()], opt={})
-        for key, st in getattr(self.model, "_optimizer_state", {}).items():
-            snap["opt"][key] = dict(step=st["step"], s=[t.clone() for t in st["s"]],
-                                    step_dev=st["step_dev"].clone() if "step_dev" in st else None,
-                                    paging=(st["slot_map"].clone(), st["slot_counter"].clone())
-                                    if "slot_map" in st else None)
+            buffers=[(b, b.clone()) for b in fn.buffers()], opt=self.model.update_state.snapshot())
         return snap
 
     def _restore_training_snapshot(self, snap: Dict[str, Any]) -> None:
@@ -549,27 +548,7 @@ class Runner:
             p.data.copy_(v)
         for b, v in snap["buffers"]:
             b.copy_(v)
-        for key, st in getattr(self.model, "_optimizer_state", {}).items():
-            old = snap["opt"].get(key)
-            # state tensors the warm-up created (or grew) go back to what they were: zero
-            st["step"] = old["step"] if old else 0
-            for i, t in enumerate(st["s"]):
-                if old and i < len(old["s"]):
-                    t.copy_(old["s"][i])
-                else:
-                    t.zero_()
-            if "slot_map" in st:  # paged state: which row owns which state row
-                if old and old.get("paging") is not None:
-                    st["slot_map"].copy_(old["paging"][0])
-                    st["slot_counter"].copy_(old["paging"][1])
-                else:
-                    st["slot_map"].fill_(-1)
-                    st["slot_counter"].zero_()
-            if "step_dev" in st:
-                if old and old["step_dev"] is not None:
-                    st["step_dev"].copy_(old["step_dev"])
-                else:
-                    st["step_dev"].fill_(st["step"])
+        self.model.update_state.restore(snap["opt"])
 
     def _split(self, batch: Dict[str, torch.Tensor], it: int) -> List[Dict[str, torch.Tensor]]:
         n = self.group.n_shard
@@ -693,6 +672,7 @@ class MultiDeviceRunner:
             # its own parameter / buffer / submodule tables; submodules - ConvE's network - copied), its own shard
             rep = copy.copy(model)
             rep.__dict__ = dict(model.__dict__)
+            rep.update_state = model.update_state.for_replica()
             rep._modules = dict(model._modules)
             rep._parameters = dict(model._parameters)
             rep._buffers = dict(model._buffers)

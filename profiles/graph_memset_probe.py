@@ -86,8 +86,8 @@ m_max = []
 for i in range(4):
     runner(**batches[i])
     torch.cuda.synchronize()
-    st = model._optimizer_state[model._local_table(0).data_ptr()]
-    m_max.append(float(st["s"][0].abs().max()))
+    st = model.update_state.get(model._local_table(0))
+    m_max.append(float(st.s[0].abs().max()))
 (counts,) = runner.graph_node_counts().values()
 print(json.dumps(dict(exp="B", build=mode, adam_m_max_per_step=m_max, nodes=counts,
                       verdict="stale" if max(m_max) > 1e3 else "clean")), flush=True)
@@ -110,8 +110,8 @@ m2, t2 = [], []
 for i in range(6):
     runner2(**batches2[i])
     torch.cuda.synchronize()
-    st = model2._optimizer_state[model2._local_table(0).data_ptr()]
-    m2.append(float(st["s"][0].abs().max()))
+    st = model2.update_state.get(model2._local_table(0))
+    m2.append(float(st.s[0].abs().max()))
     t2.append(float(model2.score_fn.entity_embedding.detach().abs().max()))
 (counts2,) = runner2.graph_node_counts().values()
 # the same six steps without a graph, from the same start: the reference trajectory

@@ -129,8 +129,8 @@ def test_rollback_in_a_live_process_under_graph_replay(tmp_path, warm):
         results[use_graphs] = (model.score_fn.entity_embedding.detach().clone(),
                                model.score_fn.relation_embedding.detach().clone(), out["loss"].clone())
         # the step count went back with the tables (Adam's bias correction restarts from step 2, not 4)
-        st = model._optimizer_state[model._local_table(0).data_ptr()]
-        assert checkpoint._step_of(st) == 4
+        st = model.update_state.get(model._local_table(0))
+        assert st.true_step() == 4
     # Adam normalises by |g|: entries whose gradient cancels to ~0 take a full +-lr step whose sign depends on
     # the order of fp32 atomics (tests/test_accumulation.py) - a stale-address replay would leave the tables
     # where the rollback put them (off by whole steps everywhere), which this still catches
@@ -169,12 +169,12 @@ def test_state_of_another_optimiser_is_not_merged(tmp_path):
     with pytest.raises(RuntimeError, match="optimiser kind"):
         cold_runner(**batches[1])
     # a history-free checkpoint under live Adam: tables back, moments zero, step count 0 (bias correction restarts)
-    st = live._optimizer_state[live._local_table(0).data_ptr()]
-    ptrs = [x.data_ptr() for x in st["s"]]
+    st = live.update_state.get(live._local_table(0))
+    ptrs = [x.data_ptr() for x in st.s]
     checkpoint.load_checkpoint(live, fresh_dir, chunk_bytes=4096)
-    st = live._optimizer_state[live._local_table(0).data_ptr()]
-    assert [x.data_ptr() for x in st["s"]] == ptrs and checkpoint._step_of(st) == 0
-    assert all(float(x.abs().max()) == 0.0 for x in st["s"])
+    st = live.update_state.get(live._local_table(0))
+    assert [x.data_ptr() for x in st.s] == ptrs and st.true_step() == 0
+    assert all(float(x.abs().max()) == 0.0 for x in st.s)
     before = live.score_fn.entity_embedding.detach().clone()
     adam(**batches[1])
     step = (live.score_fn.entity_embedding.detach() - before).abs().max()

@@ -348,8 +348,8 @@ def test_paged_optimizer_state(dev, case, graphs):
         if rows is not None:
             (used, cap), = model.optimizer_state_rows_used().values()
             assert cap == 116 and 0 < used <= 116
-            st = next(v for v in model._optimizer_state.values() if "slot_map" in v)
-            assert all(tuple(t.shape) == (116, model.entity_embedding_size) for t in st["s"])
+            st = next(v for v in model.update_state.tables.values() if v.paged)
+            assert all(tuple(t.shape) == (116, model.entity_embedding_size) for t in st.s)
     torch.testing.assert_close(out[1], out[0], rtol=1e-5, atol=1e-6)
     if not graphs:
         model = build_model(c, dev)
@@ -411,7 +411,7 @@ def test_dense_optimizer_follows_torch_optim_step_for_step(dev, opt_name, case):
         assert float(solid.float().mean()) > 0.5
         torch.testing.assert_close(got[solid], ref[solid], rtol=2e-3, atol=1e-4)
     # the accumulator is left zero
-    for scratch in model._direct_acc.values():
+    for scratch in model.update_state.direct.values():
         assert float(scratch.acc.abs().max()) == 0.0
 
 

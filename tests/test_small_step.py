@@ -246,7 +246,7 @@ def test_training_step_through_the_direct_update_equals_the_indexed_path(dev, dt
         runner = runtime.training_model(model, runtime.Options(), opt, device=dev)
         losses = [float(runner(**b)["loss"]) for b in batches]
         torch.cuda.synchronize()
-        used = "_direct_acc" in model.__dict__
+        used = bool(model.update_state.direct)
         assert used == direct, "the direct update was (not) taken"
         out.append((model.score_fn.entity_embedding.detach().float().clone(),
                     model.score_fn.relation_embedding.detach().float().clone(), losses))
