@@ -401,6 +401,51 @@ def _f32(t: torch.Tensor, name: str) -> None:
         raise ValueError(f"`{name}` must be contiguous float32, got {t.dtype}")
 
 
+def _f32s(*named: Tuple[str, torch.Tensor]) -> None:
+    for name, t in named:
+        _f32(t, name)
+
+
+def _ptr(t: Optional[torch.Tensor]) -> int:
+    """Data pointer of `t`; 0 (NULL) for None."""
+    return 0 if t is None else t.data_ptr()
+
+
+def _mat(t: Optional[torch.Tensor], dtype: Any, msg: str, rows: Optional[Tuple[int, ...]] = None,
+         cols: Optional[int] = None, who: Optional[str] = None) -> Tuple[int, int, int]:
+    """(pointer, rows, columns) of a contiguous 2-D matrix of `dtype` (one, or a tuple of them) - the mask, id, flag
+    and map operands; (0, 0, 0) for None.  `rows` / `cols`: the row counts / the column count it may have.  Anything
+    else is a ValueError with the caller's text `msg`, behind "`who`: " if given (joined on this branch only)."""
+    if t is None:
+        return 0, 0, 0
+    if (t.dtype not in dtype if type(dtype) is tuple else t.dtype != dtype) or t.dim() != 2 or not t.is_contiguous() \
+            or (rows is not None and t.shape[0] not in rows) or (cols is not None and t.shape[1] != cols):
+        raise ValueError(msg if who is None else f"{who}: {msg}")
+    return t.data_ptr(), int(t.shape[0]), int(t.shape[1])
+
+
+_KILL_MASK = "negative_mask must be a contiguous 2-D bool tensor"
+
+
+def _carve_offsets(lengths: Sequence[int]) -> List[int]:
+    """Offsets, in elements of 4 bytes, of pieces of the given lengths laid out one after the other with every piece
+    on a 16-byte boundary; the last entry is the total."""
+    offs, at = [0], 0
+    for n in lengths:
+        at += (n + 3) // 4 * 4
+        offs.append(at)
+    return offs
+
+
+def _carve_f32(dev: torch.device, *lengths: int) -> List[torch.Tensor]:
+    """ONE allocation for several small float32 vectors (`_carve_offsets`): a step makes a handful of them per call,
+    and every torch.empty is host time.  Recorded graphs and plans hold addresses inside these buffers: the layout
+    is part of what a wrapper does."""
+    offs = _carve_offsets(lengths)
+    buf = torch.empty((offs[-1],), dtype=torch.float32, device=dev)
+    return [buf[o: o + n] for o, n in zip(offs, lengths)]
+
+
 def _row_count(base: torch.Tensor, idx: Optional[torch.Tensor]) -> int:
     return int(idx.numel()) if idx is not None else int(base.shape[0])
 
@@ -569,7 +614,7 @@ def _job_arrays(jobs: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], int]]
             raise ValueError(f"{who}: job targets must be contiguous tensors of 4-byte elements")
         if s_ is not None and (s_.element_size() != 4 or not s_.is_contiguous() or s_.numel() != d_.numel()):
             raise ValueError(f"{who}: a job's source must match its target")
-        dst[i], src[i], val[i], words[i] = d_.data_ptr(), (s_.data_ptr() if s_ is not None else None), int(v_), d_.numel()
+        dst[i], src[i], val[i], words[i] = d_.data_ptr(), _ptr(s_), int(v_), d_.numel()
     return dst, src, val, words
 
 
@@ -600,8 +645,7 @@ def query_triple_bwd(d: ModelDesc, side: int, head: RowSource, tail: RowSource, 
     """(d_head [n, W], d_tail [n, W]) of positive score and query together; accumulates into d_rel_table."""
     dev, n = _triple_operands(d, head, tail, rel_table, rel_idx)
     _same_device([("d_out", d_out), ("d_query", d_query), ("d_rel_table", d_rel_table), ("x", head.base)])
-    for t, nm in ((d_out, "d_out"), (d_query, "d_query"), (d_rel_table, "d_rel_table")):
-        _f32(t, nm)
+    _f32s(("d_out", d_out), ("d_query", d_query), ("d_rel_table", d_rel_table))
     if d_out.numel() != n or tuple(d_query.shape) != (n, d.width) or tuple(d_rel_table.shape) != tuple(rel_table.shape):
         raise ValueError("query_triple_bwd: gradient shapes do not match")
     dh = torch.empty((n, d.width), dtype=torch.float32, device=dev)
@@ -687,11 +731,10 @@ def neg_score_pertriple_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, n
     _f32(out, "out")
     if tuple(out.shape) != (nq, n_neg):
         raise ValueError("neg_score_pertriple_fwd: bad `out` shape")
-    ip, keep = _neg_idx_ptr(neg, dev)
+    ip, keep = _neg_idx_ptr(neg, dev)  # (`keep`: the index array lives to the end of the call)
     d = with_row_count(d, neg.base)
     _launch("bess_neg_score_pertriple_fwd", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), ip, n_neg,
             out.data_ptr(), n_neg)
-    del keep
     return out
 
 
@@ -713,25 +756,29 @@ def neg_score_pertriple_fwd_dq(d: ModelDesc, l: LossDesc, query: torch.Tensor, n
         _f32(pos, "pos")
         if pos.numel() != nq:
             raise ValueError("`pos` must have n_query entries")
+    out, dq, st_ml, st_acc = _partials_buffers(d, nq, n_neg, dev, want_dq=not defer)
+    ip, keep = _neg_idx_ptr(neg, dev)
+    if mask is not None:
+        _same_device([("mask", mask), ("query", query)])
+    mp, mrows, mcols = _mat(mask, (torch.bool, torch.uint8),
+                            "neg_score_pertriple_fwd_dq: `mask` must be a contiguous 2-D bool / uint8 tensor")
+    _launch("bess_neg_score_pertriple_fwd_dq_masked", dev, ctypes.byref(d), ctypes.byref(l), query.data_ptr(), nq,
+            neg.base.data_ptr(), ip, n_neg, _ptr(pos), weight.data_ptr(), weight.numel(), mp, mrows, mcols,
+            out.data_ptr(), n_neg, _ptr(dq), st_ml.data_ptr(), st_acc.data_ptr())
+    return out, ((st_ml, st_acc) if defer else dq)
+
+
+def _partials_buffers(d: ModelDesc, nq: int, n_neg: int, dev: torch.device, want_dq: bool = False
+                      ) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """(scores [nq, n_neg], d_query [nq, W] | None, state_ml [nq, items, 2], state_acc [nq, items, W]) of the fused
+    per-triple forwards, allocated in this order; `items`: the work items the library splits a query's negatives into."""
     items = ctypes.c_int32(0)
     _check(load().bess_neg_pertriple_items(ctypes.byref(d), nq, n_neg, ctypes.byref(items)), "bess_neg_pertriple_items")
     out = torch.empty((nq, n_neg), dtype=torch.float32, device=dev)
-    dq = None if defer else torch.empty((nq, d.width), dtype=torch.float32, device=dev)
+    dq = torch.empty((nq, d.width), dtype=torch.float32, device=dev) if want_dq else None
     st_ml = torch.empty((nq, items.value, 2), dtype=torch.float32, device=dev)
     st_acc = torch.empty((nq, items.value, d.width), dtype=torch.float32, device=dev)
-    ip, keep = _neg_idx_ptr(neg, dev)
-    mrows = mcols = 0
-    if mask is not None:
-        _same_device([("mask", mask), ("query", query)])
-        if mask.dtype not in (torch.bool, torch.uint8) or mask.dim() != 2 or not mask.is_contiguous():
-            raise ValueError("neg_score_pertriple_fwd_dq: `mask` must be a contiguous 2-D bool / uint8 tensor")
-        mrows, mcols = int(mask.shape[0]), int(mask.shape[1])
-    _launch("bess_neg_score_pertriple_fwd_dq_masked", dev, ctypes.byref(d), ctypes.byref(l), query.data_ptr(), nq,
-            neg.base.data_ptr(), ip, n_neg, pos.data_ptr() if pos is not None else 0, weight.data_ptr(), weight.numel(),
-            mask.data_ptr() if mask is not None else 0, mrows, mcols, out.data_ptr(), n_neg,
-            dq.data_ptr() if dq is not None else 0, st_ml.data_ptr(), st_acc.data_ptr())
-    del keep
-    return out, ((st_ml, st_acc) if defer else dq)
+    return out, dq, st_ml, st_acc
 
 
 def pertriple_tail_supported(d: ModelDesc, n_neg: int) -> bool:
@@ -749,18 +796,14 @@ def pertriple_tail(d: ModelDesc, l: LossDesc, side: int, head: RowSource, tail: 
     st_ml, st_acc = partials
     _same_device([("partials", st_ml), ("partials", st_acc), ("positive_score", pos), ("negative_score", neg),
                   ("triple_weight", weight), ("d_rel_table", d_rel_table), ("x", head.base)])
-    for t, nm in ((st_ml, "partials"), (st_acc, "partials"), (pos, "positive_score"), (neg, "negative_score"),
-                  (weight, "triple_weight"), (d_rel_table, "d_rel_table")):
-        _f32(t, nm)
+    _f32s(("partials", st_ml), ("partials", st_acc), ("positive_score", pos), ("negative_score", neg),
+          ("triple_weight", weight), ("d_rel_table", d_rel_table))
     N = int(neg.shape[1])
     items = int(st_ml.shape[1])
     if tuple(st_ml.shape) != (n, items, 2) or tuple(st_acc.shape) != (n, items, d.width) or pos.numel() != n \
             or neg.shape[0] != n or weight.numel() not in (1, n) or tuple(d_rel_table.shape) != tuple(rel_table.shape):
         raise ValueError("pertriple_tail: shapes do not match")
-    # ONE allocation for the small pieces (every piece starts on a 16-byte boundary)
-    n4 = (n + 3) // 4 * 4
-    small = torch.empty((2 * n4 + 4,), dtype=torch.float32, device=dev)
-    row_loss, dp, loss = small[:n], small[n4: n4 + n], small[2 * n4: 2 * n4 + 1]
+    row_loss, dp, loss = _carve_f32(dev, n, n, 1)
     dn = torch.empty((n, N), dtype=torch.float32, device=dev)
     rows = torch.empty((3 if want_d_query else 2, n, d.width), dtype=torch.float32, device=dev)
     counter = _counters(dev, 1)
@@ -818,17 +861,13 @@ def regularize_triples(head: RowSource, tail: RowSource, rel_table: Optional[tor
                 raise ValueError(f"regularize_triples: `{nm}` has shape {tuple(g.shape)}, expected {shape}")
     if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1):
         raise ValueError("regularize_triples: `loss` must be one float32")
-    n4 = (n + 3) // 4 * 4
-    small = torch.empty((n4 + 4,), dtype=torch.float32, device=dev)  # row terms | penalty
-    penalty = small[n4: n4 + 1]
+    row_terms, penalty = _carve_f32(dev, n, 1)
     counter = _counters(dev, 1)
     _launch("bess_regularize_triples", dev, ctypes.byref(d), head.base.data_ptr(), _idx(head.idx, "head_idx"),
-            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), rel_table.data_ptr() if rel_table is not None else 0,
-            _idx(rel_idx, "relation"), n, weight.data_ptr(), weight.numel(), float(p), float(entity_coef),
-            float(relation_coef), float(loss_scale), int(flags), d_head.data_ptr() if d_head is not None else 0,
-            d_tail.data_ptr() if d_tail is not None else 0, d_rel_table.data_ptr() if d_rel_table is not None else 0,
-            small.data_ptr(), penalty.data_ptr(), loss.data_ptr() if loss is not None else 0, float(loss_factor),
-            counter.data_ptr())
+            tail.base.data_ptr(), _idx(tail.idx, "tail_idx"), _ptr(rel_table), _idx(rel_idx, "relation"), n,
+            weight.data_ptr(), weight.numel(), float(p), float(entity_coef), float(relation_coef), float(loss_scale),
+            int(flags), _ptr(d_head), _ptr(d_tail), _ptr(d_rel_table), row_terms.data_ptr(), penalty.data_ptr(),
+            _ptr(loss), float(loss_factor), counter.data_ptr())
     return penalty.reshape(())
 
 
@@ -849,15 +888,10 @@ def neg_score_pertriple_fwd_partials(d: ModelDesc, l: LossDesc, query: torch.Ten
     `combine_dq_partials` turns into this shard's share of d loss / d query."""
     nq = int(query.shape[0])
     dev = _neg_operands(d, query, neg, nq * n_neg)
-    items = ctypes.c_int32(0)
-    _check(load().bess_neg_pertriple_items(ctypes.byref(d), nq, n_neg, ctypes.byref(items)), "bess_neg_pertriple_items")
-    out = torch.empty((nq, n_neg), dtype=torch.float32, device=dev)
-    st_ml = torch.empty((nq, items.value, 2), dtype=torch.float32, device=dev)
-    st_acc = torch.empty((nq, items.value, d.width), dtype=torch.float32, device=dev)
+    out, _, st_ml, st_acc = _partials_buffers(d, nq, n_neg, dev)
     ip, keep = _neg_idx_ptr(neg, dev)
     _launch("bess_neg_score_pertriple_fwd_partials", dev, ctypes.byref(d), ctypes.byref(l), query.data_ptr(), nq,
             neg.base.data_ptr(), ip, n_neg, out.data_ptr(), n_neg, st_ml.data_ptr(), st_acc.data_ptr())
-    del keep
     return out, (st_ml, st_acc)
 
 
@@ -905,8 +939,7 @@ def neg_score_pertriple_bwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, n
         dn = d_neg_rows
     ip, keep = _neg_idx_ptr(neg, dev)
     _launch("bess_neg_score_pertriple_bwd", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(), ip, n_neg,
-            d_out.data_ptr(), n_neg, dq.data_ptr() if want_d_query else 0, dn.data_ptr() if want_d_neg else 0)
-    del keep
+            d_out.data_ptr(), n_neg, _ptr(dq), _ptr(dn))
     return dq, (None if d_neg_rows is not None else dn)
 
 
@@ -925,8 +958,7 @@ def normalize_rows(neg: RowSource, n_part: int, normalize: bool) -> Tuple[torch.
 
 def normalize_rows_bwd(hat: torch.Tensor, inv: torch.Tensor, d_hat: torch.Tensor) -> torch.Tensor:
     dev = _same_device([("hat", hat), ("inv", inv), ("d_hat", d_hat)])
-    for t, name in ((hat, "hat"), (inv, "inv"), (d_hat, "d_hat")):
-        _f32(t, name)
+    _f32s(("hat", hat), ("inv", inv), ("d_hat", d_hat))
     if hat.shape != d_hat.shape or inv.shape[0] != hat.shape[0]:
         raise ValueError("normalize_rows_bwd: shape mismatch")
     out = torch.empty_like(hat)
@@ -957,6 +989,27 @@ def _range_flag(ws: Optional[torch.Tensor], range_flags: Optional[list]) -> None
         range_flags.append(ws[off: off + 4].view(torch.int32))
 
 
+def _workspace(query: str, d: ModelDesc, nq: int, n_neg: int, dev: torch.device) -> Tuple[Optional[torch.Tensor], int]:
+    """(scratch | None, its bytes) that the workspace query `query` asks for: the scratch of the split-fp16
+    matrix-core path (0 bytes for the other scorers / small shapes).  From torch's caching allocator, so it is
+    stream-ordered and safe under graph capture."""
+    ws_bytes = int(getattr(load(), query)(ctypes.byref(d), nq, n_neg))
+    return (torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None), ws_bytes
+
+
+def _kill_desc(kill: Optional[Tuple[int, bool, int, Optional[torch.Tensor]]], query: torch.Tensor) -> Optional[KillDesc]:
+    """`kill` = (diag_step, ht, ppp, mask [rows, cols] bool | None) as struct bess_kill_desc; None for None."""
+    if kill is None:
+        return None
+    diag_step, ht, ppp, mask = kill
+    kd = KillDesc()
+    kd.diag_step, kd.ht, kd.ppp = int(diag_step), int(bool(ht)), int(ppp)
+    if mask is not None:
+        _same_device([("negative_mask", mask), ("query", query)])
+        kd.mask, kd.mask_rows, kd.mask_cols = _mat(mask, torch.bool, _KILL_MASK)
+    return kd
+
+
 def neg_score_shared_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, pad_ld: bool = False,
                          kill: Optional[Tuple[int, bool, int, Optional[torch.Tensor]]] = None,
                          range_flags: Optional[list] = None) -> torch.Tensor:
@@ -971,28 +1024,14 @@ def neg_score_shared_fwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, pad_
         neg, _, _ = _affine_candidates(d, neg)
     ld = (n_neg + 3) // 4 * 4 if pad_ld else n_neg
     out = torch.empty((nq, ld), dtype=torch.float32, device=dev)
-    lib = load()
-    # scratch of the split-fp16 matrix-core path (0 for the other scorers / small shapes); from
-    # torch's caching allocator, so it is stream-ordered and safe under graph capture
-    ws_bytes = int(lib.bess_neg_score_shared_workspace(ctypes.byref(d), nq, n_neg))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
-    kd = None
-    if kill is not None:
-        diag_step, ht, ppp, mask = kill
-        kd = KillDesc()
-        kd.diag_step, kd.ht, kd.ppp = int(diag_step), int(bool(ht)), int(ppp)
-        if mask is not None:
-            _same_device([("negative_mask", mask), ("query", query)])
-            if mask.dtype != torch.bool or mask.dim() != 2 or not mask.is_contiguous():
-                raise ValueError("negative_mask must be a contiguous 2-D bool tensor")
-            kd.mask, kd.mask_rows, kd.mask_cols = mask.data_ptr(), int(mask.shape[0]), int(mask.shape[1])
-    wp = ws.data_ptr() if ws is not None else None
+    ws, ws_bytes = _workspace("bess_neg_score_shared_workspace", d, nq, n_neg, dev)
+    kd = _kill_desc(kill, query)
     if kd is None:
         _launch("bess_neg_score_shared_fwd_ws", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, wp, ws_bytes)
+                _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, _ptr(ws), ws_bytes)
     else:
         _launch("bess_neg_score_shared_fwd_masked", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
-                _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, ctypes.byref(kd), wp, ws_bytes)
+                _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, ctypes.byref(kd), _ptr(ws), ws_bytes)
     _range_flag(ws, range_flags)
     return out if ld == n_neg else out[:, :n_neg]
 
@@ -1016,12 +1055,10 @@ def neg_score_shared_fwd_pruned(d: ModelDesc, query: torch.Tensor, neg: RowSourc
     out = torch.empty((nq, ld), dtype=torch.float32, device=dev)
     ldf = ((n_neg + 63) // 64 + 3) // 4 * 4
     flags = torch.empty((nq, ldf), dtype=torch.uint8, device=dev)
-    lib = load()
-    ws_bytes = int(lib.bess_neg_score_shared_workspace(ctypes.byref(d), nq, n_neg))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    ws, ws_bytes = _workspace("bess_neg_score_shared_workspace", d, nq, n_neg, dev)
     _launch("bess_neg_score_shared_fwd_pruned", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
             _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, thr.data_ptr(), flags.data_ptr(), ldf,
-            ws.data_ptr() if ws is not None else None, ws_bytes)
+            _ptr(ws), ws_bytes)
     _range_flag(ws, range_flags)
     return (out if ld == n_neg else out[:, :n_neg]), flags
 
@@ -1038,12 +1075,9 @@ def neg_score_shared_pairs(d: ModelDesc, query: torch.Tensor, neg: RowSource, li
     out = torch.empty((n,), dtype=torch.float32, device=dev)
     if n == 0:
         return out
-    lib = load()
-    ws_bytes = int(lib.bess_neg_score_table_fwd_pairs_workspace(ctypes.byref(d), int(like_n_query), int(like_n_neg)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    ws, ws_bytes = _workspace("bess_neg_score_table_fwd_pairs_workspace", d, int(like_n_query), int(like_n_neg), dev)
     _launch("bess_neg_score_table_fwd_pairs", dev, ctypes.byref(d), query.data_ptr(), neg.base.data_ptr(),
-            _idx(neg.idx, "negative idx"), n, int(like_n_query), int(like_n_neg), out.data_ptr(),
-            ws.data_ptr() if ws is not None else None, ws_bytes)
+            _idx(neg.idx, "negative idx"), n, int(like_n_query), int(like_n_neg), out.data_ptr(), _ptr(ws), ws_bytes)
     return out
 
 
@@ -1069,12 +1103,10 @@ def neg_score_shared_counts(d: ModelDesc, query: torch.Tensor, neg: RowSource, t
         counts = torch.zeros((nq, 2), dtype=torch.int32, device=dev)
     elif tuple(counts.shape) != (nq, 2) or counts.dtype != torch.int32 or not counts.is_contiguous():
         raise ValueError("neg_score_shared_counts: counts must be a contiguous [nq, 2] int32 tensor")
-    lib = load()
-    ws_bytes = int(lib.bess_neg_score_table_fwd_counts_workspace(ctypes.byref(d), nq, n_neg))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    ws, ws_bytes = _workspace("bess_neg_score_table_fwd_counts_workspace", d, nq, n_neg, dev)
     _launch("bess_neg_score_table_fwd_counts", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
             _idx(neg.idx, "negative idx"), n_neg, thr.data_ptr(), excl.data_ptr(), counts.data_ptr(),
-            int(bool(round_f16)), ws.data_ptr() if ws is not None else None, ws_bytes)
+            int(bool(round_f16)), _ptr(ws), ws_bytes)
     return counts
 
 
@@ -1129,9 +1161,8 @@ def query_triple_bwd_parts(d: ModelDesc, side: int, head: RowSource, tail: RowSo
     acc_h, acc_t, acc_n = rows_acc
     _same_device([("d_out", d_out), ("dq_parts", dq_parts), ("dneg_parts", dneg_parts), ("neg_idx", neg_idx),
                   ("d_rel_table", d_rel_table), ("acc_h", acc_h), ("acc_t", acc_t), ("acc_n", acc_n)])
-    for t, nm in ((d_out, "d_out"), (dq_parts, "dq_parts"), (dneg_parts, "dneg_parts"), (d_rel_table, "d_rel_table"),
-                  (acc_h, "acc_h"), (acc_t, "acc_t"), (acc_n, "acc_n")):
-        _f32(t, nm)
+    _f32s(("d_out", d_out), ("dq_parts", dq_parts), ("dneg_parts", dneg_parts), ("d_rel_table", d_rel_table),
+          ("acc_h", acc_h), ("acc_t", acc_t), ("acc_n", acc_n))
     W = int(d.width)
     n_neg = int(neg_idx.numel())
     if dq_parts.dim() != 3 or tuple(dq_parts.shape[1:]) != (n, W) or dneg_parts.dim() != 3 \
@@ -1176,12 +1207,10 @@ def neg_score_shared_bwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, out:
     else:
         dq = torch.empty((nq, qw), dtype=torch.float32, device=dev)
         dn = torch.empty((n_neg, d.width), dtype=torch.float32, device=dev)
-    lib = load()
-    ws_bytes = int(lib.bess_neg_score_shared_bwd_workspace(ctypes.byref(d), nq, n_neg))  # see neg_score_shared_fwd
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    ws, ws_bytes = _workspace("bess_neg_score_shared_bwd_workspace", d, nq, n_neg, dev)
     _launch("bess_neg_score_shared_bwd_ws", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
             _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), n_neg, d_out.data_ptr(), n_neg, dq.data_ptr(),
-            dn.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes)
+            dn.data_ptr(), _ptr(ws), ws_bytes)
     if hat is not None and (d.reserved[1] & 1):
         dn = normalize_rows_bwd(hat, inv, dn)
     return dq, dn
@@ -1194,15 +1223,14 @@ def mask_scores(neg: torch.Tensor, diag_step: int, ht: bool, ppp: int, mask: Opt
     if neg.dim() != 2:
         raise ValueError("negative_score must be 2-D")
     S, N = int(neg.shape[0]), int(neg.shape[1])
-    mp, mrows, mcols = 0, 0, 0
-    if mask is not None:
-        if mask.dtype != torch.bool or mask.dim() != 2 or not mask.is_contiguous():
-            raise ValueError("negative_mask must be a contiguous 2-D bool tensor")
-        mp, mrows, mcols = mask.data_ptr(), int(mask.shape[0]), int(mask.shape[1])
+    mp, mrows, mcols = _mat(mask, torch.bool, _KILL_MASK)
     _launch("bess_mask_scores", dev, neg.data_ptr(), S, N, N, diag_step, int(ht), ppp, mp, mrows, mcols)
 
 
-_loss_counters: dict = {}  # (device, raw stream) -> int32 [TICKET_INTS], zero between calls
+# (device, raw stream) -> int32 [TICKET_INTS], zero between calls.  Kept apart from `_counters` on purpose: under stream
+# capture this cache allocates where `_counters` raises, and it holds 544 ints, not >= 1024 - merging the two would
+# change what a recorded graph contains.
+_loss_counters: dict = {}
 
 
 def loss_fwd_bwd(l: LossDesc, pos: torch.Tensor, neg: torch.Tensor, weight: torch.Tensor, want_grad: bool,
@@ -1216,8 +1244,7 @@ def loss_fwd_bwd(l: LossDesc, pos: torch.Tensor, neg: torch.Tensor, weight: torc
     take `lead_logq`.  Two rows are the heads' / tails' halves of every block of `ppp` triples (flat "ht")."""
     dev = _same_device([("positive_score", pos), ("negative_score", neg), ("triple_weight", weight),
                         ("negative_logq", logq)])
-    for t, nm in ((pos, "positive_score"), (neg, "negative_score"), (weight, "triple_weight")):
-        _f32(t, nm)
+    _f32s(("positive_score", pos), ("negative_score", neg), ("triple_weight", weight))
     S, N = int(neg.shape[0]), int(neg.shape[1])
     if pos.numel() != S or weight.numel() not in (1, S):
         raise ValueError("loss: shapes of positive_score / triple_weight do not match negative_score")
@@ -1241,8 +1268,7 @@ def loss_fwd_bwd(l: LossDesc, pos: torch.Tensor, neg: torch.Tensor, weight: torc
             # stream is capturing would be cleared by a fill node at every replay: one more dispatch)
             _loss_counters[(dev, "capture")] = torch.zeros((TICKET_INTS,), dtype=torch.int32, device=dev)
     common = (ctypes.byref(l), pos.data_ptr(), neg.data_ptr(), S, N, N, weight.data_ptr(), weight.numel(),
-              row_loss.data_ptr(), loss.data_ptr(), dp.data_ptr() if want_grad else 0,
-              dn.data_ptr() if want_grad else 0, N, norm.data_ptr() if want_norm else 0, counter.data_ptr())
+              row_loss.data_ptr(), loss.data_ptr(), _ptr(dp), _ptr(dn), N, _ptr(norm), counter.data_ptr())
     if logq is not None:
         _launch("bess_loss_fwd_bwd_logq", dev, *common, logq.data_ptr(), int(logq.shape[0]), int(logq.shape[1]),
                 int(ppp), float(lead_logq))
@@ -1294,35 +1320,18 @@ def neg_score_shared_fwd_loss(d: ModelDesc, l: LossDesc, query: torch.Tensor, ne
         raise ValueError("neg_score_shared_fwd_loss: shapes of positive_score / triple_weight do not match the queries")
     if d.scorer == AFFINE:
         neg, _, _ = _affine_candidates(d, neg)
-    # ONE allocation: scores, score gradients, row terms, d_pos, loss (every piece starts on a 16-byte boundary;
-    # dense rows: the backward kernels take contiguous [nq, n_neg] matrices)
+    # scores, score gradients, row terms, d_pos, loss (dense rows: the backward kernels take contiguous [nq, n_neg]
+    # matrices)
     ld = n_neg
-    mat = (nq * ld + 3) // 4 * 4
-    nq4 = (nq + 3) // 4 * 4
-    buf = torch.empty((2 * mat + 2 * nq4 + 4,), dtype=torch.float32, device=dev)
-    out = buf[: nq * ld].view(nq, ld)
-    dn = buf[mat: mat + nq * ld].view(nq, ld)
-    row_loss = buf[2 * mat: 2 * mat + nq]
-    dp = buf[2 * mat + nq4: 2 * mat + nq4 + nq]
-    loss = buf[2 * mat + 2 * nq4: 2 * mat + 2 * nq4 + 1]
-    lib = load()
-    ws_bytes = int(lib.bess_neg_score_shared_workspace(ctypes.byref(d), nq, n_neg))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
-    kd = None
-    if kill is not None:
-        diag_step, ht, ppp, mask = kill
-        kd = KillDesc()
-        kd.diag_step, kd.ht, kd.ppp = int(diag_step), int(bool(ht)), int(ppp)
-        if mask is not None:
-            _same_device([("negative_mask", mask), ("query", query)])
-            if mask.dtype != torch.bool or mask.dim() != 2 or not mask.is_contiguous():
-                raise ValueError("negative_mask must be a contiguous 2-D bool tensor")
-            kd.mask, kd.mask_rows, kd.mask_cols = mask.data_ptr(), int(mask.shape[0]), int(mask.shape[1])
+    out, dn, row_loss, dp, loss = _carve_f32(dev, nq * ld, nq * ld, nq, nq, 1)
+    out, dn = out.view(nq, ld), dn.view(nq, ld)
+    ws, ws_bytes = _workspace("bess_neg_score_shared_workspace", d, nq, n_neg, dev)
+    kd = _kill_desc(kill, query)
     counters = _counters(dev, (nq + 15) // 16 + 1)
     _launch("bess_neg_score_shared_fwd_loss", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
             _idx(neg.idx, "negative idx"), n_neg, out.data_ptr(), ld, ctypes.byref(kd) if kd is not None else None,
             ctypes.byref(l), pos.data_ptr(), weight.data_ptr(), weight.numel(), row_loss.data_ptr(), loss.data_ptr(),
-            dp.data_ptr(), dn.data_ptr(), ld, counters.data_ptr(), ws.data_ptr() if ws is not None else None, ws_bytes)
+            dp.data_ptr(), dn.data_ptr(), ld, counters.data_ptr(), _ptr(ws), ws_bytes)
     return out, loss.reshape(()), dp, dn
 
 
@@ -1349,6 +1358,21 @@ def sparse_sgd(table: torch.Tensor, idx: torch.Tensor, grad: torch.Tensor, lr: f
     _launch("bess_sparse_sgd", dev, _dtype_code(table), W, table.data_ptr(), ip, grad.data_ptr(), n, lr)
 
 
+def _axpy(axpy: Optional[Tuple[torch.Tensor, torch.Tensor, float]], table: torch.Tensor, who: str
+          ) -> Tuple[int, int, int, float]:
+    """(table2, grad2, elements, alpha) of the dense `table2 += alpha * grad2` that rides in an update launch, as C
+    arguments; (0, 0, 0, 0.0) for None and for an empty table."""
+    if axpy is None:
+        return 0, 0, 0, 0.0
+    x_table, x_grad, x_alpha = axpy
+    _same_device([("table", table), ("axpy table", x_table), ("axpy grad", x_grad)])
+    _f32(x_grad, "axpy grad")
+    if x_table.dtype != table.dtype or not x_table.is_contiguous() or x_grad.numel() != x_table.numel():
+        raise ValueError(f"{who}: the axpy table must be contiguous, of the table's dtype, and match its gradient")
+    x_n = int(x_table.numel())
+    return (x_table.data_ptr() if x_n else 0), (x_grad.data_ptr() if x_n else 0), x_n, float(x_alpha)
+
+
 def sparse_sgd_lists(table: torch.Tensor, lists: Sequence[Tuple[torch.Tensor, torch.Tensor]], lr: float,
                      axpy: Optional[Tuple[torch.Tensor, torch.Tensor, float]] = None) -> None:
     """`sparse_sgd` for several (row ids, gradient rows) lists in one launch.  `axpy` = (table2, grad2, alpha):
@@ -1366,17 +1390,8 @@ def sparse_sgd_lists(table: torch.Tensor, lists: Sequence[Tuple[torch.Tensor, to
     ip = (_vp * len(lists))(*[x.data_ptr() for x, _ in lists])
     gp = (_vp * len(lists))(*[g.data_ptr() for _, g in lists])
     rows = (_i64 * len(lists))(*[int(g.shape[0]) for _, g in lists])
-    x_table = x_grad = None
-    x_n, x_alpha = 0, 0.0
-    if axpy is not None:
-        x_table, x_grad, x_alpha = axpy
-        _same_device([("table", table), ("axpy table", x_table), ("axpy grad", x_grad)])
-        _f32(x_grad, "axpy grad")
-        if x_table.dtype != table.dtype or not x_table.is_contiguous() or x_grad.numel() != x_table.numel():
-            raise ValueError("sparse_sgd_lists: the axpy table must be contiguous, of the table's dtype, and match its gradient")
-        x_n = int(x_table.numel())
     _launch("bess_sparse_sgd_lists_axpy", dev, _dtype_code(table), W, table.data_ptr(), len(lists), ip, gp, rows, lr,
-            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha))
+            *_axpy(axpy, table, "sparse_sgd_lists"))
 
 
 def dense_sgd(table: torch.Tensor, grad: torch.Tensor, lr: float) -> None:
@@ -1462,14 +1477,7 @@ def step_prologue(jobs: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor], int
     tensors = [("job dst", j[0]) for j in jobs] + [("job src", j[1]) for j in jobs] + [("ids", x) for x in id_lists]
     dev = _same_device(tensors)
     nj = len(jobs)
-    dst, src = (_vp * max(1, nj))(), (_vp * max(1, nj))()
-    val, words = (ctypes.c_uint32 * max(1, nj))(), (_i64 * max(1, nj))()
-    for i, (d_, s_, v_) in enumerate(jobs):
-        if d_.element_size() != 4 or not d_.is_contiguous():
-            raise ValueError("step_prologue: job targets must be contiguous tensors of 4-byte elements")
-        if s_ is not None and (s_.element_size() != 4 or not s_.is_contiguous() or s_.numel() != d_.numel()):
-            raise ValueError("step_prologue: a job's source must match its target")
-        dst[i], src[i], val[i], words[i] = d_.data_ptr(), (s_.data_ptr() if s_ is not None else None), int(v_), d_.numel()
+    dst, src, val, words = _job_arrays(jobs, "step_prologue")
     nl = len(id_lists)
     lp, ll = (_vp * max(1, nl))(), (_i64 * max(1, nl))()
     n_ids = 0
@@ -1529,15 +1537,13 @@ def neg_pertriple_grad_segments(d: ModelDesc, query: torch.Tensor, table: torch.
         raise ValueError("neg_pertriple_grad_segments: operand shapes do not match")
     fused = fused_sgd_lr is not None
     grad = None if fused else torch.empty((seg.max_seg, d.width), dtype=torch.float32, device=dev)
-    native = True  # every scorer id has a segmented reduction with a long-row tier
-    if native and (seg.long_grad is None or seg.long_grad.shape[1] != d.width):
+    # (every scorer id has a segmented reduction with a long-row tier)
+    if seg.long_grad is None or seg.long_grad.shape[1] != d.width:
         seg.long_grad = torch.zeros((seg.long_cap, d.width), dtype=torch.float32, device=dev)
-    long_grad = seg.long_grad
     _launch("bess_neg_pertriple_grad_segments", dev, ctypes.byref(d), query.data_ptr(), nq, table.data_ptr(), n_neg,
             d_out.data_ptr(), n_neg, seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(),
-            seg.n_seg.data_ptr(), seg.max_seg, 0 if fused else grad.data_ptr(), float(fused_sgd_lr) if fused else 0.0,
-            seg.long_segs.data_ptr() if native else None, seg.long_cap if native else 0,
-            long_grad.data_ptr() if native else None, seg.long_count.data_ptr() if native else None)
+            seg.n_seg.data_ptr(), seg.max_seg, _ptr(grad), float(fused_sgd_lr) if fused else 0.0,
+            seg.long_segs.data_ptr(), seg.long_cap, seg.long_grad.data_ptr(), seg.long_count.data_ptr())
     return grad
 
 
@@ -1590,9 +1596,8 @@ def apply_segments_opt(o: OptDesc, table: torch.Tensor, seg: SegmentIndex, grad_
     _state_ok(state1, table, o, "state1")
     _state_ok(state2, table, o, "state2")
     _launch("bess_apply_segments_opt", dev, ctypes.byref(o), _dtype_code(table), W, table.data_ptr(),
-            seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg, grad_seg.data_ptr(),
-            state1.data_ptr() if state1 is not None else 0, state2.data_ptr() if state2 is not None else 0,
-            keep.data_ptr() if keep is not None else None)
+            seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg, grad_seg.data_ptr(), _ptr(state1), _ptr(state2),
+            _ptr(keep))
 
 
 MAX_ROW_LISTS = 8  # BESS_MAX_ROW_LISTS
@@ -1625,21 +1630,11 @@ def coalesced_update(o: Optional[OptDesc], table: torch.Tensor, seg: SegmentInde
     ptrs = (_vp * len(grads))(*[g.data_ptr() for g in grads])
     rows = (_i64 * len(grads))(*[int(g.shape[0]) for g in grads])
     out = torch.empty((seg.max_seg, W), dtype=torch.float32, device=dev) if sum_only else None
-    x_table = x_grad = None
-    x_n, x_alpha = 0, 0.0
-    if axpy is not None:
-        x_table, x_grad, x_alpha = axpy
-        _same_device([("table", table), ("axpy table", x_table), ("axpy grad", x_grad)])
-        _f32(x_grad, "axpy grad")
-        if x_table.dtype != table.dtype or not x_table.is_contiguous() or x_grad.numel() != x_table.numel():
-            raise ValueError("coalesced_update: the axpy table must be contiguous, of the table's dtype, and match its gradient")
-        x_n = int(x_table.numel())
+    x = _axpy(axpy, table, "coalesced_update")
     _launch("bess_coalesced_update_axpy", dev, ctypes.byref(o) if o is not None else None, _dtype_code(table), W,
             table.data_ptr(), len(grads), ptrs, rows, seg.refs.data_ptr(), seg.seg_rows.data_ptr(),
-            seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
-            state1.data_ptr() if state1 is not None else None, state2.data_ptr() if state2 is not None else None,
-            keep.data_ptr() if keep is not None else None, out.data_ptr() if out is not None else None,
-            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha))
+            seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg, _ptr(state1), _ptr(state2), _ptr(keep),
+            _ptr(out), *x)
     return out
 
 
@@ -1685,19 +1680,9 @@ def direct_update(o: OptDesc, table: torch.Tensor, id_lists: Sequence[torch.Tens
     _state_ok(state2, table, o, "state2")
     ptrs = (_vp * len(id_lists))(*[x.data_ptr() for x in id_lists])
     lens = (_i64 * len(id_lists))(*[int(x.numel()) for x in id_lists])
-    x_table = x_grad = None
-    x_n, x_alpha = 0, 0.0
-    if axpy is not None:
-        x_table, x_grad, x_alpha = axpy
-        _same_device([("table", table), ("axpy table", x_table), ("axpy grad", x_grad)])
-        _f32(x_grad, "axpy grad")
-        if x_table.dtype != table.dtype or not x_table.is_contiguous() or x_grad.numel() != x_table.numel():
-            raise ValueError("direct_update: the axpy table must be contiguous, of the table's dtype, and match its gradient")
-        x_n = int(x_table.numel())
     _launch("bess_direct_update", dev, ctypes.byref(o), _dtype_code(table), W, table.data_ptr(), len(id_lists), ptrs,
-            lens, scratch.acc.data_ptr(), scratch.claim.data_ptr(), scratch.generation.data_ptr(),
-            state1.data_ptr() if state1 is not None else None, state2.data_ptr() if state2 is not None else None,
-            x_table.data_ptr() if x_n else None, x_grad.data_ptr() if x_n else None, x_n, float(x_alpha))
+            lens, scratch.acc.data_ptr(), scratch.claim.data_ptr(), scratch.generation.data_ptr(), _ptr(state1),
+            _ptr(state2), *_axpy(axpy, table, "direct_update"))
 
 
 def assign_state_rows(seg: Any, slot_map: torch.Tensor, counter: torch.Tensor, capacity: int,
@@ -1706,8 +1691,8 @@ def assign_state_rows(seg: Any, slot_map: torch.Tensor, counter: torch.Tensor, c
     dev = _same_device([("seg_rows", seg.seg_rows), ("slot_map", slot_map), ("counter", counter), ("keep", keep)])
     if slot_map.dtype != torch.int32 or counter.dtype != torch.int32 or not slot_map.is_contiguous():
         raise ValueError("assign_state_rows: slot_map / counter must be int32")
-    _launch("bess_assign_state_rows", dev, seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg,
-            keep.data_ptr() if keep is not None else None, slot_map.data_ptr(), counter.data_ptr(), int(capacity))
+    _launch("bess_assign_state_rows", dev, seg.seg_rows.data_ptr(), seg.n_seg.data_ptr(), seg.max_seg, _ptr(keep),
+            slot_map.data_ptr(), counter.data_ptr(), int(capacity))
 
 
 def _state_ok(st: Optional[torch.Tensor], table: torch.Tensor, o: Optional[OptDesc], name: str) -> None:
@@ -1758,9 +1743,7 @@ def neg_pertriple_step_segments(d: ModelDesc, query: torch.Tensor, table: torch.
     _launch("bess_neg_pertriple_step_segments", dev, ctypes.byref(d), query.data_ptr(), nq, table.data_ptr(), n_neg,
             d_out.data_ptr(), n_neg, seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(),
             seg.n_seg.data_ptr(), seg.max_seg, seg.long_segs.data_ptr(), seg.long_cap, seg.long_grad.data_ptr(),
-            seg.long_count.data_ptr(), ctypes.byref(o), state1.data_ptr() if state1 is not None else None,
-            state2.data_ptr() if state2 is not None else None, extra_map.data_ptr() if extra_map is not None else None,
-            extra_sum.data_ptr() if extra_sum is not None else None)
+            seg.long_count.data_ptr(), ctypes.byref(o), _ptr(state1), _ptr(state2), _ptr(extra_map), _ptr(extra_sum))
 
 
 def ranks_from_scores(pos: torch.Tensor, cand: torch.Tensor, mode: int, worst_rank_infty: bool) -> torch.Tensor:
@@ -1787,44 +1770,65 @@ def ranks_from_indices(truth: torch.Tensor, cand: torch.Tensor, worst_rank_infty
     return out
 
 
+_TOPK_FLAGS = "flags must be a contiguous uint8 [rows, 4 * ceil(L / 256)] tensor"
+
+
+def _topk(who: str, ordered: bool, scores: torch.Tensor, best_score: torch.Tensor, best_id: torch.Tensor,
+          ids: Optional[torch.Tensor], id_base: int, mask: Optional[torch.Tensor], flags: Optional[torch.Tensor],
+          excl_ptr: Optional[torch.Tensor] = None, excl_ids: Optional[torch.Tensor] = None,
+          round_f16: bool = False) -> None:
+    """The checks and the launch of `topk_update` (`ordered` False) and `topk_update_excl` (True); `who`: the name
+    in the messages."""
+    dev = _same_device([("scores", scores), ("best_score", best_score), ("best_id", best_id), ("ids", ids),
+                        ("mask", mask), ("flags", flags), ("excl_ptr", excl_ptr), ("excl_ids", excl_ids)])
+    if scores.dtype != torch.float32 or scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError(f"{who}: scores must be float32 [rows, L] with contiguous rows")
+    _f32(best_score, "best_score")
+    if best_score.dim() != 2 or best_score.shape[0] != scores.shape[0] \
+            or best_id.shape != best_score.shape or best_id.dtype != torch.int32 or not best_id.is_contiguous():
+        raise ValueError(f"{who}: best lists must be [rows, kk] (f32 scores, int32 ids)")
+    R, L, kk = int(scores.shape[0]), int(scores.shape[1]), int(best_score.shape[1])
+    if (excl_ptr is None) != (excl_ids is None):
+        raise ValueError(f"{who}: excl_ptr and excl_ids go together")
+    ep = ei = n_excl = 0
+    if excl_ptr is not None:
+        for t in (excl_ptr, excl_ids):
+            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f"{who}: excl_ptr / excl_ids must be contiguous 1-D int32 tensors")
+        if excl_ptr.numel() != R + 1:
+            raise ValueError(f"{who}: excl_ptr has {excl_ptr.numel()} entries, expected rows + 1 = {R + 1}")
+        ep, ei, n_excl = excl_ptr.data_ptr(), excl_ids.data_ptr(), int(excl_ids.numel())
+    ip, ir, _ = _mat(ids, torch.int32, "ids must be a contiguous int32 [1 | rows, L] tensor", (1, R), L, who)
+    mp, mr, _ = _mat(mask, torch.bool, "mask must be a contiguous bool [1 | rows, L] tensor", (1, R), L, who)
+    ld = int(scores.stride(0)) if R > 1 else L
+    if flags is None:
+        if ordered:
+            _launch("bess_topk_update_excl", dev, scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr, ep,
+                    ei, n_excl, int(bool(round_f16)), best_score.data_ptr(), best_id.data_ptr(), kk)
+        else:
+            _launch("bess_topk_update", dev, scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr,
+                    best_score.data_ptr(), best_id.data_ptr(), kk)
+        return
+    if mask is not None or (ids is not None and (ir != 1 or not ordered)):
+        raise ValueError(f"{who}: flagged tiles take one shared row of ids (or id_base) and no mask" if ordered
+                         else f"{who}: flagged tiles take ids from id_base and no mask")
+    fp, _, fc = _mat(flags, torch.uint8, _TOPK_FLAGS, (R,), None, who)
+    if fc % 4 or fc * 64 < L:
+        raise ValueError(f"{who}: {_TOPK_FLAGS}")
+    if ordered:
+        _launch("bess_topk_update_flagged_excl", dev, scores.data_ptr(), R, L, max(ld, L), fp, fc, ip, int(id_base), ep,
+                ei, n_excl, int(bool(round_f16)), best_score.data_ptr(), best_id.data_ptr(), kk)
+    else:
+        _launch("bess_topk_update_flagged", dev, scores.data_ptr(), R, L, max(ld, L), fp, fc, int(id_base),
+                best_score.data_ptr(), best_id.data_ptr(), kk)
+
+
 def topk_update(scores: torch.Tensor, best_score: torch.Tensor, best_id: torch.Tensor,
                 ids: Optional[torch.Tensor] = None, id_base: int = 0, mask: Optional[torch.Tensor] = None,
                 flags: Optional[torch.Tensor] = None) -> None:
     """Merge `scores` [rows, L] into the running (best_score, best_id) [rows, kk] lists in place.
     `flags` (from `neg_score_shared_fwd_pruned`): only the flagged blocks of 64 columns are read."""
-    dev = _same_device([("scores", scores), ("best_score", best_score), ("best_id", best_id), ("ids", ids),
-                        ("mask", mask), ("flags", flags)])
-    if scores.dtype != torch.float32 or scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1):
-        raise ValueError("topk_update: scores must be float32 [rows, L] with contiguous rows")
-    _f32(best_score, "best_score")
-    if best_score.dim() != 2 or best_score.shape[0] != scores.shape[0] \
-            or best_id.shape != best_score.shape or best_id.dtype != torch.int32 or not best_id.is_contiguous():
-        raise ValueError("topk_update: best lists must be [rows, kk] (f32 scores, int32 ids)")
-    R, L, kk = int(scores.shape[0]), int(scores.shape[1]), int(best_score.shape[1])
-    ip = ir = 0
-    if ids is not None:
-        if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[1] != L or ids.shape[0] not in (1, R) \
-                or not ids.is_contiguous():
-            raise ValueError("topk_update: ids must be a contiguous int32 [1 | rows, L] tensor")
-        ip, ir = ids.data_ptr(), int(ids.shape[0])
-    mp = mr = 0
-    if mask is not None:
-        if mask.dtype != torch.bool or mask.dim() != 2 or mask.shape[1] != L or mask.shape[0] not in (1, R) \
-                or not mask.is_contiguous():
-            raise ValueError("topk_update: mask must be a contiguous bool [1 | rows, L] tensor")
-        mp, mr = mask.data_ptr(), int(mask.shape[0])
-    ld = int(scores.stride(0)) if R > 1 else L
-    if flags is not None:
-        if ids is not None or mask is not None:
-            raise ValueError("topk_update: flagged tiles take ids from id_base and no mask")
-        if flags.dtype != torch.uint8 or flags.dim() != 2 or flags.shape[0] != R or not flags.is_contiguous() \
-                or flags.shape[1] % 4 or flags.shape[1] * 64 < L:
-            raise ValueError("topk_update: flags must be a contiguous uint8 [rows, 4 * ceil(L / 256)] tensor")
-        _launch("bess_topk_update_flagged", dev, scores.data_ptr(), R, L, max(ld, L), flags.data_ptr(),
-                int(flags.shape[1]), int(id_base), best_score.data_ptr(), best_id.data_ptr(), kk)
-        return
-    _launch("bess_topk_update", dev, scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr,
-            best_score.data_ptr(), best_id.data_ptr(), kk)
+    _topk("topk_update", False, scores, best_score, best_id, ids, id_base, mask, flags)
 
 
 #: id of an empty entry of the ordered lists (`topk_update_excl`): nothing sorts after (-inf, TOPK_ID_NONE)
@@ -1843,50 +1847,7 @@ def topk_update_excl(scores: torch.Tensor, best_score: torch.Tensor, best_id: to
     `round_f16`: scores are rounded to fp16 before they are compared and stored.  With `flags`, `ids` is one row
     [1, L] shared by all rows (or None: `id_base` + column) and there is no mask; the thresholds the tile was
     pruned with must be strictly below the rows' kk-th scores."""
-    dev = _same_device([("scores", scores), ("best_score", best_score), ("best_id", best_id), ("ids", ids),
-                        ("mask", mask), ("flags", flags), ("excl_ptr", excl_ptr), ("excl_ids", excl_ids)])
-    if scores.dtype != torch.float32 or scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1):
-        raise ValueError("topk_update_excl: scores must be float32 [rows, L] with contiguous rows")
-    _f32(best_score, "best_score")
-    if best_score.dim() != 2 or best_score.shape[0] != scores.shape[0] \
-            or best_id.shape != best_score.shape or best_id.dtype != torch.int32 or not best_id.is_contiguous():
-        raise ValueError("topk_update_excl: best lists must be [rows, kk] (f32 scores, int32 ids)")
-    R, L, kk = int(scores.shape[0]), int(scores.shape[1]), int(best_score.shape[1])
-    if (excl_ptr is None) != (excl_ids is None):
-        raise ValueError("topk_update_excl: excl_ptr and excl_ids go together")
-    ep = ei = n_excl = 0
-    if excl_ptr is not None:
-        for t in (excl_ptr, excl_ids):
-            if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
-                raise ValueError("topk_update_excl: excl_ptr / excl_ids must be contiguous 1-D int32 tensors")
-        if excl_ptr.numel() != R + 1:
-            raise ValueError(f"topk_update_excl: excl_ptr has {excl_ptr.numel()} entries, expected rows + 1 = {R + 1}")
-        ep, ei, n_excl = excl_ptr.data_ptr(), excl_ids.data_ptr(), int(excl_ids.numel())
-    ip = ir = 0
-    if ids is not None:
-        if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[1] != L or ids.shape[0] not in (1, R) \
-                or not ids.is_contiguous():
-            raise ValueError("topk_update_excl: ids must be a contiguous int32 [1 | rows, L] tensor")
-        ip, ir = ids.data_ptr(), int(ids.shape[0])
-    mp = mr = 0
-    if mask is not None:
-        if mask.dtype != torch.bool or mask.dim() != 2 or mask.shape[1] != L or mask.shape[0] not in (1, R) \
-                or not mask.is_contiguous():
-            raise ValueError("topk_update_excl: mask must be a contiguous bool [1 | rows, L] tensor")
-        mp, mr = mask.data_ptr(), int(mask.shape[0])
-    ld = int(scores.stride(0)) if R > 1 else L
-    if flags is not None:
-        if mask is not None or (ids is not None and ids.shape[0] != 1):
-            raise ValueError("topk_update_excl: flagged tiles take one shared row of ids (or id_base) and no mask")
-        if flags.dtype != torch.uint8 or flags.dim() != 2 or flags.shape[0] != R or not flags.is_contiguous() \
-                or flags.shape[1] % 4 or flags.shape[1] * 64 < L:
-            raise ValueError("topk_update_excl: flags must be a contiguous uint8 [rows, 4 * ceil(L / 256)] tensor")
-        _launch("bess_topk_update_flagged_excl", dev, scores.data_ptr(), R, L, max(ld, L), flags.data_ptr(),
-                int(flags.shape[1]), ip, int(id_base), ep, ei, n_excl, int(bool(round_f16)), best_score.data_ptr(),
-                best_id.data_ptr(), kk)
-        return
-    _launch("bess_topk_update_excl", dev, scores.data_ptr(), R, L, max(ld, L), ip, ir, int(id_base), mp, mr, ep, ei,
-            n_excl, int(bool(round_f16)), best_score.data_ptr(), best_id.data_ptr(), kk)
+    _topk("topk_update_excl", True, scores, best_score, best_id, ids, id_base, mask, flags, excl_ptr, excl_ids, round_f16)
 
 
 # --------------------------------------------------------------------------- #
@@ -2034,10 +1995,9 @@ def gather_candidate_lists(table_h: torch.Tensor, mask_h: Optional[torch.Tensor]
     if want_mask and mask_h is not None:
         shape = (n_step, n_neg_shard, n_shard, T, L) if mask_gather_layout else (n_step, n_shard, T, n_neg_shard, L)
         msk = torch.empty(shape, dtype=torch.bool, device=dev)
-    _launch("bess_gather_candidate_lists", dev, table_h.data_ptr(), table_t.data_ptr() if table_t is not None else None,
-            mask_h.data_ptr() if mask_h is not None else None, mask_t.data_ptr() if mask_t is not None else None,
-            n_list, lookup.data_ptr(), n_step, n_shard, T, int(per_part), int(half), n_neg_shard, L,
-            int(bool(mask_gather_layout)), ent.data_ptr(), msk.data_ptr() if msk is not None else None)
+    _launch("bess_gather_candidate_lists", dev, table_h.data_ptr(), _ptr(table_t), _ptr(mask_h), _ptr(mask_t), n_list,
+            lookup.data_ptr(), n_step, n_shard, T, int(per_part), int(half), n_neg_shard, L,
+            int(bool(mask_gather_layout)), ent.data_ptr(), _ptr(msk))
     return ent, msk
 
 
@@ -2051,6 +2011,30 @@ def _index_ptrs(ix: Optional[Sequence[torch.Tensor]], name: str) -> Tuple[int, i
     _int_tensor(off, f"{name} offsets", torch.int64, n_pair + 1)
     _int_tensor(comp, f"{name} completions", torch.int32)
     return keys.data_ptr(), off.data_ptr(), n_pair, comp.data_ptr()
+
+
+def _known_rows(index: Sequence[torch.Tensor], index2: Optional[Sequence[torch.Tensor]], kept: torch.Tensor,
+                relation: torch.Tensor, side: Optional[torch.Tensor], kept_shard: Optional[torch.Tensor],
+                local_to_global: Optional[torch.Tensor]) -> Tuple[Any, ...]:
+    """The leading C arguments that `bess_known_triple_mask` and `bess_known_completions` share, in their order - the
+    two indices, kept, kept_shard, relation, side, n_row, the row count itself - and then (map, ld_map, n_map_shard)
+    of `local_to_global`, which the two take further back."""
+    n_row = int(kept.numel())
+    kp = _int_tensor(kept, "kept", torch.int32)
+    rp = _int_tensor(relation, "relation", torch.int32, n_row)
+    ksp = _int_tensor(kept_shard, "kept_shard", torch.int32, n_row)
+    sp = 0
+    if side is not None:
+        if side.dtype not in (torch.uint8, torch.bool) or not side.is_contiguous() or side.numel() != n_row:
+            raise ValueError(f"`side` must be contiguous uint8 / bool with {n_row} entries")
+        if index2 is None:
+            raise ValueError("a `side` vector needs the index of both sides (`index2`)")
+        sp = side.data_ptr()
+    mp, n_map_shard, ld_map = _mat(local_to_global, torch.int32,
+                                   "`local_to_global` must be a contiguous int32 [n_shard, rows per shard] tensor")
+    if local_to_global is None and kept_shard is not None:
+        raise ValueError("`kept_shard` needs `local_to_global`")
+    return (*_index_ptrs(index, "index"), *_index_ptrs(index2, "index2"), kp, ksp, rp, sp, n_row), (mp, ld_map, n_map_shard)
 
 
 def known_triple_mask(index: Sequence[torch.Tensor], kept: torch.Tensor, relation: torch.Tensor, cand: torch.Tensor,
@@ -2069,20 +2053,9 @@ def known_triple_mask(index: Sequence[torch.Tensor], kept: torch.Tensor, relatio
                         ("kept_shard", kept_shard), ("cand_row", cand_row), ("local_to_global", local_to_global),
                         *[(f"index[{k}]", t) for k, t in enumerate(index)],
                         *[(f"index2[{k}]", t) for k, t in enumerate(index2 or ())]])
-    n_row = int(kept.numel())
-    kp = _int_tensor(kept, "kept", torch.int32)
-    rp = _int_tensor(relation, "relation", torch.int32, n_row)
-    ksp = _int_tensor(kept_shard, "kept_shard", torch.int32, n_row)
+    rows, l2g = _known_rows(index, index2, kept, relation, side, kept_shard, local_to_global)
+    n_row = rows[-1]
     crp = _int_tensor(cand_row, "cand_row", torch.int32, n_row)
-    sp = 0
-    if side is not None:
-        if side.dtype not in (torch.uint8, torch.bool) or not side.is_contiguous() or side.numel() != n_row:
-            raise ValueError(f"`side` must be contiguous uint8 / bool with {n_row} entries")
-        if index2 is None:
-            raise ValueError("a `side` vector needs the index of both sides (`index2`)")
-        sp = side.data_ptr()
-
-    i1, i2 = _index_ptrs(index, "index"), _index_ptrs(index2, "index2")
     _int_tensor(cand, "cand", torch.int32)
     if cand.dim() == 2 and n_col is None:
         n_cand_row, n_col = (int(x) for x in cand.shape)
@@ -2110,19 +2083,10 @@ def known_triple_mask(index: Sequence[torch.Tensor], kept: torch.Tensor, relatio
     ld_mask = int(ld_mask)
     if ld_mask < n_col or (n_row > 0 and n_col > 0 and (n_row - 1) * ld_mask + n_col > mask.numel()):
         raise ValueError(f"`mask` ({mask.numel()} bytes, ld {ld_mask}) does not hold {n_row} x {n_col}")
-    mp, ld_map, n_map_shard = 0, 0, 0
-    if local_to_global is not None:
-        if local_to_global.dtype != torch.int32 or local_to_global.dim() != 2 or not local_to_global.is_contiguous():
-            raise ValueError("`local_to_global` must be a contiguous int32 [n_shard, rows per shard] tensor")
-        n_map_shard, ld_map = (int(x) for x in local_to_global.shape)
-        if (cand_shard >= n_map_shard) or (cand_shard < 0 and n_block > n_map_shard):
-            raise ValueError("`local_to_global` does not cover the candidates' shards")
-        mp = local_to_global.data_ptr()
-    elif kept_shard is not None:
-        raise ValueError("`kept_shard` needs `local_to_global`")
-    _launch("bess_known_triple_mask", dev, *i1, *i2, kp, ksp, rp, sp, n_row, int(n_relation), cand.data_ptr(), n_col,
-            ld_cand, n_cand_row, crp, cpb, stride, int(cand_shard), mp, ld_map, n_map_shard, mask.data_ptr(), ld_mask,
-            int(bool(and_into)))
+    if local_to_global is not None and (cand_shard >= l2g[2] or (cand_shard < 0 and n_block > l2g[2])):
+        raise ValueError("`local_to_global` does not cover the candidates' shards")
+    _launch("bess_known_triple_mask", dev, *rows, int(n_relation), cand.data_ptr(), n_col, ld_cand, n_cand_row, crp, cpb,
+            stride, int(cand_shard), *l2g, mask.data_ptr(), ld_mask, int(bool(and_into)))
     return mask
 
 
@@ -2144,28 +2108,9 @@ def known_completions(index: Sequence[torch.Tensor], kept: torch.Tensor, relatio
                         ("counts", counts), ("dst", dst), ("out", out), ("tag", tag),
                         *[(f"index[{k}]", t) for k, t in enumerate(index)],
                         *[(f"index2[{k}]", t) for k, t in enumerate(index2 or ())]])
-    n_row = int(kept.numel())
-    kp = _int_tensor(kept, "kept", torch.int32)
-    rp = _int_tensor(relation, "relation", torch.int32, n_row)
-    ksp = _int_tensor(kept_shard, "kept_shard", torch.int32, n_row)
+    rows, l2g = _known_rows(index, index2, kept, relation, side, kept_shard, local_to_global)
+    n_row = rows[-1]
     skp = _int_tensor(skip, "skip", torch.int32, n_row)
-    sp = 0
-    if side is not None:
-        if side.dtype not in (torch.uint8, torch.bool) or not side.is_contiguous() or side.numel() != n_row:
-            raise ValueError(f"`side` must be contiguous uint8 / bool with {n_row} entries")
-        if index2 is None:
-            raise ValueError("a `side` vector needs the index of both sides (`index2`)")
-        sp = side.data_ptr()
-
-    i1, i2 = _index_ptrs(index, "index"), _index_ptrs(index2, "index2")
-    mp, ld_map, n_map_shard = 0, 0, 0
-    if local_to_global is not None:
-        if local_to_global.dtype != torch.int32 or local_to_global.dim() != 2 or not local_to_global.is_contiguous():
-            raise ValueError("`local_to_global` must be a contiguous int32 [n_shard, rows per shard] tensor")
-        n_map_shard, ld_map = (int(x) for x in local_to_global.shape)
-        mp = local_to_global.data_ptr()
-    elif kept_shard is not None:
-        raise ValueError("`kept_shard` needs `local_to_global`")
     kep, n_entity = 0, 0
     if keep_entity is not None:
         if keep_entity.dtype not in (torch.uint8, torch.bool) or not keep_entity.is_contiguous():
@@ -2186,8 +2131,8 @@ def known_completions(index: Sequence[torch.Tensor], kept: torch.Tensor, relatio
             raise ValueError(f"`out` has {out.numel()} elements: not a multiple of out_stride {out_stride}")
         n_out = out.numel() // out_stride
     tp = _int_tensor(tag, "tag", torch.int32, n_row)
-    _launch("bess_known_completions", dev, *i1, *i2, kp, ksp, rp, sp, n_row, int(n_relation), mp, ld_map, n_map_shard,
-            skp, kep, n_entity, cp, dp, op, n_out, int(out_stride), tp)
+    _launch("bess_known_completions", dev, *rows, int(n_relation), *l2g, skp, kep, n_entity, cp, dp, op, n_out,
+            int(out_stride), tp)
     return counts if counts is not None else out  # type: ignore[return-value]
 
 

@@ -12,10 +12,64 @@ import pytest
 from conftest import REPO
 
 
-def header_functions():
+def header_text():
     text = open(os.path.join(REPO, "include", "besskge_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(?:int|int64_t)\s+(bess_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"//[^\n]*", "", text)
+
+
+def header_functions():
+    return sorted(set(re.findall(r"\b(?:int|int64_t)\s+(bess_[a-z0-9_]+)\s*\(", header_text())))
+
+
+C_KINDS = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint32_t": "u32", "size_t": "size", "float": "f32"}
+CTYPES_KINDS = {ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint32: "u32", ctypes.c_size_t: "size",
+                ctypes.c_float: "f32"}
+
+
+def header_prototypes():
+    """{name: (return type, [kind of every parameter])} of every `(int|int64_t) bess_name(args);` of the header.  A
+    parameter with a `*` is a `ptr`; any other is looked up in `C_KINDS` by its type (KeyError: a type this test
+    does not know - extend the map, do not skip the prototype)."""
+    out = {}
+    for ret, name, args in re.findall(r"\b(int|int64_t)\s+(bess_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header_text()):
+        assert name not in out, f"{name} is declared twice"
+        kinds = []
+        for param in (p.strip() for p in args.split(",")):
+            if param in ("", "void"):
+                continue
+            if "*" in param:
+                kinds.append("ptr")
+                continue
+            words = [w for w in param.split() if w != "const"]
+            kinds.append(C_KINDS[" ".join(words[:-1]) if len(words) > 1 else words[0]])
+        out[name] = (ret, kinds)
+    return out
+
+
+def ctypes_kind(tp):
+    if tp in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(tp, ctypes._Pointer):
+        return "ptr"
+    return CTYPES_KINDS[tp]
+
+
+def test_signatures_match_the_header_by_kind():
+    """Every prototype of the header against `SIGNATURES` position by position (pointer / int32 / int64 / uint32 /
+    size_t / float), and its return type against `_RETURNS_I64`: a 32-bit argtype where the header says `int64_t`
+    - or a workspace query whose 64-bit result ctypes would truncate - is a silent wrong value, not a crash."""
+    from besskge import _native
+
+    protos = header_prototypes()
+    assert sorted(protos) == header_functions() == sorted(_native.SIGNATURES)  # no prototype is left out
+    bad = []
+    for name, (ret, kinds) in protos.items():
+        have = [ctypes_kind(tp) for tp in _native.SIGNATURES[name]]
+        if have != kinds:
+            bad.append(f"{name}: header {kinds}, ctypes {have}")
+        if (ret == "int64_t") != (name in _native._RETURNS_I64):
+            bad.append(f"{name}: returns {ret}, _RETURNS_I64 says {name in _native._RETURNS_I64}")
+    assert not bad, "\n".join(bad)
+    assert set(_native._RETURNS_I64) <= set(protos)
 
 
 def test_library_exports_every_declared_symbol():
