@@ -25,6 +25,10 @@ gradient of every *gathered row*; rows that came through the all-to-all travel
 back through one more all-to-all (C8) and are applied to the owning shard with
 a sparse atomic SGD update (K9+K10).  The shard gradient is never dense and
 never all-reduced; only the replicated relation table is (C9).
+
+The backward hands the update one `_ShardGrads` per hosted replica (row lists,
+per-triple groups with their index); `BessKGE._update_route` says once which
+way they go: `_update_dense`, `_update_atomic` or `_update_coalesced`.
 """
 
 from abc import ABC, abstractmethod
@@ -55,6 +59,15 @@ _Batch = Dict[str, torch.Tensor]
 def _i32(x: torch.Tensor) -> torch.Tensor:
     x = x if x.dtype == torch.int32 else x.to(torch.int32)
     return x.contiguous()
+
+
+def _split_ht(d: torch.Tensor, ppp: int) -> List[torch.Tensor]:
+    """Score gradients [..., blocks * ppp, C] of an "ht" step as its two groups take them: the first ppp // 2 triples
+    of every block corrupt heads, the others tails - each half flattened to [rows, C], contiguous.  (The block axis
+    is split off where it is: ScoreMoving's gradients come as a window of a wider buffer, which does not flatten.)"""
+    blocks, cut = d.unflatten(-2, (-1, ppp)), ppp // 2
+    return [blocks[..., :cut, :].reshape(-1, d.shape[-1]).contiguous(),
+            blocks[..., cut:, :].reshape(-1, d.shape[-1]).contiguous()]
 
 
 class _PlainSGD:
@@ -91,6 +104,7 @@ class _NegGroup:
         self.kill: Any = None  # K7 applied together with the scores (shared negatives, one group)
         self.neg_parts: Optional[List[torch.Tensor]] = None  # neg.idx = their concatenation, written by the prologue
         self.bwd_buf: Optional[torch.Tensor] = None  # targets of the shared backward, cleared by the prologue
+        self.seg: Any = None  # training: SegmentIndex of the per-triple negatives (`_wants_segments`), built ahead
 
 
 class _SmallPlan(list):
@@ -142,6 +156,8 @@ class _ReplicaStep:
         self.direct: Any = None
         self.direct_lists: List[torch.Tensor] = []
         self.jobs_ride = False  # the step's copy / fill jobs go with the query / positive-score launch
+        # training: (row-id lists, their SegmentIndex) of the small update lists, built ahead (prologue | side stream)
+        self.small_ahead: Optional[Tuple[List[torch.Tensor], Any]] = None
 
 
 class _StepContext:
@@ -149,7 +165,7 @@ class _StepContext:
     `train_step_replicas` makes one per micro-batch, the inference entry points the default one (a plain forward).
     It lives as long as the call: nothing of a step stays on the module."""
 
-    __slots__ = ("batches", "training", "grad_scale", "fuse", "sm_fuse", "optimizer", "seg_ahead", "small_ahead", "d_rel")
+    __slots__ = ("batches", "training", "grad_scale", "fuse", "sm_fuse", "optimizer", "applies", "d_rel")
 
     def __init__(self, batches: Optional[List[_Batch]] = None, training: bool = False, grad_scale: float = 1.0) -> None:
         # the caller's batches (masks, weights), one per hosted replica: K7 may then be applied by the scoring call
@@ -160,36 +176,42 @@ class _StepContext:
         self.fuse: Optional[List[Optional[Dict[str, Any]]]] = None  # per replica: `_training_context`
         self.sm_fuse: Any = None  # ScoreMoving, fusable loss: loss.kernel_desc - the shards keep softmax partials
         self.optimizer: Any = None  # what the step's prologue plans the update for
-        # {id(group): SegmentIndex of its per-triple negatives}, started on the side stream before the scoring kernel
-        # is queued.  None: not wanted (inference; accumulating - indexed when the sum is applied)
-        self.seg_ahead: Optional[Dict[int, Any]] = None
-        # {id(replica step): (row-id lists, their SegmentIndex)} of the small update lists, from the step's prologue
-        # launch or the side stream.  None: no prologue (inference, ScoreMoving, accumulating)
-        self.small_ahead: Optional[Dict[int, Any]] = None
+        # a training step that applies its own update: the per-triple negatives' indices start under the forward
+        # (`_NegGroup.seg`), EmbeddingMoving runs the prologue launch.  False: inference; accumulating (indexed later)
+        self.applies = False
         self.d_rel: Optional[torch.Tensor] = None  # relation gradient, allocated and cleared by the prologue
+
+
+class _ShardGrads:
+    """What the backward of one hosted replica hands to the update, for one micro-batch."""
+
+    __slots__ = ("step", "rows", "segments")
+
+    def __init__(self, step: _ReplicaStep) -> None:
+        self.step = step
+        self.rows: List[Tuple[torch.Tensor, torch.Tensor]] = []  # (rows of the shard, gradient rows) lists
+        self.segments: List[Tuple[Any, torch.Tensor]] = []  # (per-triple group, d scores): segmented K9 over `group.seg`
 
 
 class _PendingUpdate:
     """Gradients of one micro-batch that have not been applied yet (gradient accumulation)."""
 
-    __slots__ = ("steps", "local_updates", "deferred", "d_rel")
+    __slots__ = ("shards", "d_rel")
 
-    def __init__(self, steps: List[_ReplicaStep], local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]],
-                 deferred: List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]], d_rel: torch.Tensor) -> None:
-        self.steps = steps                  # one per hosted replica
-        self.local_updates = local_updates  # per replica: (rows of the shard, gradient rows) lists
-        self.deferred = deferred            # (shard, per-triple group, d loss / d scores): reduced by the segmented K9
-        self.d_rel = d_rel                  # relation-table gradient (shared by the micro-batches of one update)
+    def __init__(self, shards: List[_ShardGrads], d_rel: torch.Tensor) -> None:
+        self.shards = shards  # one per hosted replica
+        self.d_rel = d_rel    # relation-table gradient (shared by the micro-batches of one update)
 
 
 class _MergedGroup:
     """The per-triple groups of several micro-batches seen as one scoring problem: queries, score
     gradients and row references stacked along the query axis (what the segmented K9 needs of a group)."""
 
-    __slots__ = ("query", "n_per_query")
+    __slots__ = ("query", "n_per_query", "seg")
 
     def __init__(self, query: torch.Tensor, n_per_query: int) -> None:
         self.query, self.n_per_query = query, n_per_query
+        self.seg: Any = None  # SegmentIndex over the stacked references
 
 
 class BessKGE(torch.nn.Module, ABC):
@@ -573,6 +595,21 @@ class BessKGE(torch.nn.Module, ABC):
         plain = not hasattr(optimizer, "kind") or optimizer.is_plain_sgd
         return plain, float(optimizer.lr) if hasattr(optimizer, "lr") else float(optimizer)
 
+    @staticmethod
+    def _update_route(optimizer: Any, dtype: torch.dtype, dense: Optional[bool] = None) -> Tuple[str, Any]:
+        """Which way a step's shard updates go, and the optimiser they go with.  "dense": `optimizer.dense`, every row
+        of the shard is stepped; "atomic": plain SGD on fp32 rows, fp32 atomics straight into the table; "coalesced":
+        everything else - contributions summed per unique row in fp32, one read-modify-write per touched row (the
+        stateful optimisers; plain SGD on f16 shards, where a packed-f16 atomic add would round the row once per
+        contribution), a bare learning rate coming back as an optimiser object.  `dense=False` asks for the route
+        of the rows alone: how `_small_plan` plans."""
+        plain, lr = BessKGE._plain_lr(optimizer)
+        if getattr(optimizer, "dense", False) if dense is None else dense:
+            return "dense", optimizer
+        if plain and dtype == torch.float32:
+            return "atomic", optimizer
+        return "coalesced", optimizer if hasattr(optimizer, "kind") else _PlainSGD(lr)
+
     def optimizer_state_rows_used(self) -> Dict[int, Tuple[int, int]]:
         """{table pointer: (state rows asked for so far, capacity)} of the tables with paged optimiser
         state; asked > capacity means rows are being stepped without state (raise `state_rows`)."""
@@ -621,14 +658,14 @@ class BessKGE(torch.nn.Module, ABC):
         s = state.s
         return o, (s[0] if n_state > 0 else None), (s[1] if n_state > 1 else None)
 
-    def _apply_optimizer(self, opt: Any, table: torch.Tensor, contributions: List[Tuple[torch.Tensor, torch.Tensor]],
-                         ahead: Optional[Tuple[List[torch.Tensor], Any]] = None,
-                         axpy: Optional[Tuple[torch.Tensor, torch.Tensor, float]] = None) -> None:
-        """General K9 + K10: all (row, gradient row) lists of a table coalesced per unique row and one
-        optimiser update per row (`bess_coalesced_update`: the sums are formed straight from the lists, in
-        a fixed order; every touched row is written once).  `contributions` all index `table`.
-        `ahead`: (row-id lists, their SegmentIndex) built earlier on the side stream (`_small_index_ahead`);
-        used when the lists turned out to be exactly those."""
+    def _row_lists(self, table: torch.Tensor, contributions: List[Tuple[torch.Tensor, torch.Tensor]],
+                   ahead: Optional[Tuple[List[torch.Tensor], Any]], shared_scratch: bool
+                   ) -> Tuple[Any, List[torch.Tensor]]:
+        """(SegmentIndex of the lists' row ids, their gradient arrays - at most `nat.MAX_ROW_LISTS`) of a table's
+        (row, gradient row) lists.  `ahead`: (row-id lists, their SegmentIndex) built by the step's prologue or on
+        the side stream (`_small_index_ahead`), taken when the lists turned out to be exactly those; else the index
+        is built here - with the step's shared long-row scratch, except (`_apply_optimizer_fused`) next to a
+        per-triple group's index, which was built with that scratch and is still live."""
         ids = [i.reshape(-1) for i, _ in contributions]
         grads = [g.contiguous() for _, g in contributions]
         seg = None
@@ -636,11 +673,21 @@ class BessKGE(torch.nn.Module, ABC):
             seg, grads = self._match_ahead(ahead, ids, grads)
         if seg is None:
             seg = nat.SegmentIndex(torch.cat(ids).contiguous(), table.shape[0],
-                                   scratch=self.update_state.seg_scratch)
-        o, s1, s2 = self._opt_desc(opt, table)
-        self._assign_state_rows(table, seg)
+                                   scratch=self.update_state.seg_scratch if shared_scratch else None)
         if len(grads) > nat.MAX_ROW_LISTS:
             grads = [torch.cat(grads, dim=0)]
+        return seg, grads
+
+    def _apply_optimizer(self, opt: Any, table: torch.Tensor, contributions: List[Tuple[torch.Tensor, torch.Tensor]],
+                         ahead: Optional[Tuple[List[torch.Tensor], Any]] = None,
+                         axpy: Optional[Tuple[torch.Tensor, torch.Tensor, float]] = None) -> None:
+        """General K9 + K10: all (row, gradient row) lists of a table coalesced per unique row and one
+        optimiser update per row (`bess_coalesced_update`: the sums are formed straight from the lists, in
+        a fixed order; every touched row is written once).  `contributions` all index `table`.
+        `ahead`: the step's `_ReplicaStep.small_ahead` (`_row_lists`)."""
+        seg, grads = self._row_lists(table, contributions, ahead, shared_scratch=True)
+        o, s1, s2 = self._opt_desc(opt, table)
+        self._assign_state_rows(table, seg)
         nat.coalesced_update(o, table, seg, grads, s1, s2, axpy=axpy)
 
     @staticmethod
@@ -675,15 +722,16 @@ class BessKGE(torch.nn.Module, ABC):
 
     def _small_plan(self, st: _ReplicaStep, optimizer: Any) -> Optional[List[torch.Tensor]]:
         """Row-id lists of a shard's small update lists (heads, tails, shared negatives, rows returned by C8), in
-        the order the backward will hand them over (`_apply_optimizer` checks that) - or None when the update
-        will not coalesce them through one index (plain SGD on an fp32 shard: atomics; per-triple groups
+        the order the backward will put them into the shard's `_ShardGrads.rows` (`_row_lists` checks that) - or
+        None when the update will not coalesce them through one index (the "atomic" route; per-triple groups
         reduced by the segmented K9 in a way that leaves the lists unknown until the backward has run).  A
         candidate list that the step's prologue concatenates is named by its parts: the index is built in the
-        same launch, from the lists as the sampler handed them over."""
-        plain, _ = self._plain_lr(optimizer)
-        if plain and self.score_fn.entity_embedding.dtype == torch.float32:
+        same launch, from the lists as the sampler handed them over.  The plan looks at the rows' route only: a
+        "dense" step is planned like the sparse one of its optimiser."""
+        route, _ = self._update_route(optimizer, self.score_fn.entity_embedding.dtype, dense=False)
+        if route == "atomic":
             return None
-        fn = self.score_fn
+        plain, _ = self._plain_lr(optimizer)
         plan = _SmallPlan()
 
         def add(src: RowSource, parts: Optional[List[torch.Tensor]] = None) -> None:
@@ -697,7 +745,7 @@ class BessKGE(torch.nn.Module, ABC):
             add(head)
             add(st.tail)
         for g in st.groups:
-            if not g.shared and g.neg.base is st.table and fn.supports_fused_segments:
+            if self._wants_segments(g, st):
                 # reduced by the segmented K9.  With ONE such group and a stateful optimiser the small lists
                 # ride along there (`_apply_optimizer_fused`) through an index of their own - the one planned
                 # here; several groups go through `_apply_optimizer` with lists that do not exist yet
@@ -718,26 +766,23 @@ class BessKGE(torch.nn.Module, ABC):
             plan.append(st.send_idx.reshape(-1))
         return plan
 
-    def _small_index_ahead(self, steps: List[_ReplicaStep], optimizer: Any) -> Dict[int, Any]:
+    def _small_index_ahead(self, st: _ReplicaStep, optimizer: Any) -> None:
         """The index of a shard's small lists only needs their row ids, which are inputs of the step: long lists
         (more than the prologue's one workgroup indexes) are indexed here - on the side stream, right behind the
-        forward kernels - instead of on the critical path after the backward."""
-        out: Dict[int, Any] = {}
-        for st in steps:
-            plan = None if st.direct is not None else self._small_plan(st, optimizer)
-            if plan is None:
-                continue
-            if sum(int(x.numel()) for x in plan) < 4096:
-                # a short list is indexed in ~10 us: not worth a fork / join of the streams (which costs
-                # about as much inside a replayed hipGraph); `_apply_optimizer` builds it where it is needed
-                continue
-            dev = st.table.device
-            side = self._aux_stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                out[id(st)] = (plan, nat.SegmentIndex(torch.cat(plan).contiguous(), st.table.shape[0],
-                                                      scratch=self.update_state.seg_scratch))
-        return out
+        forward kernels - instead of on the critical path after the backward (`st.small_ahead`)."""
+        plan = None if st.direct is not None else self._small_plan(st, optimizer)
+        if plan is None:
+            return
+        if sum(int(x.numel()) for x in plan) < self.prologue_index_max:
+            # a short list is indexed in ~10 us: not worth a fork / join of the streams (which costs
+            # about as much inside a replayed hipGraph); `_row_lists` builds it where it is needed
+            return
+        dev = st.table.device
+        side = self._aux_stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            st.small_ahead = (plan, nat.SegmentIndex(torch.cat(plan).contiguous(), st.table.shape[0],
+                                                     scratch=self.update_state.seg_scratch))
 
     #: row ids the step prologue's single workgroup indexes; longer lists go to the side stream
     prologue_index_max = 4096
@@ -752,14 +797,11 @@ class BessKGE(torch.nn.Module, ABC):
     #: launch behind it (`bess_pertriple_tail`); False keeps the four separate launches (tests compare the two)
     pertriple_tail = True
 
-    def _direct_scratch(self, table: torch.Tensor) -> Any:
-        return self.update_state.direct_scratch(table)
-
     def _direct_ok(self, st: _ReplicaStep, optimizer: Any, desc: Any) -> bool:
         """Does this step's shard update go through `bess_direct_update`?  One shard in the process, one group of
-        shared candidates of the own shard, query + positive score fused (so are their backwards), an update that
-        coalesces per row (f16 shard or a stateful optimiser - plain SGD on fp32 rows adds its atomics straight to
-        the table), full-size optimiser state, a backward that can add its candidate rows by row id, and a shard
+        shared candidates of the own shard, query + positive score fused (so are their backwards), the "coalesced"
+        route (not "atomic": plain SGD on fp32 rows adds its atomics straight to the table; not "dense": every row
+        is stepped), full-size optimiser state, a backward that can add its candidate rows by row id, and a shard
         whose fp32 image fits the scratch budget.  Not with a regulariser: its launch adds into the positives'
         gradient rows `dh`, `dt`, which this path never forms - such steps coalesce their lists as they did before
         the direct update existed."""
@@ -770,10 +812,8 @@ class BessKGE(torch.nn.Module, ABC):
         g = st.groups[0]
         if not g.shared or g.neg.base is not st.table or g.neg.idx is None or st.tail.base is not st.table:
             return False
-        if self._plain_lr(optimizer)[0] and st.table.dtype == torch.float32:
+        if self._update_route(optimizer, st.table.dtype)[0] != "coalesced":
             return False
-        if getattr(optimizer, "dense", False):
-            return False  # (every row is stepped: `_apply_dense`)
         rows = getattr(optimizer, "state_rows", None)
         if rows is not None and int(rows) < st.table.shape[0]:
             return False
@@ -785,12 +825,12 @@ class BessKGE(torch.nn.Module, ABC):
         """ONE launch in front of a training step's kernels (`bess_step_prologue`): the concatenated candidate
         list of an augmented step, the cleared relation gradient and backward targets, and - when the update
         coalesces them and they are few enough for one workgroup - the index of the step's small update lists.
-        Returns what `_small_index_ahead` would have: (lists, their SegmentIndex), or None."""
+        Returns what `_small_index_ahead` would have left on the step: (lists, their SegmentIndex), or None."""
         jobs = st.jobs or []
         desc = self.score_fn.kernel_desc()
         if len(jobs) + 2 <= nat.MAX_WORD_JOBS and self._direct_ok(st, optimizer, desc):
             # (the backward's sums leave as partial results with plain stores: nothing of it to clear)
-            st.direct = self._direct_scratch(st.table)
+            st.direct = self.update_state.direct_scratch(st.table)
             jobs.append(st.direct.increment_job())  # this step's generation number
         for g in st.groups:
             if st.direct is not None:
@@ -811,6 +851,9 @@ class BessKGE(torch.nn.Module, ABC):
                 st.d_recv.view(st.n, -1, st.d_recv.shape[1])[:, : st.ppp].zero_()
             else:
                 jobs.append((st.d_recv, None, 0))
+        # one workgroup indexes up to 4096 ids in ~12-15 us (notebook-size steps: cheaper than any fork / join);
+        # longer lists are indexed by the device-wide pipeline on the side stream, under the forward kernels
+        # (`_small_index_ahead`) - 12.5 k ids in the prologue's one workgroup were 58 us on the critical path
         plan = None if st.direct is not None else self._small_plan(st, optimizer)
         if plan is not None and sum(int(x.numel()) for x in plan) > self.prologue_index_max:
             plan = None
@@ -820,11 +863,6 @@ class BessKGE(torch.nn.Module, ABC):
             st.jobs = jobs
             st.jobs_ride = True
             return None
-        # one workgroup indexes up to 4096 ids in ~12-15 us (notebook-size steps: cheaper than any fork / join);
-        # longer lists are indexed by the device-wide pipeline on the side stream, under the forward kernels
-        # (`_small_index_ahead`) - 12.5 k ids in the prologue's one workgroup were 58 us on the critical path
-        if plan is not None and sum(int(x.numel()) for x in plan) > self.prologue_index_max:
-            plan = None
         if plan is not None and len(plan) > nat.MAX_ROW_LISTS:
             plan = None
         seg = nat.step_prologue(jobs, plan or (), st.table.shape[0], st.table.shape[1],
@@ -844,68 +882,53 @@ class BessKGE(torch.nn.Module, ABC):
                     and st.recv.shape[0] == st.n * (st.recv.shape[0] // st.n)
                     and sum(len(g.neg) for g in st.groups) == st.recv.shape[0] - st.n * st.ppp)
 
-    def _apply_dense(self, steps: List[_ReplicaStep], local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]],
-                     deferred: List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]], seg_index: Dict[int, Any],
-                     optimizer: Any, desc: nat.ModelDesc) -> None:
-        """`optimizer.dense`: the step every dense optimiser of torch / PopTorch takes - EVERY row of the shard, with
-        the step's gradient rows summed into a dense [M, W] fp32 matrix first (the direct-update accumulator: zero
-        between steps), zero for the rows the micro-batch did not touch.  What the notebooks' `poptorch.optim.AdamW`
-        does (`notebooks/1_biokg_training_inference.ipynb:525-531`): reproducible step for step, at the price of a
-        pass over the whole shard and its state per update - for shards that fit, not for BASELINE configs[4]."""
-        if getattr(optimizer, "state_rows", None) is not None:
-            raise ValueError("a dense optimiser steps every row: it cannot have paged state (state_rows)")
-        for st, upd in zip(steps, local_updates):
-            acc = self._direct_scratch(st.table).acc
-            lists = [(idx.reshape(-1).contiguous(), g.contiguous()) for idx, g in upd]
-            for table, g, go in deferred:
-                if table is st.table:  # per-triple negatives of the own shard: summed per unique row on chip first
-                    seg = seg_index[id(g)]
-                    gseg = nat.neg_pertriple_grad_segments(desc, g.query, table, g.n_per_query, go, seg)
-                    lists.append(nat.pad_segments(seg, gseg))
-            for i in range(0, len(lists), nat.MAX_ROW_LISTS):
-                nat.sparse_sgd_lists(acc, lists[i: i + nat.MAX_ROW_LISTS], -1.0)  # acc += rows (fp32 atomics)
-            plain, lr = self._plain_lr(optimizer)
-            if plain:
-                nat.dense_sgd(st.table, acc, lr)
-            else:
-                self._apply_optimizer_dense(optimizer, st.table, acc)
-            nat.step_prologue([(acc, None, 0)])  # back to zero for the next step
+    @staticmethod
+    def _add_row_lists(target: torch.Tensor, lists: List[Tuple[torch.Tensor, torch.Tensor]], lr: float,
+                       axpy: Optional[Tuple[torch.Tensor, torch.Tensor, float]] = None) -> None:
+        """`target[rows] -= lr * gradient rows` for every list (fp32 atomics: duplicates accumulate), one launch per
+        `nat.MAX_ROW_LISTS` lists.  `axpy` rides in that launch (callers give it with one launch's lists only)."""
+        for i in range(0, len(lists), nat.MAX_ROW_LISTS):
+            nat.sparse_sgd_lists(target, lists[i: i + nat.MAX_ROW_LISTS], lr, axpy=axpy)
 
-    def _apply_optimizer_dense(self, opt: Any, table: torch.Tensor, grad: torch.Tensor) -> None:
-        """Optimiser step on every row of a small replicated table (relation table, dense parameters):
-        the rows are their own segments - nothing to sort or sum."""
+    @staticmethod
+    def _segment_rows(desc: nat.ModelDesc, table: torch.Tensor, g: Any, go: torch.Tensor
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A per-triple group as one more row list: its unique rows with their summed gradients (the segmented K9);
+        the unused tail of the segment arrays is neutralised on the device (no read-back of the row count: no host
+        sync, and the step can be recorded into a hipGraph)."""
+        return nat.pad_segments(g.seg, nat.neg_pertriple_grad_segments(desc, g.query, table, g.n_per_query, go, g.seg))
+
+    def _step_replicated(self, optimizer: Any, table: torch.Tensor, grad: torch.Tensor) -> None:
+        """Optimiser step on every row of `table` with its dense gradient (the relation table, a dense parameter of
+        the scorer, a shard on the "dense" route): the rows are their own segments - nothing to sort or sum."""
+        plain, lr = self._plain_lr(optimizer)
+        if plain:
+            return nat.dense_sgd(table, grad, lr)
         segments = self.update_state.identity_segments(table)
-        o, s1, s2 = self._opt_desc(opt, table)
+        o, s1, s2 = self._opt_desc(optimizer, table)
         nat.apply_segments_opt(o, table, segments, grad.contiguous(), s1, s2)
 
-    def _apply_optimizer_fused(self, opt: Any, desc: nat.ModelDesc, table: torch.Tensor, g: _NegGroup,
-                               go: torch.Tensor, seg: Any, extras: List[Tuple[torch.Tensor, torch.Tensor]],
+    def _apply_optimizer_fused(self, opt: Any, desc: nat.ModelDesc, table: torch.Tensor, g: Any, go: torch.Tensor,
+                               extras: List[Tuple[torch.Tensor, torch.Tensor]],
                                ahead: Optional[Tuple[List[torch.Tensor], Any]] = None) -> None:
-        """K9 + K10 of a shard whose per-triple negatives form one group, for a stateful optimiser:
-        the big per-row reduction applies the optimiser itself (no [unique rows, W] gradient, no host
+        """K9 + K10 of a shard whose per-triple negatives form one group (indexed by `g.seg`), for the "coalesced"
+        route: the big per-row reduction applies the optimiser itself (no [unique rows, W] gradient, no host
         sync); the small lists (heads, tails, ...) are summed per unique row first and ride along, so
         every touched row still gets one update with its total gradient."""
         o, s1, s2 = self._opt_desc(opt, table)
         xmap = xsum = xseg = keep = None
         if extras:
-            ids = [i.reshape(-1) for i, _ in extras]
-            grads = [x.contiguous() for _, x in extras]
-            xseg = None
-            if ahead is not None:  # built ahead: by the step's prologue, or on the side stream behind the forward
-                xseg, grads = self._match_ahead(ahead, ids, grads)
-            if xseg is None:
-                xseg = nat.SegmentIndex(torch.cat(ids).contiguous(), table.shape[0])
-            if len(grads) > nat.MAX_ROW_LISTS:
-                grads = [torch.cat(grads, dim=0)]
+            xseg, grads = self._row_lists(table, extras, ahead, shared_scratch=False)
             xsum = nat.coalesced_update(None, table, xseg, grads, sum_only=True)
-            xmap, keep = nat.map_extra_rows(seg, xseg)
-        self._assign_state_rows(table, seg)
-        nat.neg_pertriple_step_segments(desc, g.query, table, g.n_per_query, go, seg, o, s1, s2, xmap, xsum)
+            xmap, keep = nat.map_extra_rows(g.seg, xseg)
+        self._assign_state_rows(table, g.seg)
+        nat.neg_pertriple_step_segments(desc, g.query, table, g.n_per_query, go, g.seg, o, s1, s2, xmap, xsum)
         if extras:  # rows of the small lists that no negative points at
             self._assign_state_rows(table, xseg, keep)
             nat.apply_segments_opt(o, table, xseg, xsum, s1, s2, keep=keep)
 
     def _wants_segments(self, g: _NegGroup, st: _ReplicaStep) -> bool:
+        """Is this group's gradient reduced by the segmented K9 (per-triple negatives read from the own shard)?"""
         return not g.shared and g.neg.base is st.table and self.score_fn.supports_fused_segments
 
     def _segment_index_on_side(self, g: _NegGroup, st: _ReplicaStep) -> Any:
@@ -916,57 +939,58 @@ class BessKGE(torch.nn.Module, ABC):
             return nat.SegmentIndex(g.neg.idx, st.table.shape[0], width=st.table.shape[1],
                                     scratch=self.update_state.seg_scratch)
 
-    def _prefetch_segment_indices(self, steps: List[_ReplicaStep], ctx: _StepContext) -> Dict[int, Any]:
+    def _prefetch_segment_indices(self, steps: List[_ReplicaStep]) -> None:
         """The inverted indices of per-triple negatives only depend on the sampled indices: they are
         built on a side stream while the forward kernels run (`_run_groups_one` starts them before the
-        scoring kernel of their group is queued - `ctx.seg_ahead`; groups scored elsewhere are started here)."""
-        seg_index: Dict[int, Any] = dict(ctx.seg_ahead or {})
+        scoring kernel of their group is queued - `_NegGroup.seg`; groups scored elsewhere are started here)."""
         for st in steps:
             for g in st.groups:
-                if self._wants_segments(g, st) and id(g) not in seg_index:
-                    seg_index[id(g)] = self._segment_index_on_side(g, st)
-        return seg_index
+                if g.seg is None and self._wants_segments(g, st):
+                    g.seg = self._segment_index_on_side(g, st)
+
+    @staticmethod
+    def _merge_segments(pending: List[_PendingUpdate]) -> List[List[List[Tuple[Any, torch.Tensor]]]]:
+        """Per hosted shard, per merged group: the (group, d_scores) of every micro-batch that become one group - the
+        k-th group of a side on that shard, in the order of first appearance.  No device work: the caller stacks them."""
+        slots: List[Dict[Tuple[int, int], List[Tuple[Any, torch.Tensor]]]] = [{} for _ in pending[0].shards]
+        for p in pending:
+            for mine, sh in zip(slots, p.shards):
+                seen: Dict[int, int] = {}
+                for g, go in sh.segments:
+                    k = seen[g.side] = seen.get(g.side, -1) + 1
+                    items = mine.setdefault((g.side, k), [])
+                    if items and items[0][0].n_per_query != g.n_per_query:
+                        raise RuntimeError("accumulated micro-batches differ in negatives per triple")
+                    items.append((g, go))
+        return [list(mine.values()) for mine in slots]
 
     def apply_accumulated(self, pending: List[_PendingUpdate], optimizer: Any) -> None:
         """ONE optimiser step with the summed gradients of the micro-batches in `pending`
         (`train_step_replicas(..., pending=...)`; PopTorch's `Training.gradientAccumulation`, reference
         `notebooks/1_biokg_training_inference.ipynb:408-417,470-477`).  All of them were computed from the
-        tables as they are now.  Row lists are concatenated per shard; the per-triple groups of the
-        micro-batches become one group (queries, score gradients and references stacked), so the
-        segmented reduction still sums every row's references on chip and every touched row gets one
-        update - the same kernels as a single micro-batch, one index over all references."""
+        tables as they are now.  Per shard (`_ShardGrads`), the row lists are concatenated and the per-triple
+        groups of the micro-batches become one group (`_merge_segments`: queries, score gradients and references
+        stacked), so the segmented reduction still sums every row's references on chip and every touched row gets
+        one update - the same kernels as a single micro-batch, one index over all references."""
         if not pending:
             return
-        first = pending[0]
-        steps = first.steps
-        local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]] = [[] for _ in steps]
-        deferred: List[Tuple[torch.Tensor, Any, torch.Tensor]] = []
-        seg_index: Dict[int, Any] = {}
+        shards = [_ShardGrads(sh.step) for sh in pending[0].shards]
         for p in pending:
-            for mine, upd in zip(local_updates, p.local_updates):
-                mine.extend(upd)
-        # per-triple groups: merge the k-th group of every micro-batch (same shard, side and list length)
-        by_slot: Dict[Tuple[int, int, int], List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]]] = {}
-        for p in pending:
-            seen: Dict[Tuple[int, int], int] = {}
-            for table, g, go in p.deferred:
-                k = seen.get((table.data_ptr(), g.side), 0)
-                seen[(table.data_ptr(), g.side)] = k + 1
-                by_slot.setdefault((table.data_ptr(), g.side, k), []).append((table, g, go))
+            for mine, sh in zip(shards, p.shards):
+                mine.rows.extend(sh.rows)
         scratch = self.update_state.seg_scratch
-        for items in by_slot.values():
-            table, g0, go0 = items[0]
-            if len(items) == 1:
-                merged, go, idx = g0, go0, g0.neg.idx
-            else:
-                if any(g.n_per_query != g0.n_per_query for _, g, _ in items):
-                    raise RuntimeError("accumulated micro-batches differ in negatives per triple")
-                merged = _MergedGroup(torch.cat([g.query for _, g, _ in items], dim=0), g0.n_per_query)
-                go = torch.cat([x for _, _, x in items], dim=0)
-                idx = torch.cat([g.neg.idx.reshape(-1) for _, g, _ in items])
-            seg_index[id(merged)] = nat.SegmentIndex(idx, table.shape[0], width=table.shape[1], scratch=scratch)
-            deferred.append((table, merged, go))
-        self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, self.score_fn.kernel_desc(), first.d_rel)
+        for mine, merged in zip(shards, self._merge_segments(pending)):
+            table = mine.step.table
+            for items in merged:
+                group, go = items[0]
+                idx = group.neg.idx
+                if len(items) > 1:
+                    group = _MergedGroup(torch.cat([g.query for g, _ in items], dim=0), group.n_per_query)
+                    go = torch.cat([x for _, x in items], dim=0)
+                    idx = torch.cat([g.neg.idx.reshape(-1) for g, _ in items])
+                group.seg = nat.SegmentIndex(idx, table.shape[0], width=table.shape[1], scratch=scratch)
+                mine.segments.append((group, go))
+        self._apply_updates(shards, optimizer, self.score_fn.kernel_desc(), pending[0].d_rel)
         pending.clear()
 
     def _relation_gradient(self, ctx: _StepContext, pending: Optional[List[_PendingUpdate]]) -> torch.Tensor:
@@ -979,115 +1003,30 @@ class BessKGE(torch.nn.Module, ABC):
         rel_table = self.score_fn.relation_embedding.data
         return torch.zeros(rel_table.shape, dtype=torch.float32, device=rel_table.device)
 
-    def _apply_updates(self, steps: List[_ReplicaStep], local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]],
-                       deferred: List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]], seg_index: Dict[int, Any],
-                       optimizer: Any, desc: nat.ModelDesc, d_rel: torch.Tensor,
-                       small_ahead: Optional[Dict[int, Any]] = None) -> None:
-        """K9 + K10 on every hosted shard and C9 + update of the relation table (`small_ahead`: the step's)."""
+    def _hand_over(self, shards: List[_ShardGrads], d_rel: torch.Tensor, optimizer: Any, desc: nat.ModelDesc,
+                   pending: Optional[List[_PendingUpdate]]) -> None:
+        """The end of a training micro-batch: its gradients wait in `pending` (accumulation), or are applied."""
+        if pending is None:
+            return self._apply_updates(shards, optimizer, desc, d_rel)
+        pending.append(_PendingUpdate(shards, d_rel))
+
+    def _apply_updates(self, shards: List[_ShardGrads], optimizer: Any, desc: nat.ModelDesc, d_rel: torch.Tensor
+                       ) -> None:
+        """K9 + K10 on every hosted shard and C9 + update of the relation table and the scorer's dense parameters."""
         group = self._group()
         rel_table = self.score_fn.relation_embedding.data
-        small_ahead = small_ahead or {}
-        plain, lr = self._plain_lr(optimizer)
-        # f16 shards: a packed-f16 atomic add rounds the row once per contribution.  Plain SGD on them
-        # therefore takes the coalescing path of the stateful optimisers: contributions summed per unique
-        # row in fp32, one read-modify-write (one rounding) per touched row and step.
-        plain_rows = plain and self.score_fn.entity_embedding.dtype == torch.float32
-        if plain and not plain_rows and not hasattr(optimizer, "kind"):
-            optimizer = _PlainSGD(lr)
-        main = torch.cuda.current_stream(rel_table.device)
-        side = self._aux_stream(rel_table.device)
+        route, optimizer = self._update_route(optimizer, self.score_fn.entity_embedding.dtype)
         # K9 + K10.  Every gradient has been computed from the pre-update tables by now.
-        main.wait_stream(side)
-        # C9: replicated relation table
-        # (single process: d_rel already holds the sum over the local replicas)
+        torch.cuda.current_stream(rel_table.device).wait_stream(self._aux_stream(rel_table.device))
+        # C9: replicated relation table (single process: d_rel already holds the sum over the local replicas)
         (d_rel,) = group.all_reduce_sum([d_rel]) if len(group.local_shards) == 1 else (d_rel,)
         mean_over_replicas = getattr(optimizer, "replica_reduction", "sum") == "mean" and group.n_shard > 1
         if mean_over_replicas:
             d_rel = d_rel / group.n_shard
-        # plain SGD on the relation table rides along in the launch that updates the (one) shard hosted here
-        rel_axpy, rel_done = None, False
-        if plain and not plain_rows and rel_table.dtype == steps[-1].table.dtype \
-                and not any(item[0] is steps[-1].table for item in deferred):
-            rel_axpy = (rel_table, d_rel, -lr)  # (with the last shard hosted here)
-        if plain_rows and rel_table.dtype == steps[-1].table.dtype and local_updates and local_updates[-1] \
-                and sum(int(i_.numel()) for i_, _ in local_updates[-1]) < self.coalesce_sgd_from \
-                and len(local_updates[-1]) <= nat.MAX_ROW_LISTS:
-            rel_axpy = (rel_table, d_rel, -lr)  # (in the launch of the last shard's atomic row updates)
-        if getattr(optimizer, "dense", False):
-            self._apply_dense(steps, local_updates, deferred, seg_index, optimizer, desc)
-            if plain:
-                nat.dense_sgd(rel_table, d_rel, lr)
-            else:
-                self._apply_optimizer_dense(optimizer, rel_table, d_rel)
-            rel_done = True
-        elif plain_rows:
-            # per-triple negatives of the own shard: segmented reduction.  A shard with a
-            # single such group gets the SGD step fused into the reduction; with two
-            # ("ht") all row gradients are formed before the first row is changed.
-            per_table: Dict[int, List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]]] = {}
-            for item in deferred:
-                per_table.setdefault(item[0].data_ptr(), []).append(item)
-            for items in per_table.values():
-                if len(items) == 1:
-                    table, g, go = items[0]
-                    nat.neg_pertriple_grad_segments(desc, g.query, table, g.n_per_query, go, seg_index[id(g)],
-                                                    fused_sgd_lr=lr)
-                else:
-                    grads = [nat.neg_pertriple_grad_segments(desc, g.query, table, g.n_per_query, go,
-                                                             seg_index[id(g)]) for table, g, go in items]
-                    for (table, g, _), gseg in zip(items, grads):
-                        nat.apply_segments_sgd(table, seg_index[id(g)], gseg, lr)
-            # everything else: sparse atomic SGD on the shard (duplicates accumulate), one launch per shard -
-            # unless the lists are long (the gradients of per-triple negatives that C8 returned: half a million
-            # 2 KB rows at C2's shape): fp32 atomics on them run at ~1.8 TB/s of read-modify-write (1.17 ms); the
-            # coalescing path of the stateful optimisers - sort the ids once (0.09 ms), sum per unique row straight
-            # from the lists, one write per touched row (0.3 ms) - is 2.5x faster there
-            for st, upd in zip(steps, local_updates):
-                if sum(int(idx.numel()) for idx, _ in upd) >= self.coalesce_sgd_from:
-                    self._apply_optimizer(_PlainSGD(lr), st.table, list(upd))
-                    continue
-                lists = [(idx.contiguous(), g.contiguous()) for idx, g in upd]
-                ride = rel_axpy if (st is steps[-1] and len(lists) <= nat.MAX_ROW_LISTS) else None
-                for i in range(0, len(lists), nat.MAX_ROW_LISTS):
-                    nat.sparse_sgd_lists(st.table, lists[i: i + nat.MAX_ROW_LISTS], lr, axpy=ride)
-                rel_done = rel_done or ride is not None
-        else:
-            # non-linear optimisers need the *summed* gradient of every row first
-            native = desc.scorer <= nat.COMPLEX
-            for st, upd in zip(steps, local_updates):
-                mine = [item for item in deferred if item[0] is st.table]
-                if st.direct is not None:
-                    assert not upd and not mine, "a direct-update step hands over no row gradients"
-                    o, s1, s2 = self._opt_desc(optimizer, st.table)
-                    last = st is steps[-1]
-                    nat.direct_update(o, st.table, [x.contiguous() for x in st.direct_lists], st.direct, s1, s2,
-                                      axpy=rel_axpy if last else None)
-                    rel_done = rel_done or (last and rel_axpy is not None)
-                    continue
-                if native and len(mine) == 1:
-                    table, g, go = mine[0]
-                    self._apply_optimizer_fused(optimizer, desc, table, g, go, seg_index[id(g)], list(upd),
-                                                small_ahead.get(id(st)))
-                    continue
-                contrib = list(upd)
-                for table, g, go in deferred:
-                    if table is st.table:
-                        seg = seg_index[id(g)]
-                        gseg = nat.neg_pertriple_grad_segments(desc, g.query, table, g.n_per_query, go, seg)
-                        # the group's unique rows with their summed gradients become one more row list; the unused
-                        # tail of the segment arrays is neutralised on the device (no read-back of the row
-                        # count: no host sync, and the step can be recorded into a hipGraph)
-                        contrib.append(nat.pad_segments(seg, gseg))
-                last = st is steps[-1]
-                self._apply_optimizer(optimizer, st.table, contrib, small_ahead.get(id(st)),
-                                      axpy=rel_axpy if last else None)
-                rel_done = rel_done or (last and rel_axpy is not None)
-        if rel_done:
-            pass  # updated in the shard's launch (or by the dense branch above)
-        elif plain:
-            nat.dense_sgd(rel_table, d_rel, lr)
-        else:
-            self._apply_optimizer_dense(optimizer, rel_table, d_rel)
+        update = getattr(self, "_update_" + route)  # `_update_dense`, `_update_atomic` or `_update_coalesced`
+        # plain SGD on the relation table may ride along in the launch that updates the last shard hosted here
+        if not update(shards, optimizer, desc, rel_table, d_rel):
+            self._step_replicated(optimizer, rel_table, d_rel)
         # dense parameters of the scorer (ConvE's query network): replicated like the relation table
         dense_grads = self.score_fn.__dict__.pop("dense_grads", {})
         for p in self.score_fn.dense_parameters():
@@ -1099,10 +1038,86 @@ class BessKGE(torch.nn.Module, ABC):
             g = g.reshape(as_table.shape).contiguous()
             if mean_over_replicas:
                 g = g / group.n_shard
-            if plain:
-                nat.dense_sgd(as_table, g, lr)
+            self._step_replicated(optimizer, as_table, g)
+
+    # The routes of `_update_route`: each returns whether the relation table's step rode along in a shard's launch
+    def _update_dense(self, shards: List[_ShardGrads], optimizer: Any, desc: nat.ModelDesc, rel_table: torch.Tensor,
+                      d_rel: torch.Tensor) -> bool:
+        """`optimizer.dense`: the step every dense optimiser of torch / PopTorch takes - EVERY row of the shard, with
+        the step's gradient rows summed into a dense [M, W] fp32 matrix first (the direct-update accumulator: zero
+        between steps), zero for the rows the micro-batch did not touch.  What the notebooks' `poptorch.optim.AdamW`
+        does (`notebooks/1_biokg_training_inference.ipynb:525-531`): reproducible step for step, at the price of a
+        pass over the whole shard and its state per update - for shards that fit, not for BASELINE configs[4]."""
+        if getattr(optimizer, "state_rows", None) is not None:
+            raise ValueError("a dense optimiser steps every row: it cannot have paged state (state_rows)")
+        for sh in shards:
+            table = sh.step.table
+            acc = self.update_state.direct_scratch(table).acc
+            lists = [(idx.reshape(-1).contiguous(), g.contiguous()) for idx, g in sh.rows]
+            # per-triple negatives of the own shard: summed per unique row on chip first
+            lists += [self._segment_rows(desc, table, g, go) for g, go in sh.segments]
+            self._add_row_lists(acc, lists, -1.0)  # acc += rows
+            self._step_replicated(optimizer, table, acc)
+            nat.step_prologue([(acc, None, 0)])  # back to zero for the next step
+        return False
+
+    def _update_atomic(self, shards: List[_ShardGrads], optimizer: Any, desc: nat.ModelDesc, rel_table: torch.Tensor,
+                       d_rel: torch.Tensor) -> bool:
+        """Plain SGD on fp32 rows.  Per-triple negatives of the own shard first, on every shard: a single such group
+        gets the SGD step fused into the segmented reduction; with two ("ht") all row gradients are formed before
+        the first row is changed.  Then everything else: sparse atomic SGD (duplicates accumulate), one launch per
+        shard, with which the last shard's carries the relation step - unless the lists are long (`coalesce_sgd_from`;
+        per-triple negatives' gradients that C8 returned, half a million 2 KB rows at C2's shape): fp32 atomics run
+        at ~1.8 TB/s of read-modify-write there (1.17 ms); the coalescing path - sort the ids once (0.09 ms), sum per
+        unique row straight from the lists, one write per touched row (0.3 ms) - is 2.5x faster."""
+        _, lr = self._plain_lr(optimizer)
+        for sh in shards:
+            table = sh.step.table
+            if len(sh.segments) == 1:
+                g, go = sh.segments[0]
+                nat.neg_pertriple_grad_segments(desc, g.query, table, g.n_per_query, go, g.seg, fused_sgd_lr=lr)
             else:
-                self._apply_optimizer_dense(optimizer, as_table, g)
+                grads = [nat.neg_pertriple_grad_segments(desc, g.query, table, g.n_per_query, go, g.seg)
+                         for g, go in sh.segments]
+                for (g, _), gseg in zip(sh.segments, grads):
+                    nat.apply_segments_sgd(table, g.seg, gseg, lr)
+        rode = False
+        for sh in shards:
+            table = sh.step.table
+            if sum(int(idx.numel()) for idx, _ in sh.rows) >= self.coalesce_sgd_from:
+                self._apply_optimizer(_PlainSGD(lr), table, list(sh.rows))
+                continue
+            lists = [(idx.contiguous(), g.contiguous()) for idx, g in sh.rows]
+            ride = (sh is shards[-1] and 0 < len(lists) <= nat.MAX_ROW_LISTS and rel_table.dtype == table.dtype)
+            self._add_row_lists(table, lists, lr, axpy=(rel_table, d_rel, -lr) if ride else None)
+            rode = rode or ride
+        return rode
+
+    def _update_coalesced(self, shards: List[_ShardGrads], optimizer: Any, desc: nat.ModelDesc,
+                          rel_table: torch.Tensor, d_rel: torch.Tensor) -> bool:
+        """Non-linear optimisers (and one rounding per f16 row) need the *summed* gradient of every row first: the
+        direct update where the step was set up for it; one per-triple group of a native scorer with the optimiser
+        inside its segmented reduction (`_apply_optimizer_fused`); else all lists - per-triple groups as one more
+        list each - through `_apply_optimizer`.  The relation step of plain SGD rides with the last shard's launch
+        unless that shard has per-triple groups of its own."""
+        plain, lr = self._plain_lr(optimizer)
+        last = shards[-1]
+        ride = plain and rel_table.dtype == last.step.table.dtype and not last.segments
+        native = desc.scorer <= nat.COMPLEX
+        for sh in shards:
+            st = sh.step
+            axpy = (rel_table, d_rel, -lr) if ride and sh is last else None
+            if st.direct is not None:
+                assert not sh.rows and not sh.segments, "a direct-update step hands over no row gradients"
+                o, s1, s2 = self._opt_desc(optimizer, st.table)
+                nat.direct_update(o, st.table, [x.contiguous() for x in st.direct_lists], st.direct, s1, s2, axpy=axpy)
+            elif native and len(sh.segments) == 1:
+                g, go = sh.segments[0]
+                self._apply_optimizer_fused(optimizer, desc, st.table, g, go, list(sh.rows), st.small_ahead)
+            else:
+                contrib = sh.rows + [self._segment_rows(desc, st.table, g, go) for g, go in sh.segments]
+                self._apply_optimizer(optimizer, st.table, contrib, st.small_ahead, axpy=axpy)
+        return ride
 
 
     # ------------------------------------------------------ group execution
@@ -1111,10 +1126,10 @@ class BessKGE(torch.nn.Module, ABC):
                         loss_batch: Optional[_Batch] = None) -> torch.Tensor:
         """`fuse`: the replica's entry of `ctx.fuse`, unless K7 has to follow the pass; `partials_loss`: ScoreMoving's
         `ctx.sm_fuse(n)`; `loss_batch`: the replica's batch when K8 may run behind the scoring call (shared negatives)."""
-        if ctx.seg_ahead is not None and st is not None and self._wants_segments(g, st):
+        if ctx.applies and st is not None and self._wants_segments(g, st):
             # training: the inverted index of the negatives only needs their row ids - start it on the
             # side stream *before* the scoring kernel is queued, so that it runs under it
-            ctx.seg_ahead[id(g)] = self._segment_index_on_side(g, st)
+            g.seg = self._segment_index_on_side(g, st)
         if g.query is None:
             g.query, g.query_ctx = self.score_fn.query_fwd(g.side, g.ent, g.rel_idx)
         if g.shared and loss_batch is not None and st is not None and len(st.groups) == 1 and g.sel is None:
@@ -1191,8 +1206,7 @@ class BessKGE(torch.nn.Module, ABC):
         for f, b in zip(ctx.fuse, batches):
             if f is not None:
                 f["weight"] = self._triple_weight(b, dev, grad_scale)
-        if pending is None:  # (accumulating: the references of all micro-batches are indexed together when applied)
-            ctx.seg_ahead = {}
+        ctx.applies = pending is None  # (accumulating: the references of all micro-batches are indexed when applied)
         return ctx
 
     def train_step(self, optimizer: Any, **batch: torch.Tensor) -> Dict[str, Any]:
@@ -1223,10 +1237,10 @@ class EmbeddingMovingBessKGE(BessKGE):
         # NativeGroup: gather into the send buffer + all-to-all behind one entry point (bess_pack_exchange)
         packed_exchange = (hasattr(group, "pack_exchange")
                            and (W * self.score_fn.entity_embedding.element_size()) % 16 == 0)
-        early = ctx.small_ahead  # not None: a training step that applies its own update
+        early = ctx.applies  # a training step that applies its own update: the prologue launch prepares it
         for shard, b in zip(group.local_shards, batches):
             st = _ReplicaStep()
-            if early is not None:
+            if early:
                 st.jobs = []
             st.table = self._local_table(shard)
             dev = st.table.device
@@ -1266,15 +1280,13 @@ class EmbeddingMovingBessKGE(BessKGE):
             g0 = st.groups[0]
             st.fused_qt = (len(st.groups) == 1 and g0.sel is None and fn.supports_fused_query_triple
                            and st.tail.base.dtype == st.table.dtype)
-            if early is not None:
+            if early:
                 # training: what the step's kernels need prepared - the concatenated candidate list, cleared
                 # gradient targets, the index of the small update lists (it needs only row ids) - in ONE launch
                 d_rel = None
                 if i == 0:  # the relation gradient is shared by the replicas hosted here
                     d_rel = ctx.d_rel = torch.empty(rel_table.shape, dtype=torch.float32, device=rel_table.device)
-                ahead = self._launch_prologue(st, ctx.optimizer, d_rel)
-                if ahead is not None:
-                    early[id(st)] = ahead
+                st.small_ahead = self._launch_prologue(st, ctx.optimizer, d_rel)
             if st.fused_qt:
                 # K2 + K3 + K6: the query of the one negative-scoring problem and the positive scores, one launch
                 g0.query, st.positive_score = fn.query_triple_fwd(g0.side, RowSource(st.table, st.head_idx), st.tail,
@@ -1284,9 +1296,9 @@ class EmbeddingMovingBessKGE(BessKGE):
             else:
                 st.positive_score, st.triple_ctx = fn.triple_fwd(
                     RowSource(st.table, st.head_idx), st.tail, st.rel_idx)
-            if early is not None and id(st) not in early:
+            if early and st.small_ahead is None:
                 # longer lists: indexed on the side stream, started before the scoring kernels are queued
-                early.update(self._small_index_ahead([st], ctx.optimizer))
+                self._small_index_ahead(st, ctx.optimizer)
             fz = ctx.fuse[i] if ctx.fuse else None
             if fz is not None and fz.get("masked"):
                 # K7 inside the fused pass: one per-triple group over all triples, a mask of 1 or S rows, no 'ht' halves
@@ -1451,29 +1463,24 @@ class EmbeddingMovingBessKGE(BessKGE):
         by a second all-to-all (C8); K9+K10 apply them to the shard sparsely.
         """
         ctx = self._training_context(batches, optimizer, pending, grad_scale)
-        if pending is None:  # a step that applies its own update: the prologue launch prepares it
-            ctx.small_ahead = {}
         group = self._group()
         fn = self.score_fn
         n = group.n_shard
         W = self.entity_embedding_size
         steps = self._score_replicas(batches, ctx)
-        seg_index = {} if pending is not None else self._prefetch_segment_indices(steps, ctx)
-        if pending is None:
-            ctx.small_ahead.update(self._small_index_ahead([st for st in steps if id(st) not in ctx.small_ahead],
-                                                           optimizer))
+        if ctx.applies:
+            self._prefetch_segment_indices(steps)
         desc = fn.kernel_desc()
         results = []
         # (the relation gradient of accumulated micro-batches is summed in the first one's buffer)
         d_rel = self._relation_gradient(ctx, pending)
         back: List[torch.Tensor] = []
-        deferred: List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]] = []
-        local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]] = []
-        for st, b in zip(steps, batches):
+        shards = [_ShardGrads(st) for st in steps]
+        for sh, b in zip(shards, batches):
+            st, upd = sh.step, sh.rows  # (rows of my shard, gradient rows)
             out, d_pos, d_neg = self._finish(st, b, want_grad=True, scale=grad_scale)
             results.append(out)
             dev = st.table.device
-            upd: List[Tuple[torch.Tensor, torch.Tensor]] = []  # (rows of my shard, gradient rows)
             d_recv = None
             if n > 1:
                 d_recv = st.d_recv  # cleared by the step's prologue launch
@@ -1502,13 +1509,7 @@ class EmbeddingMovingBessKGE(BessKGE):
                 sink(RowSource(st.table, st.head_idx), dh)
                 sink(st.tail, dt)
             # K4'/K5' + K6': negative scores
-            if len(st.groups) == 1:
-                d_outs = [d_neg]
-            else:
-                cut = st.ppp // 2
-                dn3 = d_neg.reshape(st.n, st.ppp, -1)
-                d_outs = [dn3[:, :cut].reshape(-1, dn3.shape[-1]).contiguous(),
-                          dn3[:, cut:].reshape(-1, dn3.shape[-1]).contiguous()]
+            d_outs = [d_neg] if len(st.groups) == 1 else _split_ht(d_neg, st.ppp)
             for g, go in zip(st.groups, d_outs):
                 if g.shared and st.direct is not None:
                     # both products as partial sums (plain stores, no atomics); the query / triple backward adds them
@@ -1522,7 +1523,7 @@ class EmbeddingMovingBessKGE(BessKGE):
                 elif g.shared:
                     dq, dn = nat.neg_score_shared_bwd(desc, g.query, g.neg, g.out, go, prezeroed=g.bwd_buf)
                     sink(g.neg, dn)
-                elif g.neg.base is st.table and fn.supports_fused_segments:
+                elif self._wants_segments(g, st):
                     # per-triple negatives read straight from the shard: no [S*N, W]
                     # gradient, no atomics - references are grouped by destination row
                     # and reduced on chip (K9), unique rows updated afterwards (K10)
@@ -1531,7 +1532,7 @@ class EmbeddingMovingBessKGE(BessKGE):
                     else:
                         dq, _ = nat.neg_score_pertriple_bwd(desc, g.query, g.neg, g.n_per_query, go,
                                                             want_d_neg=False)
-                    deferred.append((st.table, g, go))
+                    sh.segments.append((g, go))
                 else:
                     # Negatives that arrived through the all-to-all are named once each by the static index map
                     # (`_run_groups`) and nothing else contributes to their rows of the receive-buffer gradient:
@@ -1560,9 +1561,8 @@ class EmbeddingMovingBessKGE(BessKGE):
                     sink(g.ent, dx)
             if n > 1:
                 # all of them summed into the receive layout by ONE launch (d_recv -= -1 * g, fp32 atomics)
-                lists = [(x.contiguous(), g.contiguous()) for x, g in into_recv if x is not None]
-                for i in range(0, len(lists), nat.MAX_ROW_LISTS):
-                    nat.sparse_sgd_lists(d_recv, lists[i:i + nat.MAX_ROW_LISTS], -1.0)
+                self._add_row_lists(d_recv, [(x.contiguous(), g.contiguous()) for x, g in into_recv if x is not None],
+                                    -1.0)
                 for x, g in into_recv:
                     if x is None:  # rows in place
                         nat.scatter_add_rows(d_recv, None, g)
@@ -1570,15 +1570,11 @@ class EmbeddingMovingBessKGE(BessKGE):
                 if st.ext_src is not None:  # rows appended for augmentation -> their origin
                     sink(st.ext_src, d_recv[st.recv_rows:].contiguous())
                 back.append(d_recv[: st.recv_rows].reshape(n, -1, W))
-            local_updates.append(upd)
         if n > 1:
             returned = group.all_to_all(back)  # C8
-            for st, upd, g in zip(steps, local_updates, returned):
-                upd.append((st.send_idx.reshape(-1), g.reshape(-1, W)))
-        if pending is not None:
-            pending.append(_PendingUpdate(steps, local_updates, deferred, d_rel))
-        else:
-            self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, desc, d_rel, ctx.small_ahead)
+            for sh, g in zip(shards, returned):
+                sh.rows.append((sh.step.send_idx.reshape(-1), g.reshape(-1, W)))
+        self._hand_over(shards, d_rel, optimizer, desc, pending)
         return results
 
 
@@ -1777,12 +1773,14 @@ class ScoreMovingBessKGE(BessKGE):
                  and kind in (nat.LOSS_LOGSIGMOID, nat.LOSS_SSCE) and fn.supports_fused_segments)
         ctx.sm_fuse = self.loss_fn.kernel_desc if fused else None
         steps = self._score_replicas(batches, ctx)
-        seg_index = {} if pending is not None else self._prefetch_segment_indices(steps, ctx)
+        if ctx.applies:
+            self._prefetch_segment_indices(steps)
         desc = fn.kernel_desc()
         d_rel = self._relation_gradient(ctx, pending)
         results, d_scores, d_tails = [], [], []
-        local_updates: List[List[Tuple[torch.Tensor, torch.Tensor]]] = []
-        for st, b in zip(steps, batches):
+        shards = [_ShardGrads(st) for st in steps]
+        for sh, b in zip(shards, batches):
+            st = sh.step
             with_norm = fused and any(g.partials is not None for g in st.groups)
             out, d_pos, d_neg = self._finish(st, b, want_grad=True, want_norm=with_norm, scale=grad_scale)
             results.append(out)
@@ -1797,21 +1795,15 @@ class ScoreMovingBessKGE(BessKGE):
                                    d_rel)
             if self.regularizer is not None:
                 self._regularize(st, b, out, grad_scale, dh, dt, d_rel)
-            local_updates.append([(st.head_idx, dh)])
+            sh.rows.append((st.head_idx, dh))
             d_tails.append(dt.reshape(n, st.ppp, W))
         # gradients of the scores I computed ([n(j), S, Nl]) and of my tail rows (C5'), one all-to-all
         d_sc_all, d_tail_back = self._paired_all_to_all(d_scores, d_tails)
-        deferred: List[Tuple[torch.Tensor, _NegGroup, torch.Tensor]] = []
         d_tq, d_hq = [], []
-        for st, dsc, dtb, upd in zip(steps, d_sc_all, d_tail_back, local_updates):
-            ppp, cut = st.ppp, st.ppp // 2
+        for sh, dsc, dtb in zip(shards, d_sc_all, d_tail_back):
+            st, upd = sh.step, sh.rows
             upd.append((st.local_tail.reshape(-1), dtb.reshape(-1, W)))
-            if len(st.groups) == 1:
-                d_outs = [dsc.reshape(n * n * ppp, -1)]
-            else:
-                d4 = dsc.reshape(n, n, ppp, -1)
-                d_outs = [d4[:, :, :cut].reshape(n * n * cut, -1).contiguous(),
-                          d4[:, :, cut:].reshape(n * n * (ppp - cut), -1).contiguous()]
+            d_outs = [dsc.reshape(n * n * st.ppp, -1)] if len(st.groups) == 1 else _split_ht(dsc, st.ppp)
             for g, go in zip(st.groups, d_outs):
                 norm = None
                 if g.partials is not None:  # the last two columns are the softmax normalisation
@@ -1821,12 +1813,14 @@ class ScoreMovingBessKGE(BessKGE):
                 if g.shared:
                     dq, dn = nat.neg_score_shared_bwd(desc, g.query, g.neg, g.out, go)
                     upd.append((g.neg.idx, dn))
-                elif norm is not None:
-                    dq = nat.combine_dq_partials(g.partials, norm)
-                    deferred.append((st.table, g, go))
-                elif fn.supports_fused_segments:
-                    dq, _ = nat.neg_score_pertriple_bwd(desc, g.query, g.neg, g.n_per_query, go, want_d_neg=False)
-                    deferred.append((st.table, g, go))
+                elif self._wants_segments(g, st):
+                    # (every group here has its negatives in `RowSource(st.table, ...)` and is scored by this shard
+                    # alone: the test comes down to `fn.supports_fused_segments`, which the partials need too)
+                    if norm is not None:
+                        dq = nat.combine_dq_partials(g.partials, norm)
+                    else:
+                        dq, _ = nat.neg_score_pertriple_bwd(desc, g.query, g.neg, g.n_per_query, go, want_d_neg=False)
+                    sh.segments.append((g, go))
                 else:
                     dq, dn = nat.neg_score_pertriple_bwd(desc, g.query, g.neg, g.n_per_query, go)
                     upd.append((g.neg.idx, dn))
@@ -1841,7 +1835,8 @@ class ScoreMovingBessKGE(BessKGE):
             return [x.sum(dim=0) for x in group.all_to_all(parts)] if parts else []
 
         back_tq, back_hq = to_owner(d_tq), to_owner(d_hq)
-        for i, (st, upd) in enumerate(zip(steps, local_updates)):
+        for i, sh in enumerate(shards):
+            st, upd = sh.step, sh.rows
             cut = st.ppp // 2
             head2d, tail2d = st.sm_head, st.local_tail
             if scheme == "h":
@@ -1851,10 +1846,7 @@ class ScoreMovingBessKGE(BessKGE):
             else:
                 upd.append((tail2d[:, :cut].reshape(-1).contiguous(), back_tq[i].reshape(-1, W)))
                 upd.append((head2d[:, cut:].reshape(-1).contiguous(), back_hq[i].reshape(-1, W)))
-        if pending is not None:
-            pending.append(_PendingUpdate(steps, local_updates, deferred, d_rel))
-        else:
-            self._apply_updates(steps, local_updates, deferred, seg_index, optimizer, desc, d_rel, ctx.small_ahead)
+        self._hand_over(shards, d_rel, optimizer, desc, pending)
         return results
 
 

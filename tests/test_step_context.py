@@ -34,10 +34,38 @@ GOLDEN_CASES = [
     "tr_SM_ht_flat_n2",          # no partials
 ]
 C4, ONE_SHARD = "c4_notebook", "one_shard_complex"
+ONE_SHARD_HT, ONE_SHARD_F16 = ONE_SHARD + "_ht", ONE_SHARD + "_f16"
+SYNTHETIC = (C4, ONE_SHARD, ONE_SHARD_HT, ONE_SHARD_F16)
+# the routes of the shard update that the cases above leave out
+ROUTE_CASES = [
+    "tr_EM_ComplEx0_h_pt_n1",    # the "h" side
+    "tr_EM_InterHT1_h_pt_n1",    # affine: segments that are no native scorer's - padded into one more row list
+    "tr_EM_InterHT1_ht_pt_n2",   # ... two groups per shard
+    "tr_EM_BoxE1_h_pt_n1",
+    "tr_EM_ConvE0_t_flat_n1",    # the scorer's dense parameters
+    "tr_EM_loc_aug_ht_flat_n4",  # augmentation, the planned concatenation, four shards
+    ONE_SHARD_HT,                # two deferred groups on one fp32 table
+]
+COALESCE_FROM = 16  # `coalesce_sgd_from` of the "sgdcoalesce" configuration: below every update list of its case
+OPTIMISERS = {
+    "sgd": lambda rt: rt.SGD(lr=0.05),
+    "adam": lambda rt: rt.Adam(lr=0.01),
+    "adagrad": lambda rt: rt.Adagrad(lr=0.05),
+    "sgdmomentum": lambda rt: rt.SGD(lr=0.05, momentum=0.9),
+    "adampaged": lambda rt: rt.Adam(lr=0.01, state_rows=1024),  # (fewer than ONE_SHARD's 3000 rows)
+    "sgddense": lambda rt: rt.SGD(lr=0.05, dense=True),
+    "adamdense": lambda rt: rt.Adam(lr=0.01, dense=True),
+    "sgdcoalesce": lambda rt: rt.SGD(lr=0.05),  # plain SGD's long-list coalescing (COALESCE_FROM)
+}
 # (case, optimiser, micro-batches per update, reduction)
 CONFIGS = [(case, opt, 1, "sum") for case in GOLDEN_CASES + [C4, ONE_SHARD] for opt in ("sgd", "adam")]
 CONFIGS += [(case, opt, 2, red) for case in (GOLDEN_CASES[0], GOLDEN_CASES[3], ONE_SHARD) for opt in ("sgd", "adam")
             for red in ("sum", "mean")]
+CONFIGS += [(case, opt, 1, "sum") for case in ROUTE_CASES for opt in ("sgd", "adam")]
+CONFIGS += [(ONE_SHARD, opt, 1, "sum") for opt in ("adagrad", "sgdmomentum", "adampaged", "sgddense", "adamdense")]
+CONFIGS += [(C4, "sgddense", 1, "sum"), (C4, "adamdense", 1, "sum"),
+            (ONE_SHARD_F16, "sgd", 1, "sum"),  # plain SGD on an f16 shard coalesces
+            (GOLDEN_CASES[0], "sgdcoalesce", 1, "sum")]
 
 
 def config_id(cfg):
@@ -46,7 +74,7 @@ def config_id(cfg):
 
 
 def _synthetic(case, dev, micro):
-    """(model, batch of `micro` micro-batches) of the two one-shard shapes that are no golden case."""
+    """(model, batch of `micro` micro-batches) of the one-shard shapes that are no golden case."""
     from besskge.bess import EmbeddingMovingBessKGE
     from besskge.loss import LogSigmoidLoss, SampledSoftmaxCrossEntropyLoss
     from besskge.negative_sampler import RandomShardedNegativeSampler
@@ -67,11 +95,14 @@ def _synthetic(case, dev, micro):
         neg_shape = (micro, 1, 1, K)
     else:
         # `test_small_step.py::test_training_step_through_the_pertriple_tail_equals_the_separate_launches`, fp32
-        # ComplEx: per-triple negatives of the own shard (`pertriple_tail`, segmented update)
+        # ComplEx: per-triple negatives of the own shard (`pertriple_tail`, segmented update).  Its "ht" variant has
+        # two such groups on the one table, its f16 variant a shard on which plain SGD coalesces
         S, K, M, n_rel = 192, 64, 3000, 9
         sharding = Sharding.create(M, 1, seed=0)
-        fn = ComplEx(False, sharding, n_rel, 32, device=dev, dtype=torch.float32)
-        ns = RandomShardedNegativeSampler(K, sharding, 0, "t", local_sampling=False, flat_negative_format=False)
+        fn = ComplEx(False, sharding, n_rel, 32, device=dev,
+                     dtype=torch.float16 if case == ONE_SHARD_F16 else torch.float32)
+        ns = RandomShardedNegativeSampler(K, sharding, 0, "ht" if case == ONE_SHARD_HT else "t", local_sampling=False,
+                                          flat_negative_format=False)
         model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn,
                                        loss_fn=LogSigmoidLoss(margin=4.0, negative_adversarial_sampling=True))
         neg_shape = (micro, 1, S, K)
@@ -86,14 +117,16 @@ def build(cfg, dev):
     from test_hip_parity import build_model
 
     case, opt_name, accum, red = cfg
-    if case in (C4, ONE_SHARD):
+    if case in SYNTHETIC:
         model, batch = _synthetic(case, dev, accum)
     else:
         c = load_bess_case(case)
         model = build_model(c, dev)
         batch = {k: torch.stack([c["batch"][k][it] for it in range(accum)]).flatten(end_dim=1)
                  for k in KEYS if k in c["batch"]}
-    opt = runtime.SGD(lr=0.05) if opt_name == "sgd" else runtime.Adam(lr=0.01)
+    opt = OPTIMISERS[opt_name](runtime)
+    if opt_name == "sgdcoalesce":
+        model.coalesce_sgd_from = COALESCE_FROM
     options = runtime.Options(device_iterations=1, gradient_accumulation=accum, accumulation_reduction=red)
     return model, runtime.training_model(model, options, opt, device=dev), batch
 
@@ -135,12 +168,14 @@ def recorded():
 def test_step_issues_the_recorded_calls_in_the_recorded_order(dev, recorded, cfg):
     """Same launches in the same order as the parent commit; and, where the parent's update is reproducible, the same
     bits from two fresh models.  `recorded["bit_identical"]` names those configurations: the ones whose tables were
-    equal between three fresh models in every run of the parent (two runs).  At the parent NONE of the configurations
-    above was, so the list is empty and the bit-for-bit assertion is dropped for all of them: every step sums the relation gradient - a few relations, many
-    triples each - with fp32 atomics, whose order is not fixed; plain SGD on an fp32 shard adds every row
-    contribution with an atomic too, the direct update adds gradient rows into its accumulator with atomics, and
-    on two shards the gradients of the rows that came through the all-to-all are summed into the receive layout
-    with atomics whatever the optimiser."""
+    equal between three fresh models in every run of the parent (five runs of the writer; the file holds the lists
+    of the first and the configurations that every run named - a single run names a few more, another few each
+    time).  They are four: Adam on the 16-triple one-shard cases of InterHT, BoxE and ConvE, and plain SGD on the f16
+    copy of the one-shard ComplEx step.  For all others the bit-for-bit assertion is dropped: every step sums the
+    relation gradient - a few relations, many triples each - with fp32 atomics, whose order is not fixed; plain SGD
+    on an fp32 shard adds every row contribution with an atomic too, the direct update and the dense step add
+    gradient rows into their accumulator with atomics, and on two shards the gradients of the rows that came
+    through the all-to-all are summed into the receive layout with atomics whatever the optimiser."""
     key = config_id(cfg)
     names, ent, rel = two_updates(cfg, dev)
     want = recorded["calls"][key]
