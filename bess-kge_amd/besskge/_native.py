@@ -35,7 +35,8 @@ _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _RETURNS_I64 = ("bess_neg_score_shared_workspace", "bess_neg_score_shared_bwd_workspace",
                 "bess_neg_score_shared_fwd_counts_workspace", "bess_neg_score_shared_fwd_pairs_workspace",
-                "bess_neg_score_table_fwd_counts_workspace", "bess_neg_score_table_fwd_pairs_workspace")  # every other entry returns an int status
+                "bess_neg_score_table_fwd_counts_workspace", "bess_neg_score_table_fwd_pairs_workspace",
+                "bess_neg_score_shared_fwd_lse_workspace", "bess_neg_score_shared_bwd_softmax_workspace")  # every other entry returns an int status
 _i32 = ctypes.c_int32
 _f32 = ctypes.c_float
 
@@ -146,6 +147,10 @@ SIGNATURES = {
     "bess_neg_score_shared_fwd_counts": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
     "bess_neg_score_shared_fwd_pairs_workspace": [_MD, _i64, _i64],
     "bess_neg_score_shared_fwd_pairs": [_MD, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
+    "bess_neg_score_shared_fwd_lse_workspace": [_MD, _i64, _i64],
+    "bess_neg_score_shared_fwd_lse": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
+    "bess_neg_score_shared_bwd_softmax_workspace": [_MD, _i64, _i64],
+    "bess_neg_score_shared_bwd_softmax": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "bess_neg_score_table_fwd_counts_workspace": [_MD, _i64, _i64],
     "bess_neg_score_table_fwd_counts": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
     "bess_neg_score_table_fwd_pairs_workspace": [_MD, _i64, _i64],
@@ -1108,6 +1113,86 @@ def neg_score_shared_counts(d: ModelDesc, query: torch.Tensor, neg: RowSource, t
             _idx(neg.idx, "negative idx"), n_neg, thr.data_ptr(), excl.data_ptr(), counts.data_ptr(),
             int(bool(round_f16)), _ptr(ws), ws_bytes)
     return counts
+
+
+def _sized_workspace(query: str, d: ModelDesc, nq: int, n_neg: int, dev: torch.device,
+                     workspace_bytes: Optional[int]) -> Tuple[Optional[torch.Tensor], int]:
+    """`_workspace`, or a scratch of `workspace_bytes` when the caller sets the size (the tile width of the
+    softmax passes follows from it)."""
+    if workspace_bytes is None:
+        return _workspace(query, d, nq, n_neg, dev)
+    ws_bytes = int(workspace_bytes)
+    return (torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None), ws_bytes
+
+
+def neg_score_shared_lse(d: ModelDesc, query: torch.Tensor, neg: RowSource, state_ml: Optional[torch.Tensor] = None,
+                         workspace_bytes: Optional[int] = None) -> torch.Tensor:
+    """Softmax normaliser over all candidates without the score matrix (`bess_neg_score_shared_fwd_lse`): merges
+    the scores of every query against `neg` into `state_ml` [nq, 2] f32 = (running max m, running sum l of
+    exp(score - m)) - made empty, (-inf, 0), when None - and returns it; log-sum-exp = m + log(l).  Several calls
+    accumulate.  `workspace_bytes`: scratch size instead of the library's default (the score tile of the shapes
+    without a fused epilogue is as wide as it allows, whole multiples of 64 columns).  An operand outside the fp16
+    range of the matrix-core product (the library answers NaN states): the call is repeated in fp32 arithmetic on
+    the state as it was (one host read of a flag, on the matrix-core path only)."""
+    nq, n_neg = int(query.shape[0]), len(neg)
+    dev = _neg_operands(d, query, neg, n_neg)
+    if int(d.scorer) > COMPLEX:
+        raise ValueError("neg_score_shared_lse: TransE / RotatE / DistMult / ComplEx only")
+    if state_ml is None:
+        state_ml = torch.empty((nq, 2), dtype=torch.float32, device=dev)
+        state_ml[:, 0] = float("-inf")
+        state_ml[:, 1] = 0.0
+    else:
+        _same_device([("state_ml", state_ml), ("query", query)])
+        if tuple(state_ml.shape) != (nq, 2) or state_ml.dtype != torch.float32 or not state_ml.is_contiguous():
+            raise ValueError("neg_score_shared_lse: state_ml must be a contiguous [nq, 2] float32 tensor")
+    if nq == 0 or n_neg == 0:
+        return state_ml
+
+    def run(desc: ModelDesc, ws_bytes: Optional[int]) -> None:
+        ws, nbytes = _sized_workspace("bess_neg_score_shared_fwd_lse_workspace", desc, nq, n_neg, dev, ws_bytes)
+        _launch("bess_neg_score_shared_fwd_lse", dev, ctypes.byref(desc), query.data_ptr(), nq, neg.base.data_ptr(),
+                _idx(neg.idx, "negative idx"), n_neg, state_ml.data_ptr(), _ptr(ws), nbytes)
+
+    # (the matrix-core path is the only one that can answer NaN for finite operands)
+    fused = int(load().bess_neg_score_shared_workspace(ctypes.byref(d), nq, n_neg)) > 0
+    before = state_ml.clone() if fused else None
+    run(d, workspace_bytes)
+    if fused and bool(torch.isnan(state_ml).any()) and not bool(torch.isnan(before).any()):
+        state_ml.copy_(before)
+        exact = copy_desc(d)
+        exact.reserved[0] |= FLAG_FP32_MATH
+        run(exact, None)
+    return state_ml
+
+
+def neg_score_shared_bwd_softmax(d: ModelDesc, query: torch.Tensor, neg: RowSource, lse: torch.Tensor,
+                                 coef: torch.Tensor, d_query: Optional[torch.Tensor] = None,
+                                 workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Backward of a softmax over all candidates without the score matrix (`bess_neg_score_shared_bwd_softmax`):
+    with P[q, j] = coef[q] * exp(score(q, j) - lse[q]), returns (d_query [nq, W] with sum_j P dscore/dquery ADDED
+    to what it held - zeros when None -, d_neg [n_neg, W] = sum_q P dscore/dcandidate in candidate order)."""
+    nq, n_neg = int(query.shape[0]), len(neg)
+    dev = _neg_operands(d, query, neg, n_neg)
+    if int(d.scorer) > COMPLEX:
+        raise ValueError("neg_score_shared_bwd_softmax: TransE / RotatE / DistMult / ComplEx only")
+    _same_device([("lse", lse), ("coef", coef), ("d_query", d_query), ("query", query)])
+    _f32s(("lse", lse), ("coef", coef))
+    if lse.numel() != nq or coef.numel() != nq or not lse.is_contiguous() or not coef.is_contiguous():
+        raise ValueError("neg_score_shared_bwd_softmax: one contiguous lse and coef per query")
+    W = int(d.width)
+    if d_query is None:
+        d_query = torch.zeros((nq, W), dtype=torch.float32, device=dev)
+    elif tuple(d_query.shape) != (nq, W) or d_query.dtype != torch.float32 or not d_query.is_contiguous():
+        raise ValueError("neg_score_shared_bwd_softmax: d_query must be a contiguous [nq, W] float32 tensor")
+    d_neg = torch.empty((n_neg, W), dtype=torch.float32, device=dev)
+    if nq == 0 or n_neg == 0:
+        return d_query, d_neg.zero_()
+    ws, ws_bytes = _sized_workspace("bess_neg_score_shared_bwd_softmax_workspace", d, nq, n_neg, dev, workspace_bytes)
+    _launch("bess_neg_score_shared_bwd_softmax", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n_neg, lse.data_ptr(), coef.data_ptr(), d_query.data_ptr(),
+            d_neg.data_ptr(), _ptr(ws), ws_bytes)
+    return d_query, d_neg
 
 
 def shared_bwd_buffer(d: ModelDesc, nq: int, n_neg: int, device: torch.device) -> Optional[torch.Tensor]:

@@ -52,7 +52,16 @@ struct CountArgs {
     int32_t* counts;
     int64_t col0;
     int round16;
+    // log-sum-exp epilogue instead (bess_neg_score_shared_fwd_lse; nothing is counted): the (max, sum of exp(s - max))
+    // of row `r` over the 64 columns of wave tile `c` of the launch goes to lse_part[(c * rows + r) * 2]
+    float* lse_part;
 };
+// (m, l) <- (m, l) merged with (m2, l2): states of a running log-sum-exp, (-inf, 0) the empty one
+__device__ __forceinline__ void lse_merge(float& m, float& l, float m2, float l2) {
+    const float mm = fmaxf(m, m2);
+    l = mm == -INFINITY ? 0.f : l * __expf(m - mm) + l2 * __expf(m2 - mm);
+    m = mm;
+}
 __device__ __forceinline__ float count_value(float v, int round16) {
     return round16 ? static_cast<float>(static_cast<_Float16>(v)) : v;
 }
@@ -65,7 +74,10 @@ int64_t gemm_split_workspace_any(int64_t S, int64_t N, int W);  // (bytes for a 
 int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const int32_t* idx, int64_t N, int W,
                    float* out, int64_t ld, void* ws, int64_t ws_bytes, hipStream_t st, const float* thr = nullptr,
                    uint8_t* flags = nullptr, int64_t ld_flags = 0, const CountArgs* count = nullptr,
-                   bool diag = false);  // diag: S == N, out [S, 128] receives the diagonal 128 x 128 tiles only
+                   bool diag = false,  // diag: S == N, out [S, 128] receives the diagonal 128 x 128 tiles only
+                   float* lse_state = nullptr);  // [S, 2]: merge every row's log-sum-exp in (the front of ws holds
+                                                 // gemm_split_lse_parts bytes of tile partials; nothing is stored)
+int64_t gemm_split_lse_parts(int64_t S, int64_t N);
 int64_t gemm_split_bwd_workspace(int64_t S, int64_t N, int W);
 int gemm_split_bwd(int dtype, const float* G, int64_t ldg, int64_t S, const float* Q, const void* E,
                    const int32_t* idx, int64_t N, int W, float* dQ, float* dE, void* ws, int64_t ws_bytes,

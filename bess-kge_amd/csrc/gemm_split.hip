@@ -47,7 +47,7 @@
 //               forward products whose tiles fill the chip.
 // The two GEMM kernels share what a wave does with its 64 x 64: WaveTile (the accumulators, the lane's fragment
 // offsets, the fragment reads and the MFMA group of a k step) and wave_tile_epilogue<EPI> (stores / pruned stores /
-// counts) exist once.  A kernel owns its tile shape, the way slices reach LDS, and how it interleaves reads and
+// counts / log-sum-exp) exist once.  A kernel owns its tile shape, the way slices reach LDS, and how it interleaves reads and
 // MFMAs.  launch_product picks the instantiation from one [B_LO][EPI] table per kernel.
 #include "common.h"
 
@@ -345,12 +345,37 @@ __device__ __forceinline__ void interleave_reads() {
 // A finished wave tile (rows m0 .., columns n0 .. of the M x N product): main + corr / 2048 -> C, where c0 points at
 // this lane's first element.  C/D layout of the 32x32 MFMA: col = lane & 31 (l31),
 // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (lk).
-template <int EPI>  // 0 stores, 1 pruned stores (top-k passes), 2 counts (ranks; nothing is stored)
+template <int EPI>  // 0 stores, 1 pruned stores (top-k passes), 2 counts (ranks; nothing is stored), 3 log-sum-exp
 __device__ __forceinline__ void wave_tile_epilogue(const f32x16 (&accm)[2][2], const f32x16 (&accc)[2][2], int64_t m0,
                                                    int64_t n0, float* __restrict__ c0, int64_t ldc, int64_t M, int64_t N,
                                                    const float* __restrict__ thr, uint8_t* __restrict__ pflags,
                                                    int64_t ldf, const CountArgs& cnt, int l31, int lk) {
-    if constexpr (EPI == 2) {
+    if constexpr (EPI == 3) {
+        // log-sum-exp epilogue (1vsAll training): nothing is stored but one (max, sum of exp(s - max)) per row of
+        // the wave tile.  A row's 64 scores sit in the 32 lanes of one lk (two each): max and sum are butterflies
+        // over those 32 lanes (offsets 1 .. 16 never cross the halves), so every step serves two rows - rr in the
+        // low half, rr + 4 in the high one.  The first lane of each half stores its row's pair with a plain 8-B
+        // store into slab n0 / 64 of the launch's partials (merged in a fixed order by k_lse_merge_parts): no
+        // atomics, bitwise reproducible.  Columns past N count as -inf.
+        const bool ok0 = n0 + l31 < N, ok1 = n0 + l31 + 32 < N;
+        float* __restrict__ slab = cnt.lse_part + ((n0 / 64) * M + m0 + 4 * lk) * 2;
+        const bool writer = l31 == 0 && n0 < N;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
+                const float v0 = ok0 ? accm[i][0][r] + accc[i][0][r] * (1.f / 2048.f) : -INFINITY;
+                const float v1 = ok1 ? accm[i][1][r] + accc[i][1][r] * (1.f / 2048.f) : -INFINITY;
+                float m = fmaxf(v0, v1);
+#pragma unroll
+                for (int o = 1; o < 32; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+                float l = m == -INFINITY ? 0.f : __expf(v0 - m) + __expf(v1 - m);
+#pragma unroll
+                for (int o = 1; o < 32; o <<= 1) l += __shfl_xor(l, o, 64);
+                if (writer && m0 + 4 * lk + rr < M) *reinterpret_cast<float2*>(slab + rr * 2) = make_float2(m, l);
+            }
+    } else if constexpr (EPI == 2) {
         // counting epilogue (ranks): nothing is stored.  Lane l of the wave keeps the two counts of row
         // m0 + l: a row's 64 scores sit in the 32 lanes of one lk, so one ballot per comparison holds two
         // rows' verdicts (low half: row rr, high half: rr + 4), counted with s_bcnt1 and kept by the
@@ -667,12 +692,12 @@ __global__ __launch_bounds__(512) void k_gemm_split_w8(const char* __restrict__ 
 // the instantiations of the two kernels, [B_LO][EPI]
 using SplitKernel = void (*)(const char*, const char*, int64_t, int64_t, int, float*, int64_t, int, int, int, int64_t,
                              const int32_t*, const float*, uint8_t*, int64_t, CountArgs);
-static const SplitKernel SPLIT_F16[2][3] = {
-    {k_gemm_split_f16<false, 0>, k_gemm_split_f16<false, 1>, k_gemm_split_f16<false, 2>},
-    {k_gemm_split_f16<true, 0>, k_gemm_split_f16<true, 1>, k_gemm_split_f16<true, 2>}};
-static const SplitKernel SPLIT_W8[2][3] = {
-    {k_gemm_split_w8<false, 0>, k_gemm_split_w8<false, 1>, k_gemm_split_w8<false, 2>},
-    {k_gemm_split_w8<true, 0>, k_gemm_split_w8<true, 1>, k_gemm_split_w8<true, 2>}};
+static const SplitKernel SPLIT_F16[2][4] = {
+    {k_gemm_split_f16<false, 0>, k_gemm_split_f16<false, 1>, k_gemm_split_f16<false, 2>, k_gemm_split_f16<false, 3>},
+    {k_gemm_split_f16<true, 0>, k_gemm_split_f16<true, 1>, k_gemm_split_f16<true, 2>, k_gemm_split_f16<true, 3>}};
+static const SplitKernel SPLIT_W8[2][4] = {
+    {k_gemm_split_w8<false, 0>, k_gemm_split_w8<false, 1>, k_gemm_split_w8<false, 2>, k_gemm_split_w8<false, 3>},
+    {k_gemm_split_w8<true, 0>, k_gemm_split_w8<true, 1>, k_gemm_split_w8<true, 2>, k_gemm_split_w8<true, 3>}};
 
 static int n_compute_units() {
     static const int n = [] {
@@ -697,14 +722,15 @@ static int launch_product(const char* A, const char* B, int64_t M, int64_t N, in
                           const CountArgs* count = nullptr, bool diag = false) {
     BESS_REQUIRE(!thr || (ksplit == 1 && (pflags || count)),
                  "gemm_split: pruned stores / counts need an unsplit product and a flag or count array");
-    const CountArgs cnt = count ? *count : CountArgs{nullptr, nullptr, 0, 0};
-    const int epi = count ? 2 : (thr ? 1 : 0);
+    BESS_REQUIRE(!count || ksplit == 1, "gemm_split: the reduction epilogues need an unsplit product");
+    const CountArgs cnt = count ? *count : CountArgs{nullptr, nullptr, 0, 0, nullptr};
+    const int epi = count ? (count->lse_part ? 3 : 2) : (thr ? 1 : 0);
     const int cus = n_compute_units();
     const int64_t tx = ceil_div(N, 128);
     const int64_t t8 = tx * ceil_div(M, W8_A) * ksplit, t4 = tx * ceil_div(M, 128) * ksplit;
     BESS_REQUIRE(t4 < (1ll << 31), "gemm_split: too many tiles");
     // one launch form: `tiles` tiles of kernel k[b_lo][epi], one persistent workgroup per CU at most
-    auto launch = [&](const SplitKernel (&k)[2][3], int64_t tiles, int lds_bytes, int64_t tiles_x, const char* what) {
+    auto launch = [&](const SplitKernel (&k)[2][4], int64_t tiles, int lds_bytes, int64_t tiles_x, const char* what) {
         const int grid = static_cast<int>(tiles < cus ? tiles : cus);
         k[b_lo][epi]<<<grid, 512, lds_bytes, st>>>(A, B, M, N, n_slice, C, ldc, static_cast<int>(tiles_x),
                                                    static_cast<int>(tiles), ksplit, part_stride, flag, thr, pflags, ldf, cnt);
@@ -767,6 +793,43 @@ static int split_rows(const SplitSrc& a, char* dst_a, int dtype_b, const SplitSr
     return check_launch("split_rows");
 }
 
+// Tile partials of the log-sum-exp epilogue -> state [rows, 2]: one wave per row.  Lane l merges slabs l, l + 64, ..
+// in order, the 64 lanes meet in a butterfly, the result is merged into the row's state: a fixed order throughout.
+// An operand outside the fp16 range (the flag is up, the product kernels returned at once): the state becomes NaN.
+__global__ __launch_bounds__(256) void k_lse_merge_parts(const float* __restrict__ part, int64_t rows, int n_slab,
+                                                         const int32_t* __restrict__ flag, float* __restrict__ state) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    if (*flag) {
+        if (lane < 2) state[2 * r + lane] = __builtin_nanf("");
+        return;
+    }
+    float m = -INFINITY, l = 0.f;
+    for (int c = lane; c < n_slab; c += 64) {
+        const float2 p = *reinterpret_cast<const float2*>(part + (static_cast<int64_t>(c) * rows + r) * 2);
+        lse_merge(m, l, p.x, p.y);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float m2 = __shfl_xor(m, o, 64), l2 = __shfl_xor(l, o, 64);
+        lse_merge(m, l, m2, l2);
+    }
+    if (lane == 0) {
+        float ms = state[2 * r], ls = state[2 * r + 1];
+        if (ms == ms && ls == ls) {  // (a state an earlier call poisoned stays NaN)
+            lse_merge(ms, ls, m, l);
+            *reinterpret_cast<float2*>(state + 2 * r) = make_float2(ms, ls);
+        }
+    }
+}
+
+// bytes of tile partials in front of the workspace of a log-sum-exp pass: one (m, l) per row and 64 candidates of a
+// chunk - chunks are at most SPLIT_CHUNK rows, so the size does not depend on N beyond that
+int64_t gemm_split_lse_parts(int64_t S, int64_t N) {
+    return pad_b(N < SPLIT_CHUNK ? N : SPLIT_CHUNK) / 64 * S * 8;
+}
+
 __global__ void k_poison_counts(const int32_t* __restrict__ flag, int32_t* __restrict__ counts, int64_t n) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (*flag && i < n) counts[i] = INT32_MIN;
@@ -775,8 +838,17 @@ __global__ void k_poison_counts(const int32_t* __restrict__ flag, int32_t* __res
 // out[q, j] = Q[q] . E[idx[j]] through the workspace (>= gemm_split_workspace bytes, 16-B aligned)
 int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const int32_t* idx, int64_t N, int W,
                    float* out, int64_t ld, void* ws, int64_t ws_bytes, hipStream_t st, const float* thr,
-                   uint8_t* pflags, int64_t ldf, const CountArgs* count, bool diag) {
+                   uint8_t* pflags, int64_t ldf, const CountArgs* count, bool diag, float* lse_state) {
     const int64_t pitch = split_pitch(W);
+    float* lse_part = nullptr;
+    if (lse_state) {
+        BESS_REQUIRE(!diag && !thr && !count && !out, "gemm_split: the log-sum-exp pass stores nothing else");
+        const int64_t pb = gemm_split_lse_parts(S, N);
+        BESS_REQUIRE(ws_bytes > pb, "gemm_split: workspace too small");
+        lse_part = static_cast<float*>(ws);
+        ws = static_cast<char*>(ws) + pb;
+        ws_bytes -= pb;
+    }
     BESS_REQUIRE(!diag || (S == N && idx && !thr && !count && ld == 128), "gemm_split: bad diagonal product");
     BESS_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0, "gemm_split: workspace must be 16-B aligned");
     BESS_REQUIRE(ws_bytes >= FLAG_BYTES + 256 * pitch, "gemm_split: workspace too small");
@@ -788,6 +860,7 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
     }
     int64_t chunk = (ws_bytes / pitch - pad_a(S)) / 128 * 128;  // candidate rows per pass
     BESS_REQUIRE(chunk >= 128, "gemm_split: workspace too small");
+    if (lse_state && chunk > SPLIT_CHUNK) chunk = SPLIT_CHUNK;  // (what the partials in front of the workspace cover)
     if (chunk >= N) chunk = N;
     char* qa = static_cast<char*>(ws);
     char* eb = qa + pad_a(S) * pitch;
@@ -800,14 +873,20 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
         // the query rows ride along with the first chunk
         if (int e = split_rows(SplitSrc{Q, nullptr, j0 == 0 ? S : 0, W, flag}, qa, dtype, src, eb, W, st)) return e;
         // (pruned stores: the chunk's flags start at block j0 / 64 - chunks are multiples of 128 rows)
-        CountArgs cj{nullptr, nullptr, 0, 0};
-        if (count) cj = CountArgs{count->excl, count->counts, count->col0 + j0, count->round16};
+        CountArgs cj{nullptr, nullptr, 0, 0, lse_part};
+        if (count) cj = CountArgs{count->excl, count->counts, count->col0 + j0, count->round16, nullptr};
         BESS_REQUIRE(!diag || nc == N, "gemm_split: the diagonal product wants its operands in one pass");
-        if (int e = launch_product(qa, eb, S, nc, n_slice, count ? nullptr : out + (diag ? 0 : j0), ld, 1, 0,
+        if (int e = launch_product(qa, eb, S, nc, n_slice, (count || lse_state) ? nullptr : out + (diag ? 0 : j0), ld, 1, 0,
                                    dtype == BESS_F32, true, flag, st, thr, pflags ? pflags + j0 / 64 : nullptr, ldf,
-                                   count ? &cj : nullptr, diag))
+                                   (count || lse_state) ? &cj : nullptr, diag))
             return e;
+        if (lse_state) {  // (the partials are rewritten by the next chunk: merged per chunk, in chunk order)
+            k_lse_merge_parts<<<static_cast<unsigned>(ceil_div(S, 4)), 256, 0, st>>>(
+                lse_part, S, static_cast<int>(ceil_div(nc, 64)), flag, lse_state);
+            if (int e = check_launch("lse_merge_parts")) return e;
+        }
     }
+    if (lse_state) return BESS_OK;  // (an operand outside the fp16 range: every state of the call is NaN)
     if (count) {
         // (no score matrix for the fp32 kernels to fill) an operand outside the fp16 range: every count becomes
         // negative - the caller sees it where it reads the counts and scores that batch through the matrix

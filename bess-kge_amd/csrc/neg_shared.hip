@@ -1011,6 +1011,7 @@ __global__ __launch_bounds__(256) void k_count_scores(const float* __restrict__ 
     }
 }
 
+static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 constexpr int64_t COUNT_TILE_BYTES = 64ll << 20;  // score tile of the scorers without a counting epilogue
 static int64_t count_tile_cols(int64_t n_query, int64_t n_neg) {
     int64_t c = COUNT_TILE_BYTES / 4 / n_query / 64 * 64;
@@ -1090,6 +1091,185 @@ extern "C" int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const 
     });
 }
 
+// ---- softmax over all candidates without the score matrix (1vsAll training) -------------------------------------
+// Forward: every row's running (max m, sum l of exp(score - m)) over the candidates of the call, merged into
+// state_ml [n_query, 2]; backward: the products of the softmax coefficients with the operands, candidates in chunks.
+// Neither writes more than a bounded tile of scores.
+
+// folds a stored score tile into the rows' states: one wave per row, as k_count_scores
+__global__ __launch_bounds__(256) void k_lse_scores(const float* __restrict__ sc, int64_t ld, int64_t n_row,
+                                                    int64_t n_col, float* __restrict__ state) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (r >= n_row) return;
+    const float* row = sc + r * ld;
+    float m = -INFINITY;
+    for (int64_t j = lane; j < n_col; j += 64) m = fmaxf(m, row[j]);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    float l = 0.f;
+    if (m != -INFINITY)
+        for (int64_t j = lane; j < n_col; j += 64) l += __expf(row[j] - m);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) l += __shfl_xor(l, o, 64);
+    if (lane == 0) {
+        float ms = state[2 * r], ls = state[2 * r + 1];
+        if (ms == ms && ls == ls) {  // (a state an earlier call poisoned stays NaN)
+            lse_merge(ms, ls, m, l);
+            state[2 * r] = ms;
+            state[2 * r + 1] = ls;
+        }
+    }
+}
+
+// P[q, j] = coef[q] * exp(score[q, j] - lse[q]); a zero coefficient gives exact zeros whatever the row's lse
+__global__ __launch_bounds__(256) void k_softmax_coef(const float* __restrict__ sc, float* __restrict__ P, int64_t ld,
+                                                      int64_t n_row, int64_t n_col, const float* __restrict__ lse,
+                                                      const float* __restrict__ coef) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (r >= n_row) return;
+    const float c = coef[r], z = lse[r];
+    const float* row = sc + r * ld;
+    float* prow = P + r * ld;
+    for (int64_t j = lane; j < n_col; j += 64) prow[j] = c == 0.f ? 0.f : c * __expf(row[j] - z);
+}
+
+__global__ __launch_bounds__(256) void k_add_into(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i < n) dst[i] += src[i];
+}
+
+// columns of a score tile in `bytes` of workspace: whole multiples of 64, no more than the candidates need; 0: too few
+static int64_t softmax_tile_cols(int64_t bytes, int64_t tiles, int64_t n_query, int64_t n_neg) {
+    int64_t c = bytes / (4 * tiles * n_query) / 64 * 64;
+    const int64_t need = ceil_div(n_neg, 64) * 64;
+    return c < need ? c : need;
+}
+static int64_t softmax_default_cols(int64_t n_query, int64_t n_neg) {
+    int64_t c = COUNT_TILE_BYTES / 4 / n_query / 64 * 64;
+    if (c < 64) c = 64;
+    const int64_t need = ceil_div(n_neg, 64) * 64;
+    return c < need ? c : need;
+}
+// the fused log-sum-exp epilogue takes the shapes the counting epilogue of the split product takes
+static int64_t lse_fused_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
+    if (reduce_of(d) != RED_DOT || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return 0;
+    const int64_t want = gemm_split_workspace(n_query, n_neg, d->width);
+    return want > 0 ? align256(gemm_split_lse_parts(n_query, n_neg)) + want : 0;
+}
+// the tile paths score in fp32 arithmetic throughout: the packed-fp16 L1 kernel rounds the query to fp16, which a
+// sum over all entities would carry into every row's normaliser
+static bess_model_desc tile_path_desc(const bess_model_desc* d) {
+    bess_model_desc t = *d;
+    t.reserved[0] &= ~BESS_FLAG_PREZEROED;
+    if (reduce_of(d) != RED_DOT) t.reserved[0] |= BESS_FLAG_FP32_MATH;
+    return t;
+}
+
+extern "C" int64_t bess_neg_score_shared_fwd_lse_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
+    if (!d || check_desc(d) || d->scorer > BESS_COMPLEX || n_query <= 0 || n_neg <= 0) return 0;
+    if (const int64_t fused = lse_fused_workspace(d, n_query, n_neg)) return fused;
+    return n_query * softmax_default_cols(n_query, n_neg) * 4;
+}
+
+extern "C" int bess_neg_score_shared_fwd_lse(const bess_model_desc* d, const float* query, int64_t n_query,
+                                             const void* neg_base, const int32_t* neg_idx, int64_t n_neg,
+                                             float* state_ml, void* workspace, int64_t workspace_bytes,
+                                             void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->scorer > BESS_COMPLEX)
+        return fail(BESS_EUNSUPPORTED, "neg_score_shared_fwd_lse: TransE / RotatE / DistMult / ComplEx only");
+    BESS_REQUIRE(n_query >= 0 && n_neg >= 0, "neg_score_shared_fwd_lse: bad sizes");
+    if (n_query == 0 || n_neg == 0) return BESS_OK;
+    BESS_REQUIRE(query && neg_base && state_ml, "neg_score_shared_fwd_lse: NULL pointer");
+    BESS_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+                 "neg_score_shared_fwd_lse: workspace missing (bess_neg_score_shared_fwd_lse_workspace) or misaligned");
+    hipStream_t st = as_stream(stream);
+    const int64_t fused = lse_fused_workspace(d, n_query, n_neg);
+    if (fused > 0 && workspace_bytes >= fused) {
+        // [tile partials | images of the split product]
+        return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, nullptr, 0, workspace,
+                              workspace_bytes, st, nullptr, nullptr, 0, nullptr, false, state_ml);
+    }
+    // no epilogue for this scorer / shape: score tiles through the workspace, folded by a second kernel
+    const int64_t cols = softmax_tile_cols(workspace_bytes, 1, n_query, n_neg);
+    BESS_REQUIRE(cols >= 64, "neg_score_shared_fwd_lse: workspace holds less than 64 columns of scores "
+                             "(bess_neg_score_shared_fwd_lse_workspace)");
+    const bess_model_desc td = tile_path_desc(d);
+    float* tile = static_cast<float*>(workspace);
+    return for_each_candidate_chunk(neg_base, neg_idx, n_neg, cols, row_bytes_of(d),
+                                    [&](int64_t, int64_t nc, const void* base, const int32_t* idx) {
+        if (int e = bess_neg_score_shared_fwd_ws(&td, query, n_query, base, idx, nc, tile, cols, nullptr, 0, stream)) return e;
+        k_lse_scores<<<static_cast<unsigned>(ceil_div(n_query, 4)), 256, 0, st>>>(tile, cols, n_query, nc, state_ml);
+        return check_launch("lse_scores");
+    });
+}
+
+// workspace of the backward: [d_query of one chunk | score tile | coefficient tile | scratch of the matrix-core products]
+static int64_t softmax_bwd_fixed(const bess_model_desc* d, int64_t n_query) {
+    return align256(n_query * static_cast<int64_t>(d->width) * 4);
+}
+static int64_t softmax_bwd_gemm_ws(const bess_model_desc* d, int64_t n_query, int64_t cols) {
+    if (reduce_of(d) != RED_DOT || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return 0;
+    const int64_t f = gemm_split_workspace(n_query, cols, d->width), b = gemm_split_bwd_workspace(n_query, cols, d->width);
+    return f > b ? f : b;
+}
+
+extern "C" int64_t bess_neg_score_shared_bwd_softmax_workspace(const bess_model_desc* d, int64_t n_query,
+                                                               int64_t n_neg) {
+    if (!d || check_desc(d) || d->scorer > BESS_COMPLEX || n_query <= 0 || n_neg <= 0) return 0;
+    const int64_t cols = softmax_default_cols(n_query, n_neg);
+    return softmax_bwd_fixed(d, n_query) + 2 * n_query * cols * 4 +
+           softmax_bwd_gemm_ws(d, n_query, cols < n_neg ? cols : n_neg);
+}
+
+extern "C" int bess_neg_score_shared_bwd_softmax(const bess_model_desc* d, const float* query, int64_t n_query,
+                                                 const void* neg_base, const int32_t* neg_idx, int64_t n_neg,
+                                                 const float* lse, const float* coef, float* d_query, float* d_neg,
+                                                 void* workspace, int64_t workspace_bytes, void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->scorer > BESS_COMPLEX)
+        return fail(BESS_EUNSUPPORTED, "neg_score_shared_bwd_softmax: TransE / RotatE / DistMult / ComplEx only");
+    BESS_REQUIRE(n_query >= 0 && n_neg >= 0, "neg_score_shared_bwd_softmax: bad sizes");
+    if (n_query == 0 || n_neg == 0) return BESS_OK;
+    BESS_REQUIRE(query && neg_base && lse && coef && d_query && d_neg, "neg_score_shared_bwd_softmax: NULL pointer");
+    BESS_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+                 "neg_score_shared_bwd_softmax: workspace missing (bess_neg_score_shared_bwd_softmax_workspace) or misaligned");
+    hipStream_t st = as_stream(stream);
+    const int W = d->width;
+    const int64_t fixed = softmax_bwd_fixed(d, n_query);
+    int64_t cols = workspace_bytes > fixed ? softmax_tile_cols(workspace_bytes - fixed, 2, n_query, n_neg) : 0;
+    BESS_REQUIRE(cols >= 64, "neg_score_shared_bwd_softmax: workspace holds less than 64 columns of scores "
+                             "(bess_neg_score_shared_bwd_softmax_workspace)");
+    // the matrix-core products take their scratch behind the tiles; tiles stop at the default width to leave it there
+    const int64_t dflt = softmax_default_cols(n_query, n_neg);
+    if (cols > dflt) cols = dflt;
+    char* ws = static_cast<char*>(workspace);
+    float* dq_chunk = reinterpret_cast<float*>(ws);
+    float* sc = reinterpret_cast<float*>(ws + fixed);
+    float* P = sc + n_query * cols;
+    void* gws = ws + fixed + 2 * n_query * cols * 4;
+    const int64_t gws_bytes = workspace_bytes - fixed - 2 * n_query * cols * 4;
+    const bess_model_desc td = tile_path_desc(d);
+    const unsigned rows4 = static_cast<unsigned>(ceil_div(n_query, 4));
+    const int64_t nqw = n_query * W;
+    return for_each_candidate_chunk(neg_base, neg_idx, n_neg, cols, row_bytes_of(d),
+                                    [&](int64_t j0, int64_t nc, const void* base, const int32_t* idx) {
+        // (the ragged last chunk is laid out densely: the fp32 matrix-core products read a score gradient whose
+        // leading dimension is a multiple of 4 in whole groups of 4 columns, as if its width were one too)
+        const int64_t ld = (nc & 3) ? nc : cols;
+        if (int e = bess_neg_score_shared_fwd_ws(&td, query, n_query, base, idx, nc, sc, ld, gws, gws_bytes, stream)) return e;
+        k_softmax_coef<<<rows4, 256, 0, st>>>(sc, P, ld, n_query, nc, lse, coef);
+        if (int e = check_launch("softmax_coef")) return e;
+        if (int e = bess_neg_score_shared_bwd_ws(&td, query, n_query, base, idx, nc, sc, ld, P, ld, dq_chunk,
+                                                 d_neg + j0 * W, gws, gws_bytes, stream))
+            return e;
+        k_add_into<<<static_cast<unsigned>(ceil_div(nqw, 256)), 256, 0, st>>>(d_query, dq_chunk, nqw);
+        return check_launch("add_into");
+    });
+}
+
 // ---- single (query, candidate) scores in the arithmetic of the all-entity kernels -------------------------
 // out[i] = score(query[i], candidate idx[i]) as bess_neg_score_shared_fwd_counts on a (like_n_query x like_n_neg)
 // problem computes it: the SAME kernel on the diagonal tiles of the (pairs x pairs) problem - 128 x 128 tiles of the
@@ -1164,7 +1344,6 @@ extern "C" int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const f
 // neg_base is always the table in desc.dtype (optional neg_idx).  That is what the shared calls take for every
 // scorer but the affine family, whose shared kernels are defined on dense normalised f32 rows: for them the tile
 // kernel stages the raw rows and scales them by inverse norms computed per chunk (affine.hip).
-static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 extern "C" int64_t bess_neg_score_table_fwd_counts_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
     if (!d || check_desc(d) || n_query <= 0 || n_neg <= 0) return 0;

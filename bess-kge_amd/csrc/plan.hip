@@ -85,11 +85,13 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_neg_score_shared_fwd_pruned),
     BESS_PLAN_FN(bess_neg_score_shared_fwd_counts),
     BESS_PLAN_FN(bess_neg_score_shared_fwd_pairs),
+    BESS_PLAN_FN(bess_neg_score_shared_fwd_lse),
     BESS_PLAN_FN(bess_neg_score_table_fwd_counts),
     BESS_PLAN_FN(bess_neg_score_table_fwd_pairs),
     BESS_PLAN_FN(bess_neg_score_shared_bwd),
     BESS_PLAN_FN(bess_neg_score_shared_bwd_ws),
     BESS_PLAN_FN(bess_neg_score_shared_bwd_parts),
+    BESS_PLAN_FN(bess_neg_score_shared_bwd_softmax),
     BESS_PLAN_FN(bess_mask_scores),
     BESS_PLAN_FN(bess_loss_fwd_bwd),
     BESS_PLAN_FN(bess_loss_fwd_bwd_norm),

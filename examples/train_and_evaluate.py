@@ -7,6 +7,7 @@ queries and report filtered-free MRR / hits@10.
     python examples/train_and_evaluate.py [--n-shard 1] [--steps 400] [--scorer TransE] [--negative-weights degree]
                                              [--loss ssce --proposal-correction]
                                              [--regularizer n3 --reg-coef 1e-3]
+                                             [--training 1vsall]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -33,6 +34,7 @@ from besskge.dataset import KGDataset  # noqa: E402
 from besskge.device_sampler import DeviceBatchSampler  # noqa: E402
 from besskge.loss import LogSigmoidLoss, SampledSoftmaxCrossEntropyLoss  # noqa: E402
 from besskge.metric import Evaluation  # noqa: E402
+from besskge.one_vs_all import OneVsAllBessKGE  # noqa: E402
 from besskge.negative_sampler import (  # noqa: E402
     PlaceholderNegativeSampler,
     RandomShardedNegativeSampler,
@@ -81,9 +83,17 @@ def main(argv=None) -> dict:
                     help="penalty on the embeddings of the positive triples: n3 = cubed moduli (ComplEx-N3, "
                          "DistMult-N3), l2 / l3 = squared / cubed coordinates")
     ap.add_argument("--reg-coef", type=float, default=1e-3, help="coefficient of --regularizer")
+    ap.add_argument("--training", default="sampled", choices=["sampled", "1vsall"],
+                    help="1vsall: the loss of a triple is the cross entropy of its tail against ALL entities "
+                         "(OneVsAllBessKGE: no negatives are sampled, no score matrix is written)")
     args = ap.parse_args(argv)
     if args.proposal_correction and (args.negative_weights != "degree" or args.loss != "ssce"):
         ap.error("--proposal-correction needs --negative-weights degree and --loss ssce")
+    one_vs_all = args.training == "1vsall"
+    if one_vs_all and (args.proposal_correction or args.negative_weights != "uniform" or args.loss != "logsigmoid"
+                       or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx")):
+        ap.error("--training 1vsall samples nothing and brings its own loss: TransE / RotatE / DistMult / ComplEx, "
+                 "without --negative-weights / --loss / --proposal-correction")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
 
@@ -101,7 +111,9 @@ def main(argv=None) -> dict:
 
     # ---- training: shared ("flat") random negatives, log-sigmoid (or sampled-softmax) loss, Adam
     pts = PartitionedTripleSet.create_from_dataset(ds, "train", sharding, partition_mode="ht_shardpair")
-    if args.negative_weights == "degree":
+    if one_vs_all:
+        ns = PlaceholderNegativeSampler("t")
+    elif args.negative_weights == "degree":
         ns = WeightedShardedNegativeSampler(degree_weights([train], args.n_entity), n_negative=64, sharding=sharding,
                                             seed=1, corruption_scheme="t", local_sampling=False,
                                             flat_negative_format=True, return_logq=args.proposal_correction)
@@ -109,14 +121,17 @@ def main(argv=None) -> dict:
         ns = RandomShardedNegativeSampler(n_negative=64, sharding=sharding, seed=1, corruption_scheme="t",
                                           local_sampling=False, flat_negative_format=True)
     bs = RandomShardedBatchSampler(pts, ns, shard_bs=512, batches_per_step=4, seed=2)
-    if args.loss == "ssce":
+    if args.loss == "ssce" or one_vs_all:
         loss_fn = SampledSoftmaxCrossEntropyLoss(args.n_entity, proposal_correction=args.proposal_correction)
     else:
         loss_fn = LogSigmoidLoss(margin=6.0, negative_adversarial_sampling=True)
     regularizer = {"none": None, "n3": EmbeddingRegularizer.n3(args.reg_coef),
                    "l2": EmbeddingRegularizer.lp(2, args.reg_coef), "l3": EmbeddingRegularizer.lp(3, args.reg_coef)
                    }[args.regularizer]
-    model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)
+    if one_vs_all:
+        model = OneVsAllBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)
+    else:
+        model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)
     trainer = runtime.training_model(model, runtime.Options(device_iterations=bs.batches_per_step),
                                      runtime.Adam(lr=args.lr), device=dev)
     feed = DeviceBatchSampler(bs, dev)  # the numpy streams of `bs`, continued in HBM
@@ -129,7 +144,7 @@ def main(argv=None) -> dict:
             print(f"step {step:4d}  loss {losses[-1]:.4f}", flush=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    per_step = bs.batches_per_step * args.n_shard * 512 * (1 + 64 * args.n_shard)
+    per_step = bs.batches_per_step * args.n_shard * 512 * (1 + (args.n_entity if one_vs_all else 64 * args.n_shard))
     print(f"{args.steps} steps in {dt:.2f} s  ({args.steps * per_step / dt / 1e6:.1f} M triples/s incl. sampling)")
 
     # ---- evaluation: score every entity as tail of the held-out (h, r, ?) queries

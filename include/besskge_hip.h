@@ -351,6 +351,45 @@ int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const float* quer
                                      const int32_t* excl, int32_t* counts, int32_t round_f16, void* workspace,
                                      int64_t workspace_bytes, void* stream);
 
+/* K4 for a softmax over ALL candidates without the score matrix ("1vsAll" training: the loss of a triple is the
+ * cross entropy of its true completion against every entity).  TransE / RotatE / DistMult / ComplEx; other scorers
+ * return BESS_EUNSUPPORTED.
+ *
+ * bess_neg_score_shared_fwd_lse merges, for every query row q, the candidates' scores into state_ml [n_query, 2] f32
+ * = (running max m, running sum l of exp(score - m)); log-sum-exp = m + log l.  The state is merged INTO, so several
+ * calls (candidate chunks, windows, shards) accumulate; (-inf, 0) is the empty state.
+ *   - DistMult / ComplEx shapes whose counts are an epilogue of the split-fp16 matrix-core product (ksplit == 1,
+ *     bess_neg_score_shared_workspace > 0, no BESS_FLAG_FP32_MATH) and a workspace of at least
+ *     bess_neg_score_shared_fwd_lse_workspace bytes: an epilogue of that product beside the counting one.  Every
+ *     64 x 64 wave tile reduces its rows to (m, l) and stores them with plain stores into partials at the front of
+ *     the workspace (one per row and 64 candidates of a chunk of at most 65,536: bounded whatever n_neg); a small
+ *     kernel merges them in a fixed order.  No float atomics: state_ml is bitwise reproducible.  An operand outside
+ *     the fp16 range sets every state_ml of the call to NaN (the INT32_MIN of the counts): call again with
+ *     BESS_FLAG_FP32_MATH on a fresh state.
+ *   - every other shape: candidates go through in chunks of `cols` columns of scores (bess_neg_score_shared_fwd_ws
+ *     in fp32 arithmetic) in the workspace, a one-wave-per-row kernel folds each tile into state_ml.
+ *     cols = workspace_bytes / (4 * n_query), rounded down to a multiple of 64 and to what n_neg needs; at least 64.
+ *
+ * bess_neg_score_shared_bwd_softmax: with P[q, j] = coef[q] * exp(score(q, j) - lse[q]) (lse, coef: f32 [n_query]),
+ *   d_query [n_query, W] += sum_j P[q, j] dscore/dquery      (added to: clear it, or hand in what it is to join)
+ *   d_neg   [n_neg, W]    = sum_q P[q, j] dscore/dcandidate   (written, in candidate order)
+ * Per chunk of `cols` candidates the scores are recomputed into a tile, turned into P in a second tile (the scores
+ * stay: the p != 1 backward reads them) and bess_neg_score_shared_bwd_ws computes both products; that call
+ * overwrites its d_query, so the chunk's d_query goes to a buffer of its own in the workspace and a kernel adds it
+ * in.  coef[q] == 0 gives exact zeros.  Workspace layout: [n_query * W floats, rounded up to 256 B | scores | P |
+ * scratch of the matrix-core products]; cols = (workspace_bytes - first part) / (8 * n_query), rounded down to a
+ * multiple of 64, to what n_neg needs and to the 64 MiB tiles of the default; at least 64.
+ * Both workspaces 16-B aligned; the _workspace queries are host arithmetic. */
+int64_t bess_neg_score_shared_fwd_lse_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg);
+int bess_neg_score_shared_fwd_lse(const bess_model_desc* d, const float* query, int64_t n_query,
+                                  const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* state_ml,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+int64_t bess_neg_score_shared_bwd_softmax_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg);
+int bess_neg_score_shared_bwd_softmax(const bess_model_desc* d, const float* query, int64_t n_query,
+                                      const void* neg_base, const int32_t* neg_idx, int64_t n_neg, const float* lse,
+                                      const float* coef, float* d_query, float* d_neg, void* workspace,
+                                      int64_t workspace_bytes, void* stream);
+
 /* Single (query, candidate) scores in the arithmetic of the all-entity pass: out[i] = score(query[i], row
  * neg_idx[i] of neg_base) exactly as bess_neg_score_shared_fwd_counts / _fwd_ws computes that element inside a
  * (like_n_query x like_n_neg) problem - the same kernel run on the diagonal tiles of the (pairs x pairs) problem
