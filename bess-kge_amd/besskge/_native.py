@@ -36,7 +36,8 @@ _i64 = ctypes.c_int64
 _RETURNS_I64 = ("bess_neg_score_shared_workspace", "bess_neg_score_shared_bwd_workspace",
                 "bess_neg_score_shared_fwd_counts_workspace", "bess_neg_score_shared_fwd_pairs_workspace",
                 "bess_neg_score_table_fwd_counts_workspace", "bess_neg_score_table_fwd_pairs_workspace",
-                "bess_neg_score_shared_fwd_lse_workspace", "bess_neg_score_shared_bwd_softmax_workspace")  # every other entry returns an int status
+                "bess_neg_score_shared_fwd_lse_workspace", "bess_neg_score_shared_bwd_softmax_workspace",
+                "bess_neg_score_shared_fwd_bce_workspace", "bess_neg_score_shared_bwd_bce_workspace")  # every other entry returns an int status
 _i32 = ctypes.c_int32
 _f32 = ctypes.c_float
 
@@ -151,6 +152,12 @@ SIGNATURES = {
     "bess_neg_score_shared_fwd_lse": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
     "bess_neg_score_shared_bwd_softmax_workspace": [_MD, _i64, _i64],
     "bess_neg_score_shared_bwd_softmax": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "bess_neg_score_shared_fwd_bce_workspace": [_MD, _i64, _i64],
+    "bess_neg_score_shared_fwd_bce": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
+    "bess_label_score_sums": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "bess_neg_score_shared_bwd_bce_workspace": [_MD, _i64, _i64],
+    "bess_neg_score_shared_bwd_bce": [_MD, _vp, _i64, _vp, _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                      _vp],
     "bess_neg_score_table_fwd_counts_workspace": [_MD, _i64, _i64],
     "bess_neg_score_table_fwd_counts": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
     "bess_neg_score_table_fwd_pairs_workspace": [_MD, _i64, _i64],
@@ -1192,6 +1199,108 @@ def neg_score_shared_bwd_softmax(d: ModelDesc, query: torch.Tensor, neg: RowSour
     _launch("bess_neg_score_shared_bwd_softmax", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
             _idx(neg.idx, "negative idx"), n_neg, lse.data_ptr(), coef.data_ptr(), d_query.data_ptr(),
             d_neg.data_ptr(), _ptr(ws), ws_bytes)
+    return d_query, d_neg
+
+
+def neg_score_shared_bce(d: ModelDesc, query: torch.Tensor, neg: RowSource, state_ab: Optional[torch.Tensor] = None,
+                         workspace_bytes: Optional[int] = None) -> torch.Tensor:
+    """The dense sums of a multi-label BCE over all candidates without the score matrix
+    (`bess_neg_score_shared_fwd_bce`): adds (A, B) = (sum_j softplus(score), sum_j score) of every query over `neg`
+    to `state_ab` [nq, 2] f32 - zeros when None - and returns it.  Several calls accumulate.  `workspace_bytes` and
+    the fp16 range: as for `neg_score_shared_lse` (NaN states from the matrix-core path are restored and the call is
+    repeated in fp32 arithmetic; one host read of a flag, on that path only)."""
+    nq, n_neg = int(query.shape[0]), len(neg)
+    dev = _neg_operands(d, query, neg, n_neg)
+    if int(d.scorer) > COMPLEX:
+        raise ValueError("neg_score_shared_bce: TransE / RotatE / DistMult / ComplEx only")
+    if state_ab is None:
+        state_ab = torch.zeros((nq, 2), dtype=torch.float32, device=dev)
+    else:
+        _same_device([("state_ab", state_ab), ("query", query)])
+        if tuple(state_ab.shape) != (nq, 2) or state_ab.dtype != torch.float32 or not state_ab.is_contiguous():
+            raise ValueError("neg_score_shared_bce: state_ab must be a contiguous [nq, 2] float32 tensor")
+    if nq == 0 or n_neg == 0:
+        return state_ab
+
+    def run(desc: ModelDesc, ws_bytes: Optional[int]) -> None:
+        ws, nbytes = _sized_workspace("bess_neg_score_shared_fwd_bce_workspace", desc, nq, n_neg, dev, ws_bytes)
+        _launch("bess_neg_score_shared_fwd_bce", dev, ctypes.byref(desc), query.data_ptr(), nq, neg.base.data_ptr(),
+                _idx(neg.idx, "negative idx"), n_neg, state_ab.data_ptr(), _ptr(ws), nbytes)
+
+    fused = int(load().bess_neg_score_shared_workspace(ctypes.byref(d), nq, n_neg)) > 0
+    before = state_ab.clone() if fused else None
+    run(d, workspace_bytes)
+    if fused and bool(torch.isnan(state_ab).any()) and not bool(torch.isnan(before).any()):
+        state_ab.copy_(before)
+        exact = copy_desc(d)
+        exact.reserved[0] |= FLAG_FP32_MATH
+        run(exact, None)
+    return state_ab
+
+
+def _labels(who: str, label_ptr: torch.Tensor, label_col: torch.Tensor, nq: int, validate: bool) -> None:
+    """The ragged label lists of the BCE calls: `label_ptr` int64 [nq + 1], `label_col` int32 [label_ptr[-1]]
+    (positions in the candidate list).  `validate`: read `label_ptr` on the host and check it against `label_col`
+    (callers that built the lists on the device from their own count pass skip the read)."""
+    if label_ptr.dtype != torch.int64 or label_ptr.dim() != 1 or label_ptr.numel() != nq + 1 \
+            or not label_ptr.is_contiguous():
+        raise ValueError(f"{who}: label_ptr must be a contiguous int64 [n_query + 1] tensor")
+    if label_col.dtype != torch.int32 or label_col.dim() != 1 or not label_col.is_contiguous():
+        raise ValueError(f"{who}: label_col must be a contiguous 1-D int32 tensor")
+    if validate:
+        ptr = label_ptr.cpu()
+        if int(ptr[0]) != 0 or int(ptr[-1]) != label_col.numel() or bool((ptr[1:] < ptr[:-1]).any()):
+            raise ValueError(f"{who}: label_ptr must ascend from 0 to the {label_col.numel()} entries of label_col")
+
+
+def label_score_sums(d: ModelDesc, query: torch.Tensor, neg: RowSource, label_ptr: torch.Tensor,
+                     label_col: torch.Tensor, validate: bool = True) -> torch.Tensor:
+    """C [nq] f32 of a multi-label BCE (`bess_label_score_sums`): the sum, in list order, of
+    score(query[q], candidate label_col[k]) over the labels label_ptr[q] <= k < label_ptr[q + 1] of every row;
+    positions outside 0 .. len(neg) - 1 are skipped, an empty list gives 0."""
+    nq, n_neg = int(query.shape[0]), len(neg)
+    dev = _neg_operands(d, query, neg, n_neg)
+    if int(d.scorer) > COMPLEX:
+        raise ValueError("label_score_sums: TransE / RotatE / DistMult / ComplEx only")
+    _same_device([("label_ptr", label_ptr), ("label_col", label_col), ("query", query)])
+    _labels("label_score_sums", label_ptr, label_col, nq, validate)
+    out = torch.empty(nq, dtype=torch.float32, device=dev)
+    if nq:
+        _launch("bess_label_score_sums", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+                _idx(neg.idx, "negative idx"), n_neg, label_ptr.data_ptr(), label_col.data_ptr(), out.data_ptr())
+    return out
+
+
+def neg_score_shared_bwd_bce(d: ModelDesc, query: torch.Tensor, neg: RowSource, smooth: float, pw: float,
+                             label_ptr: torch.Tensor, label_col: torch.Tensor, coef: torch.Tensor,
+                             d_query: Optional[torch.Tensor] = None, workspace_bytes: Optional[int] = None,
+                             validate: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Backward of a multi-label BCE over all candidates without the score matrix
+    (`bess_neg_score_shared_bwd_bce`): with P[q, j] = coef[q] * (sigmoid(score(q, j)) - smooth - pw * [j is a label
+    of q]), returns (d_query [nq, W] with sum_j P dscore/dquery ADDED to what it held - zeros when None -,
+    d_neg [n_neg, W] = sum_q P dscore/dcandidate in candidate order).  Labels: as for `label_score_sums`."""
+    nq, n_neg = int(query.shape[0]), len(neg)
+    dev = _neg_operands(d, query, neg, n_neg)
+    if int(d.scorer) > COMPLEX:
+        raise ValueError("neg_score_shared_bwd_bce: TransE / RotatE / DistMult / ComplEx only")
+    _same_device([("label_ptr", label_ptr), ("label_col", label_col), ("coef", coef), ("d_query", d_query),
+                  ("query", query)])
+    _f32(coef, "coef")
+    if coef.numel() != nq:
+        raise ValueError("neg_score_shared_bwd_bce: one coef per query")
+    _labels("neg_score_shared_bwd_bce", label_ptr, label_col, nq, validate)
+    W = int(d.width)
+    if d_query is None:
+        d_query = torch.zeros((nq, W), dtype=torch.float32, device=dev)
+    elif tuple(d_query.shape) != (nq, W) or d_query.dtype != torch.float32 or not d_query.is_contiguous():
+        raise ValueError("neg_score_shared_bwd_bce: d_query must be a contiguous [nq, W] float32 tensor")
+    d_neg = torch.empty((n_neg, W), dtype=torch.float32, device=dev)
+    if nq == 0 or n_neg == 0:
+        return d_query, d_neg.zero_()
+    ws, ws_bytes = _sized_workspace("bess_neg_score_shared_bwd_bce_workspace", d, nq, n_neg, dev, workspace_bytes)
+    _launch("bess_neg_score_shared_bwd_bce", dev, ctypes.byref(d), query.data_ptr(), nq, neg.base.data_ptr(),
+            _idx(neg.idx, "negative idx"), n_neg, float(smooth), float(pw), label_ptr.data_ptr(),
+            label_col.data_ptr(), coef.data_ptr(), d_query.data_ptr(), d_neg.data_ptr(), _ptr(ws), ws_bytes)
     return d_query, d_neg
 
 

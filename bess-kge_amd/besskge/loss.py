@@ -184,3 +184,43 @@ class SampledSoftmaxCrossEntropyLoss(BaseLossFunction):
         if self.proposal_correction:
             return -float(np.log(n_negative))
         return float(np.log(self.n_entity - 1) - np.log(n_negative))
+
+
+class AllEntitiesBCELoss(BaseLossFunction):
+    """Binary cross entropy with logits over ALL entities ("KvsAll": every known completion of a query is a positive
+    label, every other entity a negative), the loss of `besskge.k_vs_all.KvsAllBessKGE`:
+
+        loss_scale * sum_i w_i sum_e BCEWithLogits(s_ie, (1 - label_smoothing) * [e is a label of i]
+                                                          + label_smoothing / n_entity)
+
+    It carries its three numbers; the sums run inside the scoring kernels, which never hold the [S, n_entity] score
+    matrix this class would need to be applied to."""
+
+    def __init__(self, n_entity: int, label_smoothing: float = 0.0, loss_scale: float = 1.0) -> None:
+        super().__init__()
+        if int(n_entity) <= 0:
+            raise ValueError("AllEntitiesBCELoss: n_entity must be positive")
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f"AllEntitiesBCELoss: label_smoothing {label_smoothing} is not in [0, 1)")
+        self.negative_adversarial_sampling = False
+        self.negative_adversarial_scale = torch.tensor(0.0, dtype=torch.float32)
+        self.loss_scale = torch.tensor(loss_scale, dtype=torch.float32)
+        self.n_entity = int(n_entity)
+        self.label_smoothing = float(label_smoothing)
+
+    @property
+    def smooth(self) -> float:
+        """The label of an entity that is no completion: label_smoothing / n_entity."""
+        return self.label_smoothing / self.n_entity
+
+    @property
+    def positive_weight(self) -> float:
+        """What a completion's label has on top of `smooth`: 1 - label_smoothing."""
+        return 1.0 - self.label_smoothing
+
+    def kernel_desc(self, n_negative: int) -> nat.LossDesc:
+        raise RuntimeError("AllEntitiesBCELoss has no score-matrix kernel: it is the loss of KvsAllBessKGE")
+
+    def forward(self, *args: object, **kwargs: object) -> torch.Tensor:
+        raise RuntimeError("AllEntitiesBCELoss is not applied to score matrices: KvsAllBessKGE sums it inside the "
+                           "scoring kernels (bess_neg_score_shared_fwd_bce)")

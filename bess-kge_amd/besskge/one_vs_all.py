@@ -67,22 +67,52 @@ class OneVsAllBessKGE(BessKGE):
         :param evaluation: must be None (ranks over all entities: `AllScoresPipeline`).
         :param regularizer: as for the other schemes.
         """
+        me = type(self).__name__
         if return_scores:
-            raise ValueError("OneVsAllBessKGE never holds the [S, n_entity] scores: return_scores=True is refused")
+            raise ValueError(f"{me} never holds the [S, n_entity] scores: return_scores=True is refused")
         if not isinstance(negative_sampler, PlaceholderNegativeSampler) or negative_sampler.corruption_scheme not in (
                 "h", "t"):
-            raise ValueError('OneVsAllBessKGE takes PlaceholderNegativeSampler("h") or ("t"): every entity is a '
+            raise ValueError(f'{me} takes PlaceholderNegativeSampler("h") or ("t"): every entity is a '
                              'candidate, nothing is sampled (scheme "ht" is not built)')
         if type(score_fn) not in (TransE, RotatE, DistMult, ComplEx):
-            raise ValueError("OneVsAllBessKGE: TransE, RotatE, DistMult or ComplEx "
+            raise ValueError(f"{me}: TransE, RotatE, DistMult or ComplEx "
                              f"(the scorers of bess_neg_score_shared_fwd_lse), not {type(score_fn).__name__}")
+        self._check_loss(loss_fn, score_fn)
+        if evaluation is not None:
+            raise ValueError(f"{me}: metrics over all entities come from AllScoresPipeline, evaluation=None")
+        super().__init__(negative_sampler, score_fn, loss_fn, None, False, False, regularizer)
+
+    # ---- what a loss over all entities defines (KvsAllBessKGE overrides these five) ----------------------------
+    def _check_loss(self, loss_fn: BaseLossFunction, score_fn: BaseScoreFunction) -> None:
         if not isinstance(loss_fn, SampledSoftmaxCrossEntropyLoss) or loss_fn.proposal_correction \
                 or int(loss_fn.n_entity) != int(score_fn.sharding.n_entity):
             raise ValueError("OneVsAllBessKGE: the loss is SampledSoftmaxCrossEntropyLoss(n_entity=sharding.n_entity) "
                              "without proposal_correction (the softmax runs over all entities: nothing to correct)")
-        if evaluation is not None:
-            raise ValueError("OneVsAllBessKGE: metrics over all entities come from AllScoresPipeline, evaluation=None")
-        super().__init__(negative_sampler, score_fn, loss_fn, None, False, False, regularizer)
+
+    def _query_labels(self, steps: List[_ReplicaStep], rel_all: List[torch.Tensor]) -> List[Any]:
+        """Per local shard: what its pass over all queries needs beside the query matrix (nothing here)."""
+        return [None] * len(steps)
+
+    def _shard_partial(self, shard: int, st: _ReplicaStep, desc: Any, query: torch.Tensor, labels: Any) -> torch.Tensor:
+        """[n_query, k] f32: the shard's share of every query's sum over all entities - here (m, l)."""
+        return nat.neg_score_shared_lse(desc, query, self._candidates(shard, st.table))
+
+    def _merge_partials(self, part: torch.Tensor, pos: torch.Tensor) -> Any:
+        """part [n_shard, S, k] at the triples' owner -> (what the backward needs of every row [S, m], the rows'
+        loss terms [S], d term / d pos); merged in shard order."""
+        m, l = part[0, :, 0], part[0, :, 1]
+        for s in range(1, part.shape[0]):
+            mm = torch.maximum(m, part[s, :, 0])
+            l = l * torch.exp(m - mm) + part[s, :, 1] * torch.exp(part[s, :, 0] - mm)
+            m = mm
+        lse = (m + torch.log(l)).contiguous()
+        return lse.reshape(-1, 1), lse - pos, -1.0
+
+    def _shard_backward(self, shard: int, st: _ReplicaStep, desc: Any, query: torch.Tensor, norm: torch.Tensor,
+                        coef: torch.Tensor, labels: Any) -> Any:
+        """(the shard's share of d_query, the dense gradient of its real rows)"""
+        return nat.neg_score_shared_bwd_softmax(desc, query, self._candidates(shard, st.table),
+                                                norm[:, 0].contiguous(), coef)
 
     # ------------------------------------------------------------------ pieces
     def _triple_weight(self, batch: _Batch, device: torch.device, scale: float = 1.0) -> torch.Tensor:
@@ -117,7 +147,7 @@ class OneVsAllBessKGE(BessKGE):
             st.table = self._local_table(shard)
             dev = st.table.device
             if nat._capturing(dev):
-                raise RuntimeError("OneVsAllBessKGE runs eagerly: its step reads a flag on the host and cannot be "
+                raise RuntimeError(f"{type(self).__name__} runs eagerly: its step reads a flag on the host and cannot be "
                                    "recorded into a graph (Options.use_graphs / use_plans)")
             for k in ("head", "relation", "tail"):
                 if b[k].shape[0] != 1:
@@ -135,7 +165,8 @@ class OneVsAllBessKGE(BessKGE):
         rel_all = group.all_gather(rels)  # [n(j), n, ppp]
         rows_all = group.all_gather(rows_q)  # "t": [n(j), n(t), ppp, W]; "h": [n(t), n(j), ppp, W]
         partials, q_state = [], []
-        for shard, st, rows, relr in zip(group.local_shards, steps, rows_all, rel_all):
+        labels_all = self._query_labels(steps, rel_all)
+        for shard, st, rows, relr, labels in zip(group.local_shards, steps, rows_all, rel_all, labels_all):
             dev = st.table.device
             idx = None
             if scheme == "h":  # gathered as [t, j, p] but wanted as [j, t, p]
@@ -145,33 +176,29 @@ class OneVsAllBessKGE(BessKGE):
             ent = RowSource(rows.reshape(-1, W), idx)
             rel_q = relr.reshape(-1).contiguous()
             query, qctx = fn.query_fwd(side, ent, rel_q)
-            state = nat.neg_score_shared_lse(desc, query, self._candidates(shard, st.table))
-            partials.append(state.reshape(n, n * st.ppp, 2))
-            q_state.append((ent, rel_q, query, qctx))
+            state = self._shard_partial(shard, st, desc, query, labels)
+            partials.append(state.reshape(n, n * st.ppp, -1))
+            q_state.append((ent, rel_q, query, qctx, labels))
         ml_back = group.all_to_all(partials)  # [n(shard), S, 2] at the triples' owner
         tails_in = group.all_to_all(tails_out)
-        outs, lses, coefs = [], [], []
+        outs, norms, coefs = [], [], []
+        d_pos = -1.0
         for st, b, ml, tl in zip(steps, batches, ml_back, tails_in):
             dev = st.table.device
-            # the n partials of a query, merged in shard order
-            m, l = ml[0, :, 0], ml[0, :, 1]
-            for s in range(1, n):
-                mm = torch.maximum(m, ml[s, :, 0])
-                l = l * torch.exp(m - mm) + ml[s, :, 1] * torch.exp(ml[s, :, 0] - mm)
-                m = mm
-            lse = (m + torch.log(l)).contiguous()
             st.recv = tl.reshape(-1, W)
             st.tail = RowSource(st.recv, None)
             st.positive_score, st.triple_ctx = fn.triple_fwd(RowSource(st.table, st.head_idx), st.tail, st.rel_idx)
+            # the n partials of a query, merged in shard order
+            norm, term, d_pos = self._merge_partials(ml, st.positive_score)
             w = self._triple_weight(b, dev, scale)
-            coef = (w * float(self.loss_fn.loss_scale)).expand(lse.shape[0]).contiguous()
-            loss = (coef * (lse - st.positive_score)).sum().reshape(1)
+            coef = (w * float(self.loss_fn.loss_scale)).expand(term.shape[0]).contiguous()
+            loss = (coef * term).sum().reshape(1)
             out: Dict[str, Any] = dict(loss=(loss if scale == 1.0 else loss / scale).reshape(()),
                                        positive_score=st.positive_score.to(fn.relation_embedding.dtype))
             outs.append(out)
-            lses.append(lse)
+            norms.append(norm)
             coefs.append(coef)
-        return dict(steps=steps, q_state=q_state, outs=outs, lse=lses, coef=coefs)
+        return dict(steps=steps, q_state=q_state, outs=outs, norm=norms, coef=coefs, d_pos=d_pos)
 
     # ---------------------------------------------------------------- forward
     def forward(self, head: torch.Tensor, relation: torch.Tensor, tail: torch.Tensor,  # type: ignore[override]
@@ -208,30 +235,29 @@ class OneVsAllBessKGE(BessKGE):
         ctx = _StepContext(batches, training=True, grad_scale=grad_scale)
         d_rel = self._relation_gradient(ctx, pending)
         shards = [_ShardGrads(st) for st in steps]
-        # positives: d loss / d pos = -coef
+        # positives: d loss / d pos = -coef (times the positive label's weight under KvsAll)
         d_tails = []
         for sh, b, out, coef in zip(shards, batches, outs, fwd["coef"]):
             st = sh.step
             dh, dt = fn.triple_bwd(RowSource(st.table, st.head_idx), st.tail, st.rel_idx, st.triple_ctx,
-                                   (-coef).contiguous(), d_rel)
+                                   (fwd["d_pos"] * coef).contiguous(), d_rel)
             if self.regularizer is not None:
                 self._regularize(st, b, out, grad_scale, dh, dt, d_rel)
             sh.rows.append((st.head_idx, dh))
             d_tails.append(dt.reshape(n, st.ppp, W))
         d_tail_back = group.all_to_all(d_tails)
-        # the softmax: every shard needs (lse, coef) of the queries it scored
-        norm_all = group.all_gather([torch.stack([z, c], dim=1) for z, c in zip(fwd["lse"], fwd["coef"])])  # [n(j), S, 2]
+        # every shard needs (the rows' normalisers, coef) of the queries it scored
+        norm_all = group.all_gather([torch.cat([z, c.reshape(-1, 1)], dim=1)
+                                     for z, c in zip(fwd["norm"], fwd["coef"])])  # [n(j), S, m + 1]
         d_q = []
-        for shard, sh, dtb, norm, (ent, rel_q, query, qctx) in zip(group.local_shards, shards, d_tail_back, norm_all,
-                                                                  fwd["q_state"]):
+        for shard, sh, dtb, norm, (ent, rel_q, query, qctx, labels) in zip(group.local_shards, shards, d_tail_back,
+                                                                          norm_all, fwd["q_state"]):
             st = sh.step
             dev = st.table.device
             sh.rows.append((st.local_tail.reshape(-1), dtb.reshape(-1, W)))
-            norm = norm.reshape(-1, 2)
-            cand = self._candidates(shard, st.table)
-            dq, dn = nat.neg_score_shared_bwd_softmax(desc, query, cand, norm[:, 0].contiguous(),
-                                                      norm[:, 1].contiguous())
-            rows = self._static_map(("1vsall rows", len(cand)), lambda: torch.arange(len(cand)), dev)
+            norm = norm.reshape(-1, norm.shape[-1])
+            dq, dn = self._shard_backward(shard, st, desc, query, norm[:, :-1], norm[:, -1].contiguous(), labels)
+            rows = self._static_map(("1vsall rows", dn.shape[0]), lambda: torch.arange(dn.shape[0]), dev)
             sh.rows.append((rows, dn))
             dx = fn.query_bwd(side, ent, rel_q, qctx, dq, d_rel)
             if ent.idx is not None:  # undo the [t, j, p] -> [j, t, p] re-ordering

@@ -55,6 +55,9 @@ struct CountArgs {
     // log-sum-exp epilogue instead (bess_neg_score_shared_fwd_lse; nothing is counted): the (max, sum of exp(s - max))
     // of row `r` over the 64 columns of wave tile `c` of the launch goes to lse_part[(c * rows + r) * 2]
     float* lse_part;
+    // multi-label BCE epilogue instead (bess_neg_score_shared_fwd_bce): the same slabs hold the row's (sum of
+    // softplus(s), sum of s) over the 64 columns of the wave tile
+    int bce;
 };
 // (m, l) <- (m, l) merged with (m2, l2): states of a running log-sum-exp, (-inf, 0) the empty one
 __device__ __forceinline__ void lse_merge(float& m, float& l, float m2, float l2) {
@@ -62,6 +65,9 @@ __device__ __forceinline__ void lse_merge(float& m, float& l, float m2, float l2
     l = mm == -INFINITY ? 0.f : l * __expf(m - mm) + l2 * __expf(m2 - mm);
     m = mm;
 }
+// softplus(v) = log(1 + exp(v)) and its derivative, the two functions of a binary cross entropy with logits
+__device__ __forceinline__ float bce_softplus(float v) { return fmaxf(v, 0.f) + __logf(1.f + __expf(-fabsf(v))); }
+__device__ __forceinline__ float bce_sigmoid(float v) { return 1.f / (1.f + __expf(-v)); }
 __device__ __forceinline__ float count_value(float v, int round16) {
     return round16 ? static_cast<float>(static_cast<_Float16>(v)) : v;
 }
@@ -75,8 +81,9 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
                    float* out, int64_t ld, void* ws, int64_t ws_bytes, hipStream_t st, const float* thr = nullptr,
                    uint8_t* flags = nullptr, int64_t ld_flags = 0, const CountArgs* count = nullptr,
                    bool diag = false,  // diag: S == N, out [S, 128] receives the diagonal 128 x 128 tiles only
-                   float* lse_state = nullptr);  // [S, 2]: merge every row's log-sum-exp in (the front of ws holds
-                                                 // gemm_split_lse_parts bytes of tile partials; nothing is stored)
+                   float* lse_state = nullptr,  // [S, 2]: merge every row's log-sum-exp in (the front of ws holds
+                                                // gemm_split_lse_parts bytes of tile partials; nothing is stored)
+                   bool bce = false);  // lse_state is (sum of softplus(s), sum of s) instead, added to
 int64_t gemm_split_lse_parts(int64_t S, int64_t N);
 int64_t gemm_split_bwd_workspace(int64_t S, int64_t N, int W);
 int gemm_split_bwd(int dtype, const float* G, int64_t ldg, int64_t S, const float* Q, const void* E,

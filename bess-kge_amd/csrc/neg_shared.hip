@@ -1270,6 +1270,240 @@ extern "C" int bess_neg_score_shared_bwd_softmax(const bess_model_desc* d, const
     });
 }
 
+// ---- multi-label BCE over all candidates without the score matrix (KvsAll training) ------------------------------
+// With y[q, j] = pw * [j is a label of q] + smooth the loss of row q is sum_j BCEWithLogits(s_qj, y_qj) =
+// A - smooth * B - pw * C:  A = sum_j softplus(s), B = sum_j s (bess_neg_score_shared_fwd_bce, state_ab),
+// C = sum over the row's labels of s (bess_label_score_sums).  The labels are a ragged list of candidate positions.
+
+// folds a stored score tile into the rows' (A, B): one wave per row, as k_lse_scores
+__global__ __launch_bounds__(256) void k_bce_scores(const float* __restrict__ sc, int64_t ld, int64_t n_row,
+                                                    int64_t n_col, float* __restrict__ state) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (r >= n_row) return;
+    const float* row = sc + r * ld;
+    float a = 0.f, b = 0.f;
+    for (int64_t j = lane; j < n_col; j += 64) {
+        const float v = row[j];
+        a += bce_softplus(v);
+        b += v;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    if (lane == 0) {
+        state[2 * r] += a;
+        state[2 * r + 1] += b;
+    }
+}
+
+// P[q, j] = coef[q] * (sigmoid(score[q, j]) - smooth - pw * [j0 + j is a label of q]); a zero coefficient gives
+// exact zeros.  One wave per row: first the dense part, then the wave walks the row's label list and rewrites the
+// elements of this chunk.  An element is written twice then - by the lane of its column, later by the lane of its
+// place in the list - so the wave waits for its first stores to complete before the second ones are issued; the
+// second value is computed from the score again (the arithmetic of a read-modify-write, without reading through a
+// cache line the first store may have left stale).  Rows belong to one wave and their labels are distinct: no race.
+__global__ __launch_bounds__(256) void k_bce_coef(const float* __restrict__ sc, float* __restrict__ P, int64_t ld,
+                                                  int64_t n_row, int64_t n_col, int64_t j0, float smooth, float pw,
+                                                  const int64_t* __restrict__ label_ptr,
+                                                  const int32_t* __restrict__ label_col,
+                                                  const float* __restrict__ coef) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (r >= n_row) return;
+    const float c = coef[r];
+    const float* row = sc + r * ld;
+    float* prow = P + r * ld;
+    for (int64_t j = lane; j < n_col; j += 64) prow[j] = c == 0.f ? 0.f : c * (bce_sigmoid(row[j]) - smooth);
+    if (c == 0.f) return;
+    release_to_agent();
+    const float sub = pw * c;
+    const int64_t k1 = label_ptr[r + 1];
+    for (int64_t k = label_ptr[r] + lane; k < k1; k += 64) {
+        const int64_t j = static_cast<int64_t>(label_col[k]) - j0;
+        if (j >= 0 && j < n_col) prow[j] = c * (bce_sigmoid(row[j]) - smooth) - sub;
+    }
+}
+
+// out[q] = sum over the labels of row q of score(query[q], candidate label_col[k]), in list order: one wave per row.
+// The query row stays in registers (lane l holds chunks l, l + 64, .. of VEC scalars, IT of them); every labelled
+// candidate row comes in with one coalesced vector load per chunk, U rows in flight at a time (a wave alone on a
+// long list is bound by the latency of a row, not by its bytes); the scorer's reduction in fp32, a wave sum per
+// label.  A position outside 0 .. n_neg - 1 is skipped: its loads go to candidate 0 and are dropped.
+template <typename T, int RED, int VEC, int IT>
+__global__ __launch_bounds__(256) void k_label_score_sums(const float* __restrict__ query, int64_t n_query,
+                                                          RowSrc<T> E, int W, float sign, float p,
+                                                          const int64_t* __restrict__ label_ptr,
+                                                          const int32_t* __restrict__ label_col,
+                                                          float* __restrict__ out) {
+    constexpr int U = IT <= 2 ? 4 : (IT == 4 ? 2 : 1);
+    const int lane = threadIdx.x & 63;
+    const int64_t r = blockIdx.x * 4ll + (threadIdx.x >> 6);
+    if (r >= n_query) return;
+    const int nch = W / VEC;
+    float q[IT][VEC];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) load_chunk<float, VEC>(query + r * W, lane + 64 * i, nch, q[i]);
+    float total = 0.f;
+    const int64_t k1 = label_ptr[r + 1];
+    for (int64_t k = label_ptr[r]; k < k1; k += U) {
+        float e[U][IT][VEC];
+        bool live[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t pos = k + u < k1 ? static_cast<int64_t>(label_col[k + u]) : -1;
+            live[u] = pos >= 0 && pos < E.n;
+            const T* row = E.row(live[u] ? pos : 0, W);
+#pragma unroll
+            for (int i = 0; i < IT; ++i) load_chunk<T, VEC>(row, lane + 64 * i, nch, e[u][i]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < IT; ++i)
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    if (RED == RED_DOT) acc = fmaf(q[i][v], e[u][i][v], acc);
+                    else if (RED == RED_L1) acc += fabsf(q[i][v] - e[u][i][v]);
+                    else acc += lp_term(q[i][v] - e[u][i][v], p);
+                }
+            acc = wave_allreduce_sum(acc);
+            if (RED == RED_L2) acc = lp_root(acc, p);
+            total += live[u] ? sign * acc : 0.f;
+        }
+    }
+    if (lane == 0) out[r] = total;
+}
+
+extern "C" int bess_label_score_sums(const bess_model_desc* d, const float* query, int64_t n_query,
+                                     const void* neg_base, const int32_t* neg_idx, int64_t n_neg,
+                                     const int64_t* label_ptr, const int32_t* label_col, float* out, void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->scorer > BESS_COMPLEX)
+        return fail(BESS_EUNSUPPORTED, "label_score_sums: TransE / RotatE / DistMult / ComplEx only");
+    BESS_REQUIRE(n_query >= 0 && n_neg >= 0, "label_score_sums: bad sizes");
+    if (n_query == 0) return BESS_OK;
+    BESS_REQUIRE(query && label_ptr && out, "label_score_sums: NULL pointer");
+    hipStream_t st = as_stream(stream);
+    if (n_neg == 0) {  // (no position is inside an empty list)
+        const hipError_t e = fill_words_async(out, 0u, n_query, st);
+        return e == hipSuccess ? BESS_OK : fail(static_cast<int>(e), "fill: %s", hipGetErrorString(e));
+    }
+    BESS_REQUIRE(neg_base, "label_score_sums: NULL pointer");  // (label_col may be NULL when every list is empty)
+    const int W = d->width;
+    // the widest vector the row width and both operands' alignment allow
+    const int64_t sz = scalar_bytes_of(d);
+    int vec = vec_of(d);
+    if (reinterpret_cast<uintptr_t>(query) % 16 || reinterpret_cast<uintptr_t>(neg_base) % (vec * sz)) vec = 1;
+    const int64_t per_lane = ceil_div(W / vec, 64);
+    BESS_REQUIRE(per_lane <= 8, "label_score_sums: rows of %d scalars do not fit a wave's registers", W);
+    const unsigned grid = static_cast<unsigned>(ceil_div(n_query, 4));
+    const float sign = score_sign(d), p = static_cast<float>(d->norm_p);
+    with_candidates(d, neg_base, neg_idx, n_neg, [&](auto E) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(E.base)>>;
+        with_constant<RED_DOT, RED_L1, RED_L2>(reduce_of(d), [&](auto red) {
+            auto launch = [&](auto v) {
+                with_constant<1, 2, 4, 8>(per_lane <= 2 ? static_cast<int>(per_lane) : (per_lane <= 4 ? 4 : 8), [&](auto it) {
+                    k_label_score_sums<T, decltype(red)::value, decltype(v)::value, decltype(it)::value>
+                        <<<grid, 256, 0, st>>>(query, n_query, E, W, sign, p, label_ptr, label_col, out);
+                });
+            };
+            if constexpr (std::is_same_v<T, float>) with_constant<4, 1>(vec, launch);
+            else with_constant<8, 2, 1>(vec, launch);
+        });
+        return BESS_OK;
+    });
+    return check_launch("label_score_sums");
+}
+
+extern "C" int64_t bess_neg_score_shared_fwd_bce_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
+    return bess_neg_score_shared_fwd_lse_workspace(d, n_query, n_neg);  // (the same partials, the same tiles)
+}
+
+extern "C" int bess_neg_score_shared_fwd_bce(const bess_model_desc* d, const float* query, int64_t n_query,
+                                             const void* neg_base, const int32_t* neg_idx, int64_t n_neg,
+                                             float* state_ab, void* workspace, int64_t workspace_bytes,
+                                             void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->scorer > BESS_COMPLEX)
+        return fail(BESS_EUNSUPPORTED, "neg_score_shared_fwd_bce: TransE / RotatE / DistMult / ComplEx only");
+    BESS_REQUIRE(n_query >= 0 && n_neg >= 0, "neg_score_shared_fwd_bce: bad sizes");
+    if (n_query == 0 || n_neg == 0) return BESS_OK;
+    BESS_REQUIRE(query && neg_base && state_ab, "neg_score_shared_fwd_bce: NULL pointer");
+    BESS_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+                 "neg_score_shared_fwd_bce: workspace missing (bess_neg_score_shared_fwd_bce_workspace) or misaligned");
+    hipStream_t st = as_stream(stream);
+    const int64_t fused = lse_fused_workspace(d, n_query, n_neg);
+    if (fused > 0 && workspace_bytes >= fused) {
+        // [tile partials | images of the split product]
+        return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, nullptr, 0, workspace,
+                              workspace_bytes, st, nullptr, nullptr, 0, nullptr, false, state_ab, true);
+    }
+    const int64_t cols = softmax_tile_cols(workspace_bytes, 1, n_query, n_neg);
+    BESS_REQUIRE(cols >= 64, "neg_score_shared_fwd_bce: workspace holds less than 64 columns of scores "
+                             "(bess_neg_score_shared_fwd_bce_workspace)");
+    const bess_model_desc td = tile_path_desc(d);
+    float* tile = static_cast<float*>(workspace);
+    return for_each_candidate_chunk(neg_base, neg_idx, n_neg, cols, row_bytes_of(d),
+                                    [&](int64_t, int64_t nc, const void* base, const int32_t* idx) {
+        if (int e = bess_neg_score_shared_fwd_ws(&td, query, n_query, base, idx, nc, tile, cols, nullptr, 0, stream)) return e;
+        k_bce_scores<<<static_cast<unsigned>(ceil_div(n_query, 4)), 256, 0, st>>>(tile, cols, n_query, nc, state_ab);
+        return check_launch("bce_scores");
+    });
+}
+
+extern "C" int64_t bess_neg_score_shared_bwd_bce_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
+    return bess_neg_score_shared_bwd_softmax_workspace(d, n_query, n_neg);  // (the same layout)
+}
+
+extern "C" int bess_neg_score_shared_bwd_bce(const bess_model_desc* d, const float* query, int64_t n_query,
+                                             const void* neg_base, const int32_t* neg_idx, int64_t n_neg,
+                                             float smooth, float pw, const int64_t* label_ptr,
+                                             const int32_t* label_col, const float* coef, float* d_query,
+                                             float* d_neg, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->scorer > BESS_COMPLEX)
+        return fail(BESS_EUNSUPPORTED, "neg_score_shared_bwd_bce: TransE / RotatE / DistMult / ComplEx only");
+    BESS_REQUIRE(n_query >= 0 && n_neg >= 0, "neg_score_shared_bwd_bce: bad sizes");
+    if (n_query == 0 || n_neg == 0) return BESS_OK;
+    BESS_REQUIRE(query && neg_base && label_ptr && coef && d_query && d_neg, "neg_score_shared_bwd_bce: NULL pointer");
+    BESS_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
+                 "neg_score_shared_bwd_bce: workspace missing (bess_neg_score_shared_bwd_bce_workspace) or misaligned");
+    hipStream_t st = as_stream(stream);
+    const int W = d->width;
+    const int64_t fixed = softmax_bwd_fixed(d, n_query);
+    int64_t cols = workspace_bytes > fixed ? softmax_tile_cols(workspace_bytes - fixed, 2, n_query, n_neg) : 0;
+    BESS_REQUIRE(cols >= 64, "neg_score_shared_bwd_bce: workspace holds less than 64 columns of scores "
+                             "(bess_neg_score_shared_bwd_bce_workspace)");
+    const int64_t dflt = softmax_default_cols(n_query, n_neg);
+    if (cols > dflt) cols = dflt;
+    // [d_query of one chunk | scores | P | scratch of the matrix-core products], as bess_neg_score_shared_bwd_softmax
+    char* ws = static_cast<char*>(workspace);
+    float* dq_chunk = reinterpret_cast<float*>(ws);
+    float* sc = reinterpret_cast<float*>(ws + fixed);
+    float* P = sc + n_query * cols;
+    void* gws = ws + fixed + 2 * n_query * cols * 4;
+    const int64_t gws_bytes = workspace_bytes - fixed - 2 * n_query * cols * 4;
+    const bess_model_desc td = tile_path_desc(d);
+    const unsigned rows4 = static_cast<unsigned>(ceil_div(n_query, 4));
+    const int64_t nqw = n_query * W;
+    return for_each_candidate_chunk(neg_base, neg_idx, n_neg, cols, row_bytes_of(d),
+                                    [&](int64_t j0, int64_t nc, const void* base, const int32_t* idx) {
+        const int64_t ld = (nc & 3) ? nc : cols;  // (the ragged last chunk is laid out densely, as in the softmax pass)
+        if (int e = bess_neg_score_shared_fwd_ws(&td, query, n_query, base, idx, nc, sc, ld, gws, gws_bytes, stream)) return e;
+        k_bce_coef<<<rows4, 256, 0, st>>>(sc, P, ld, n_query, nc, j0, smooth, pw, label_ptr, label_col, coef);
+        if (int e = check_launch("bce_coef")) return e;
+        if (int e = bess_neg_score_shared_bwd_ws(&td, query, n_query, base, idx, nc, sc, ld, P, ld, dq_chunk,
+                                                 d_neg + j0 * W, gws, gws_bytes, stream))
+            return e;
+        k_add_into<<<static_cast<unsigned>(ceil_div(nqw, 256)), 256, 0, st>>>(d_query, dq_chunk, nqw);
+        return check_launch("add_into");
+    });
+}
+
 // ---- single (query, candidate) scores in the arithmetic of the all-entity kernels -------------------------
 // out[i] = score(query[i], candidate idx[i]) as bess_neg_score_shared_fwd_counts on a (like_n_query x like_n_neg)
 // problem computes it: the SAME kernel on the diagonal tiles of the (pairs x pairs) problem - 128 x 128 tiles of the

@@ -7,7 +7,7 @@ queries and report filtered-free MRR / hits@10.
     python examples/train_and_evaluate.py [--n-shard 1] [--steps 400] [--scorer TransE] [--negative-weights degree]
                                              [--loss ssce --proposal-correction]
                                              [--regularizer n3 --reg-coef 1e-3]
-                                             [--training 1vsall]
+                                             [--training 1vsall | kvsall [--label-smoothing 0.1]]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -32,7 +32,8 @@ from besskge.batch_sampler import RandomShardedBatchSampler, RigidShardedBatchSa
 from besskge.bess import EmbeddingMovingBessKGE  # noqa: E402
 from besskge.dataset import KGDataset  # noqa: E402
 from besskge.device_sampler import DeviceBatchSampler  # noqa: E402
-from besskge.loss import LogSigmoidLoss, SampledSoftmaxCrossEntropyLoss  # noqa: E402
+from besskge.k_vs_all import KvsAllBessKGE  # noqa: E402
+from besskge.loss import AllEntitiesBCELoss, LogSigmoidLoss, SampledSoftmaxCrossEntropyLoss  # noqa: E402
 from besskge.metric import Evaluation  # noqa: E402
 from besskge.one_vs_all import OneVsAllBessKGE  # noqa: E402
 from besskge.negative_sampler import (  # noqa: E402
@@ -83,16 +84,20 @@ def main(argv=None) -> dict:
                     help="penalty on the embeddings of the positive triples: n3 = cubed moduli (ComplEx-N3, "
                          "DistMult-N3), l2 / l3 = squared / cubed coordinates")
     ap.add_argument("--reg-coef", type=float, default=1e-3, help="coefficient of --regularizer")
-    ap.add_argument("--training", default="sampled", choices=["sampled", "1vsall"],
+    ap.add_argument("--training", default="sampled", choices=["sampled", "1vsall", "kvsall"],
                     help="1vsall: the loss of a triple is the cross entropy of its tail against ALL entities "
-                         "(OneVsAllBessKGE: no negatives are sampled, no score matrix is written)")
+                         "(OneVsAllBessKGE: no negatives are sampled, no score matrix is written); kvsall: a binary "
+                         "cross entropy over all entities whose positive labels are all known tails of the training "
+                         "set (KvsAllBessKGE)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing of --training kvsall")
     args = ap.parse_args(argv)
     if args.proposal_correction and (args.negative_weights != "degree" or args.loss != "ssce"):
         ap.error("--proposal-correction needs --negative-weights degree and --loss ssce")
-    one_vs_all = args.training == "1vsall"
+    k_vs_all = args.training == "kvsall"
+    one_vs_all = args.training == "1vsall" or k_vs_all
     if one_vs_all and (args.proposal_correction or args.negative_weights != "uniform" or args.loss != "logsigmoid"
                        or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx")):
-        ap.error("--training 1vsall samples nothing and brings its own loss: TransE / RotatE / DistMult / ComplEx, "
+        ap.error(f"--training {args.training} samples nothing and brings its own loss: TransE / RotatE / DistMult / ComplEx, "
                  "without --negative-weights / --loss / --proposal-correction")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -121,14 +126,19 @@ def main(argv=None) -> dict:
         ns = RandomShardedNegativeSampler(n_negative=64, sharding=sharding, seed=1, corruption_scheme="t",
                                           local_sampling=False, flat_negative_format=True)
     bs = RandomShardedBatchSampler(pts, ns, shard_bs=512, batches_per_step=4, seed=2)
-    if args.loss == "ssce" or one_vs_all:
+    if k_vs_all:
+        loss_fn = AllEntitiesBCELoss(args.n_entity, label_smoothing=args.label_smoothing)
+    elif args.loss == "ssce" or one_vs_all:
         loss_fn = SampledSoftmaxCrossEntropyLoss(args.n_entity, proposal_correction=args.proposal_correction)
     else:
         loss_fn = LogSigmoidLoss(margin=6.0, negative_adversarial_sampling=True)
     regularizer = {"none": None, "n3": EmbeddingRegularizer.n3(args.reg_coef),
                    "l2": EmbeddingRegularizer.lp(2, args.reg_coef), "l3": EmbeddingRegularizer.lp(3, args.reg_coef)
                    }[args.regularizer]
-    if one_vs_all:
+    if k_vs_all:  # (the filter is the training triples)
+        model = KvsAllBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, known_triples=[train],
+                              regularizer=regularizer)
+    elif one_vs_all:
         model = OneVsAllBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)
     else:
         model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)

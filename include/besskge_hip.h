@@ -390,6 +390,49 @@ int bess_neg_score_shared_bwd_softmax(const bess_model_desc* d, const float* que
                                       const float* coef, float* d_query, float* d_neg, void* workspace,
                                       int64_t workspace_bytes, void* stream);
 
+/* K4 for a multi-label binary cross entropy over ALL candidates without the score matrix ("KvsAll" training: every
+ * known completion of a query is a positive label, every other entity a negative, optionally smoothed).  With
+ * y[q, j] = pw * [j is a label of q] + smooth, the loss of row q is
+ *   sum_j BCEWithLogits(s_qj, y_qj) = A_q - smooth * B_q - pw * C_q,
+ *   A = sum_j softplus(s_qj),  B = sum_j s_qj,  C = sum over the labels of q of s_qj.
+ * Labels are a ragged list: label_ptr int64 [n_query + 1], label_col int32 [label_ptr[n_query]] holding POSITIONS in
+ * the candidate list (0 .. n_neg - 1; the candidate is row neg_idx[position] when there is a neg_idx), distinct
+ * within a row, in any order; a position outside the list is skipped and never loaded through.
+ * TransE / RotatE / DistMult / ComplEx; other scorers return BESS_EUNSUPPORTED.
+ *
+ * bess_neg_score_shared_fwd_bce adds, for every query row, (A, B) over the call's candidates to state_ab
+ * [n_query, 2] f32; (0, 0) is the empty state and several calls accumulate.  Its two paths, their shapes, their
+ * workspace and its `cols` arithmetic are those of bess_neg_score_shared_fwd_lse: on the split-fp16 product an
+ * epilogue that reduces every 64 x 64 wave tile to one (sum of softplus, sum) per row - plain stores into slabs at
+ * the front of the workspace, summed in a fixed order by a merge kernel after every chunk: no float atomics,
+ * state_ab is bitwise reproducible, an operand outside the fp16 range sets every state_ab of the call to NaN (call
+ * again with BESS_FLAG_FP32_MATH on the state as it was) -, else score tiles of `cols` columns folded by a
+ * one-wave-per-row kernel.
+ *
+ * bess_label_score_sums writes out[q] = C_q in fp32, summed in list order (0 for an empty list): one wave per query
+ * row, the query row in registers, every labelled candidate row read with coalesced vector loads.  Rows of more
+ * than 512 vector chunks (2048 f32 / 4096 f16 scalars at full vector width) are refused with BESS_EINVAL.
+ *
+ * bess_neg_score_shared_bwd_bce: with P[q, j] = coef[q] * (sigmoid(s_qj) - smooth - pw * [j is a label of q]),
+ *   d_query [n_query, W] += sum_j P[q, j] dscore/dquery      (added to)
+ *   d_neg   [n_neg, W]    = sum_q P[q, j] dscore/dcandidate   (written, in candidate order)
+ * with the chunk loop, the workspace layout and the `cols` arithmetic of bess_neg_score_shared_bwd_softmax; per
+ * chunk one kernel (one wave per row) writes the dense part of P and then rewrites the row's labelled columns of the
+ * chunk.  coef[q] == 0 gives exact zeros.  Workspaces 16-B aligned; the _workspace queries are host arithmetic. */
+int64_t bess_neg_score_shared_fwd_bce_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg);
+int bess_neg_score_shared_fwd_bce(const bess_model_desc* d, const float* query, int64_t n_query,
+                                  const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* state_ab,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+int bess_label_score_sums(const bess_model_desc* d, const float* query, int64_t n_query, const void* neg_base,
+                          const int32_t* neg_idx, int64_t n_neg, const int64_t* label_ptr,
+                          const int32_t* label_col, float* out, void* stream);
+int64_t bess_neg_score_shared_bwd_bce_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg);
+int bess_neg_score_shared_bwd_bce(const bess_model_desc* d, const float* query, int64_t n_query,
+                                  const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float smooth,
+                                  float pw, const int64_t* label_ptr, const int32_t* label_col, const float* coef,
+                                  float* d_query, float* d_neg, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
 /* Single (query, candidate) scores in the arithmetic of the all-entity pass: out[i] = score(query[i], row
  * neg_idx[i] of neg_base) exactly as bess_neg_score_shared_fwd_counts / _fwd_ws computes that element inside a
  * (like_n_query x like_n_neg) problem - the same kernel run on the diagonal tiles of the (pairs x pairs) problem
