@@ -251,6 +251,10 @@ SIGNATURES = {
                                    ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_i64), _vp],
     "bess_neg_score_shared_fwd_loss": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.POINTER(KillDesc), _LD, _vp, _vp, _i64,
                                        _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp],
+    "bess_tucker_query_workspace": [_i64, _i64, _i64, ctypes.POINTER(_i64)],
+    "bess_tucker_query_fwd": [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp],
+    "bess_tucker_query_bwd": [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64,
+                              _vp, _i64, _vp],
 }
 COMM_ID_BYTES = 128
 AFFINE_COUNT_CHUNK_BYTES = 32 << 20  # BESS_AFFINE_COUNT_CHUNK_BYTES
@@ -701,6 +705,47 @@ def query_bwd(d: ModelDesc, side: int, ent: RowSource, rel_table: torch.Tensor, 
     _launch("bess_query_bwd", dev, ctypes.byref(d), side, ent.base.data_ptr(), _idx(ent.idx, "entity idx"),
             rel_table.data_ptr(), rel_idx.data_ptr(), n, d_query.data_ptr(), dx.data_ptr(), d_rel_table.data_ptr())
     return dx
+
+
+def _tucker_operands(who: str, x: torch.Tensor, rel: torch.Tensor, core: torch.Tensor,
+                     dq: Optional[torch.Tensor] = None) -> Tuple[torch.device, int, int, int]:
+    """(device, S, de, dr) of TuckER's query product: x [S, de], rel [S, dr], core [dr * de, de] (and dq [S, de])."""
+    named = [("x", x), ("rel", rel), ("core", core)] + ([("dq", dq)] if dq is not None else [])
+    dev = _same_device(named)
+    _f32s(*named)
+    if x.dim() != 2 or rel.dim() != 2 or core.dim() != 2 or rel.shape[0] != x.shape[0]:
+        raise ValueError(f"{who}: x [S, de], rel [S, dr] and core [dr * de, de] must be 2-D with the same S")
+    S, de, dr = int(x.shape[0]), int(x.shape[1]), int(rel.shape[1])
+    if tuple(core.shape) != (dr * de, de) or (dq is not None and dq.shape != x.shape):
+        raise ValueError(f"{who}: core must be [dr * de, de] = [{dr * de}, {de}] and dq like x, got {tuple(core.shape)}")
+    return dev, S, de, dr
+
+
+def tucker_query_fwd(x: torch.Tensor, rel: torch.Tensor, core: torch.Tensor, swap_axes: bool) -> torch.Tensor:
+    """q [S, de] = sum_{k, a} rel[:, k] x[:, a] W[k, a, :] (`swap_axes`: W[k, :, a], the head-corruption query) for
+    the core stored as [dr * de, de] rows (k, a) (`bess_tucker_query_fwd`); exact fp32 on the matrix cores."""
+    dev, S, de, dr = _tucker_operands("tucker_query_fwd", x, rel, core)
+    q = torch.empty((S, de), dtype=torch.float32, device=dev)
+    if S:
+        _launch("bess_tucker_query_fwd", dev, x.data_ptr(), de, rel.data_ptr(), dr, core.data_ptr(), int(bool(swap_axes)),
+                q.data_ptr(), de, S, de, dr, 0, 0)
+    return q
+
+
+def tucker_query_bwd(x: torch.Tensor, rel: torch.Tensor, core: torch.Tensor, swap_axes: bool, dq: torch.Tensor,
+                     want: Sequence[bool] = (True, True, True)
+                     ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(d_x [S, de], d_rel [S, dr], d_core [dr * de, de]) of `tucker_query_fwd` for dq [S, de]; None where `want`
+    is False (that product is not computed).  Bitwise reproducible: no atomics (`bess_tucker_query_bwd`)."""
+    dev, S, de, dr = _tucker_operands("tucker_query_bwd", x, rel, core, dq)
+    d_x, d_rel, d_core = (torch.empty_like(t) if w else None for t, w in zip((x, rel, core), want))
+    nbytes = ctypes.c_int64(0)
+    _check(load().bess_tucker_query_workspace(S, de, dr, ctypes.byref(nbytes)), "bess_tucker_query_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if d_rel is not None and nbytes.value else None
+    _launch("bess_tucker_query_bwd", dev, x.data_ptr(), de, rel.data_ptr(), dr, core.data_ptr(), int(bool(swap_axes)),
+            dq.data_ptr(), de, _ptr(d_x), de, _ptr(d_rel), dr, _ptr(d_core), S, de, dr, _ptr(ws),
+            nbytes.value if ws is not None else 0)
+    return d_x, d_rel, d_core
 
 
 def query_width(d: ModelDesc) -> int:

@@ -152,6 +152,27 @@ class ReduceNegatives(torch.autograd.Function):
         return None, None, dq, dn.reshape(ctx.neg_shape).to(rows.dtype)
 
 
+class TuckerQuery(torch.autograd.Function):
+    """TuckER's query product `(x [S, de], rel_rows [S, dr], core [dr * de, de], swap_axes) -> q [S, de]`
+    (`nat.tucker_query_fwd`); the backward gives the three gradients it is asked for.  No double backward."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, rel_rows: torch.Tensor, core: torch.Tensor,  # type: ignore
+                swap_axes: bool) -> torch.Tensor:
+        x32, r32, c32 = (t.detach().float().contiguous() for t in (x, rel_rows, core))
+        ctx.swap = bool(swap_axes)
+        ctx.save_for_backward(x32, r32, c32)
+        ctx.dtypes = (x.dtype, rel_rows.dtype, core.dtype)
+        return nat.tucker_query_fwd(x32, r32, c32, ctx.swap)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx: Any, dq: torch.Tensor):  # type: ignore
+        x, rel_rows, core = ctx.saved_tensors
+        grads = nat.tucker_query_bwd(x, rel_rows, core, ctx.swap, dq.float().contiguous(), ctx.needs_input_grad[:3])
+        return tuple(None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)) + (None,)
+
+
 class Loss(torch.autograd.Function):
     """K8 fused loss + score gradients (`logq`: the sampled softmax's per-candidate log-proposals, see
     `nat.loss_fwd_bwd`)."""

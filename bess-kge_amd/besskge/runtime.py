@@ -226,6 +226,9 @@ def place_shards(model: BessKGE, group: ReplicaGroup, device: torch.device,
     # whatever else the scorer owns (ConvE's query network, offset buffers): replicated on the device
     for child in fn.children():
         child.to(device)
+    for name, prm in fn.named_parameters(recurse=False):  # (TuckER's core)
+        if name not in ("entity_embedding", "relation_embedding"):
+            prm.data = prm.data.to(device)
     for name, buf in list(fn.named_buffers(recurse=False)):
         setattr(fn, name, buf.to(device))
     model.attach(group, {s: i for i, s in enumerate(group.local_shards)})

@@ -929,6 +929,93 @@ class ConvE(_TorchQueryHooks, MatrixDecompositionScoreFunction):
                                          self._table_dtype(tail_emb))
 
 
+def init_core_uniform(core: torch.Tensor) -> torch.Tensor:
+    """U(-1, 1): the initialisation of TuckER's core tensor in Balazevic et al. 2019."""
+    return torch.nn.init.uniform_(core, -1.0, 1.0)
+
+
+class TuckER(_TorchQueryHooks, MatrixDecompositionScoreFunction):
+    """TuckER (Balazevic et al. 2019): `sum_{k,a,b} r_k h_a W[k, a, b] t_b` with a dense core tensor shared by all
+    relations.  Entity rows are `entity_embedding_size` (de) wide, relation rows `relation_embedding_size` (dr).
+
+    The core is the parameter `core [dr * de, de]`, fp32: row (k, a), column b hold W[k, a, b] (relation, head,
+    tail) - the right operand of the product `q = (r (x) x) core` that `csrc/tucker.hip` runs on the matrix cores
+    (`ops.TuckerQuery`) without forming `r @ W` per triple.  Against the candidates the score is the dot product
+    `<q, e>`: the DistMult kernels, as for ConvE.  Both corruption sides are served (heads: the same kernels read the
+    core with its two entity axes exchanged).
+
+    The query chain is the paper's: batch-norm and dropout on the kept entity rows, the core product, batch-norm and
+    dropout on the query.  The paper's third dropout acts on the mixed `[de, de]` matrix `r @ W` of every triple;
+    that matrix is never formed here, so that dropout is left out."""
+
+    _scorer_id = nat.DISTMULT  # candidates see a dot product with the query
+    supports_fused_segments = True  # ... so their K9 is the dot-product segmented reduction
+
+    def __init__(
+        self,
+        negative_sample_sharing: bool,
+        sharding: Sharding,
+        n_relation_type: int,
+        entity_embedding_size: int,
+        relation_embedding_size: int,
+        entity_initializer: _Init = [init_xavier_norm],
+        relation_initializer: _Init = [init_xavier_norm],
+        core_initializer: Callable[[torch.Tensor], torch.Tensor] = init_core_uniform,
+        inverse_relations: bool = False,
+        input_dropout: float = 0.0,
+        hidden_dropout: float = 0.0,
+        batch_normalization: bool = False,
+        **placement: Any,
+    ) -> None:
+        super().__init__(negative_sample_sharing)
+        self._allocate(
+            sharding, n_relation_type, inverse_relations, entity_initializer,
+            relation_initializer, entity_embedding_size, relation_embedding_size,
+            "TuckER requires `entity_embedding_size` embedding parameters for each entity"
+            " and `relation_embedding_size` for each relation",
+            placement=placement,
+        )
+        de, dr = int(entity_embedding_size), int(relation_embedding_size)
+        self.entity_embedding_size, self.relation_embedding_size = de, dr
+        core = torch.empty((dr * de, de), dtype=torch.float32, device=_placement(placement)["device"])
+        self.core = torch.nn.Parameter(core_initializer(core))
+        norm = [torch.nn.BatchNorm1d(de)] if batch_normalization else []
+        self.input_layers = torch.nn.Sequential(*norm, torch.nn.Dropout(input_dropout))
+        norm = [torch.nn.BatchNorm1d(de)] if batch_normalization else []
+        self.hidden_layers = torch.nn.Sequential(*norm, torch.nn.Dropout(hidden_dropout))
+
+    def kernel_desc(self) -> nat.ModelDesc:
+        d = super().kernel_desc()
+        d.rel_width = d.width  # the dot-product kernels only see entity rows and queries
+        return d
+
+    def dense_parameters(self) -> List[torch.nn.Parameter]:
+        return [self.core] + list(self.input_layers.parameters()) + list(self.hidden_layers.parameters())
+
+    def _query_torch(self, side: int, rows: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
+        r = torch.index_select(rel, 0, rel_idx.reshape(-1).long()).float()
+        q = ops.TuckerQuery.apply(self.input_layers(rows.float()), r, self.core, side == nat.CORRUPT_HEAD)
+        return self.hidden_layers(q)
+
+    def _triple_torch(self, h: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        return torch.sum(self._query_torch(nat.CORRUPT_TAIL, h, rel, rel_idx) * t.float(), dim=-1)
+
+    def score_triple(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._triple_torch(head_emb, self.relation_embedding, relation_id, tail_emb)
+
+    def _score_candidates(self, side: int, kept: torch.Tensor, relation_id: torch.Tensor,
+                          candidates: torch.Tensor) -> torch.Tensor:
+        q = self._query_torch(side, kept, self.relation_embedding, relation_id)
+        return ops.ReduceNegatives.apply(self.kernel_desc(), bool(self.negative_sample_sharing), q.contiguous(),
+                                         self._table_dtype(candidates))
+
+    def score_heads(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_HEAD, tail_emb, relation_id, head_emb)
+
+    def score_tails(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_TAIL, head_emb, relation_id, tail_emb)
+
+
 class BoxE(_TorchQueryHooks, DistanceBasedScoreFunction):
     """BoxE (reference scoring.py:1149-1415): entities are [base | bump]; the head is
     bumped by the tail's bump and vice versa, and each bumped point is scored by a

@@ -138,6 +138,8 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_allgather),
     BESS_PLAN_FN(bess_allreduce_sum_f32),
     BESS_PLAN_FN(bess_pack_exchange),
+    BESS_PLAN_FN(bess_tucker_query_fwd),
+    BESS_PLAN_FN(bess_tucker_query_bwd),
 };
 #undef BESS_PLAN_FN
 

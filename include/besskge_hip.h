@@ -1148,6 +1148,30 @@ int bess_plan_add_call(bess_plan* plan, const char* name, int32_t n_args, const 
                        const uint64_t* values, const void* const* blobs, const int64_t* blob_bytes);
 int bess_plan_run(const bess_plan* plan, void* stream);
 
+/* ---- TuckER: the core-tensor query product (csrc/tucker.hip) ---------------------
+ * The core is a dense fp32 parameter stored as a GEMM's right operand: core [dr * de, de], row (k, a), column b =
+ * W[k, a, b] (relation, head, tail).  With x [S, de] the entity rows kept in the triples and rel [S, dr] their
+ * relation rows (already gathered), all contiguous fp32 with leading dimensions in elements:
+ *   swap_axes == 0 (tail corruption, x = heads):  q[i, b] = sum_{k, a} rel[i, k] x[i, a] W[k, a, b]
+ *   swap_axes == 1 (head corruption, x = tails):  q[i, a] = sum_{k, b} rel[i, k] x[i, b] W[k, a, b]
+ * Candidates are then scored with the dot-product kernels (BESS_DISTMULT with an identity query).  Exact fp32
+ * products with fp32 accumulation on the matrix cores; neither [S, de, de] nor [S, dr * de] is ever formed.
+ * bess_tucker_query_bwd writes (overwrites) the gradients of its three operands for dq [S, de]; each of d_x [S, de],
+ * d_rel [S, dr] and d_core [dr * de, de] may be NULL to skip its product.  No float atomics: every output is
+ * bitwise reproducible.  d_rel goes through partial sums in the workspace: bess_tucker_query_workspace bytes =
+ * 8 * ceil(de / 64) * S * dr (16-byte aligned; bess_tucker_query_fwd needs none and ignores its workspace).
+ * Any S >= 0 (< 2^22), dr >= 1 (<= 65535), 1 <= de <= 544: the 64 x de tile of the rows stays in LDS, a wider
+ * de is refused with BESS_EUNSUPPORTED.  Widths, leading dimensions or pointers that are not multiples of 4 floats
+ * take scalar loads. */
+int bess_tucker_query_workspace(int64_t S, int64_t de, int64_t dr, int64_t* bytes);
+int bess_tucker_query_fwd(const float* x, int64_t ldx, const float* rel, int64_t ldr, const float* core,
+                          int32_t swap_axes, float* q, int64_t ldq, int64_t S, int64_t de, int64_t dr,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int bess_tucker_query_bwd(const float* x, int64_t ldx, const float* rel, int64_t ldr, const float* core,
+                          int32_t swap_axes, const float* dq, int64_t lddq, float* d_x, int64_t ld_dx,
+                          float* d_rel, int64_t ld_drel, float* d_core, int64_t S, int64_t de, int64_t dr,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- recorded steps -----------------------------------------------------------
  * A step of this library can be captured into a hipGraph as a whole (every call is asynchronous on the
  * caller's stream, every clear is a kernel).  bess_graph_node_counts tells what a captured graph holds:
