@@ -255,6 +255,10 @@ SIGNATURES = {
     "bess_tucker_query_fwd": [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp],
     "bess_tucker_query_bwd": [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64,
                               _vp, _i64, _vp],
+    "bess_relation_query_workspace": [_i64, _i64, _i64, ctypes.POINTER(_i64)],
+    "bess_relation_query_fwd": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],
+    "bess_relation_query_bwd": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64,
+                                _vp, _i64, _vp, _i64, _vp],
 }
 COMM_ID_BYTES = 128
 AFFINE_COUNT_CHUNK_BYTES = 32 << 20  # BESS_AFFINE_COUNT_CHUNK_BYTES
@@ -420,6 +424,16 @@ def _f32(t: torch.Tensor, name: str) -> None:
 def _f32s(*named: Tuple[str, torch.Tensor]) -> None:
     for name, t in named:
         _f32(t, name)
+
+
+def _f32_ld(t: torch.Tensor, name: str, shape: Tuple[int, int]) -> int:
+    """Leading dimension, in elements, of the float32 matrix `t` of `shape` whose rows are contiguous (a view of the
+    leading columns of a wider buffer is fine)."""
+    if t.dtype != torch.float32 or tuple(t.shape) != shape or (shape[1] > 1 and t.stride(1) != 1) \
+            or (shape[0] > 1 and t.stride(0) < shape[1]):
+        raise ValueError(f"`{name}` must be a float32 {list(shape)} matrix with contiguous rows, got {t.dtype} "
+                         f"{tuple(t.shape)} stride {t.stride()}")
+    return int(t.stride(0)) if shape[0] > 1 else shape[1]
 
 
 def _ptr(t: Optional[torch.Tensor]) -> int:
@@ -746,6 +760,57 @@ def tucker_query_bwd(x: torch.Tensor, rel: torch.Tensor, core: torch.Tensor, swa
             dq.data_ptr(), de, _ptr(d_x), de, _ptr(d_rel), dr, _ptr(d_core), S, de, dr, _ptr(ws),
             nbytes.value if ws is not None else 0)
     return d_x, d_rel, d_core
+
+
+def _relation_query_call(who: str, x: torch.Tensor, M: torch.Tensor, seg: "SegmentIndex",
+                         more: Sequence[Tuple[str, Optional[torch.Tensor]]]) -> Tuple[torch.device, List[Any], List[int]]:
+    """(device, the leading arguments x .. n_rel of both entry points, the (pointer, ld) pairs of `more` - [S, de] like
+    x, or [n_rel, de * de] like M when named "d_M"; (0, 0) for None) and the workspace arguments are appended by
+    `_relation_query_workspace`."""
+    dev = _same_device([("x", x), ("M", M), ("refs", seg.refs)] + list(more))
+    if x.dim() != 2 or M.dim() != 2 or M.shape[1] != x.shape[1] ** 2 or seg.n_refs != x.shape[0]:
+        raise ValueError(f"{who}: x [S, de], M [n_rel, de * de] and an index of S relation ids, got "
+                         f"{tuple(x.shape)}, {tuple(M.shape)} and {seg.n_refs} ids")
+    S, de, n_rel = int(x.shape[0]), int(x.shape[1]), int(M.shape[0])
+    args = [x.data_ptr(), _f32_ld(x, "x", (S, de)), M.data_ptr(), _f32_ld(M, "M", (n_rel, de * de)), None,
+            seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr(), S, de, n_rel]
+    rest: List[int] = []
+    for name, t in more:
+        shape = (n_rel, de * de) if name == "d_M" else (S, de)
+        rest += [0, shape[1]] if t is None else [t.data_ptr(), _f32_ld(t, name, shape)]
+    nbytes = ctypes.c_int64(0)
+    _check(load().bess_relation_query_workspace(S, de, n_rel, ctypes.byref(nbytes)), "bess_relation_query_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)  # (kept alive by the stream-ordered allocator)
+    return dev, args, rest + [ws.data_ptr(), nbytes.value]
+
+
+def relation_query_fwd(x: torch.Tensor, M: torch.Tensor, seg: "SegmentIndex", swap_axes: bool,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q [S, de]: row i of x times the de x de matrix (row-major in M [n_rel, de * de], head axis first) of the
+    relation of triple i - `q[i] = x[i] @ M_r`, with `swap_axes` `M_r @ x[i]` (the head-corruption query).  `seg` is
+    the `SegmentIndex` of the S relation ids (all in [0, n_rel)).  Exact fp32 on the matrix cores
+    (`bess_relation_query_fwd`); matrices may be views with padded rows, `out` a preallocated q."""
+    q = torch.empty(x.shape, dtype=torch.float32, device=x.device) if out is None else out
+    dev, args, rest = _relation_query_call("relation_query_fwd", x, M, seg, [("q", q)])
+    args[4] = int(bool(swap_axes))
+    if x.shape[0]:
+        _launch("bess_relation_query_fwd", dev, *args, *rest)
+    return q
+
+
+def relation_query_bwd(x: torch.Tensor, M: torch.Tensor, seg: "SegmentIndex", swap_axes: bool, dq: torch.Tensor,
+                       want: Sequence[bool] = (True, True),
+                       out: Sequence[Optional[torch.Tensor]] = (None, None)
+                       ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(d_x [S, de], d_M [n_rel, de * de]) of `relation_query_fwd` for dq [S, de]; None where `want` is False (that
+    product is not computed).  d_M is dense: zero rows for relations the batch does not name.  Bitwise reproducible:
+    no atomics (`bess_relation_query_bwd`).  `out`: preallocated outputs."""
+    d_x, d_M = ((torch.empty(t.shape, dtype=torch.float32, device=t.device) if o is None else o) if w else None
+                for t, w, o in zip((x, M), want, out))
+    dev, args, rest = _relation_query_call("relation_query_bwd", x, M, seg, [("dq", dq), ("d_x", d_x), ("d_M", d_M)])
+    args[4] = int(bool(swap_axes))
+    _launch("bess_relation_query_bwd", dev, *args, *rest)
+    return d_x, d_M
 
 
 def query_width(d: ModelDesc) -> int:

@@ -44,7 +44,7 @@ from besskge.bess import BessKGE, _Batch, _PendingUpdate, _ReplicaStep, _ShardGr
 from besskge.loss import BaseLossFunction, SampledSoftmaxCrossEntropyLoss
 from besskge.negative_sampler import PlaceholderNegativeSampler, ShardedNegativeSampler
 from besskge.regularizer import EmbeddingRegularizer
-from besskge.scoring import BaseScoreFunction, ComplEx, DistMult, RotatE, TransE, TuckER
+from besskge.scoring import RESCAL, BaseScoreFunction, ComplEx, DistMult, RotatE, TransE, TuckER
 
 
 class OneVsAllBessKGE(BessKGE):
@@ -61,7 +61,7 @@ class OneVsAllBessKGE(BessKGE):
     ) -> None:
         """
         :param negative_sampler: `PlaceholderNegativeSampler("h" | "t")` (nothing is sampled).
-        :param score_fn: TransE, RotatE, DistMult or ComplEx; or TuckER (its query against DistMult's kernels).
+        :param score_fn: TransE, RotatE, DistMult or ComplEx; or TuckER / RESCAL (their query against DistMult's kernels).
         :param loss_fn: `SampledSoftmaxCrossEntropyLoss(n_entity=sharding.n_entity)`
             without `proposal_correction`; only its `loss_scale` enters.
         :param evaluation: must be None (ranks over all entities: `AllScoresPipeline`).
@@ -74,9 +74,9 @@ class OneVsAllBessKGE(BessKGE):
                 "h", "t"):
             raise ValueError(f'{me} takes PlaceholderNegativeSampler("h") or ("t"): every entity is a '
                              'candidate, nothing is sampled (scheme "ht" is not built)')
-        if type(score_fn) not in (TransE, RotatE, DistMult, ComplEx, TuckER):
+        if type(score_fn) not in (TransE, RotatE, DistMult, ComplEx, TuckER, RESCAL):
             raise ValueError(f"{me}: TransE, RotatE, DistMult or ComplEx "
-                             f"(the scorers of bess_neg_score_shared_fwd_lse; TuckER through DistMult's), not "
+                             f"(the scorers of bess_neg_score_shared_fwd_lse; TuckER and RESCAL through DistMult's), not "
                              f"{type(score_fn).__name__}")
         self._check_loss(loss_fn, score_fn)
         if evaluation is not None:

@@ -173,6 +173,30 @@ class TuckerQuery(torch.autograd.Function):
         return tuple(None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)) + (None,)
 
 
+class RelationQuery(torch.autograd.Function):
+    """The relation-grouped query product `(x [S, de], M [n_rel, de * de], rel_idx [S], swap_axes) -> q [S, de]`:
+    `q[i] = x[i] @ M_r` (`swap_axes`: `M_r @ x[i]`) for the row-major de x de matrix M_r of triple i's relation
+    (`nat.relation_query_fwd`).  The batch is grouped by relation once, in the forward; the backward reuses the index
+    and computes only the gradients it is asked for (d_M dense, zero for absent relations).  No double backward."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, M: torch.Tensor, rel_idx: torch.Tensor,  # type: ignore
+                swap_axes: bool) -> torch.Tensor:
+        x32, m32 = (t.detach().float().contiguous() for t in (x, M))
+        ctx.seg = nat.SegmentIndex(rel_idx.reshape(-1).to(torch.int32).contiguous(), int(M.shape[0]))
+        ctx.swap = bool(swap_axes)
+        ctx.save_for_backward(x32, m32)
+        ctx.dtypes = (x.dtype, M.dtype)
+        return nat.relation_query_fwd(x32, m32, ctx.seg, ctx.swap)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx: Any, dq: torch.Tensor):  # type: ignore
+        x, M = ctx.saved_tensors
+        grads = nat.relation_query_bwd(x, M, ctx.seg, ctx.swap, dq.float().contiguous(), ctx.needs_input_grad[:2])
+        return tuple(None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)) + (None, None)
+
+
 class Loss(torch.autograd.Function):
     """K8 fused loss + score gradients (`logq`: the sampled softmax's per-candidate log-proposals, see
     `nat.loss_fwd_bwd`)."""

@@ -946,7 +946,19 @@ class TuckER(_TorchQueryHooks, MatrixDecompositionScoreFunction):
 
     The query chain is the paper's: batch-norm and dropout on the kept entity rows, the core product, batch-norm and
     dropout on the query.  The paper's third dropout acts on the mixed `[de, de]` matrix `r @ W` of every triple;
-    that matrix is never formed here, so that dropout is left out."""
+    that matrix is never formed here, so that dropout is left out.
+
+    `query_route` chooses how the core product is computed; both give the same query up to fp32 rounding:
+
+    * `"outer"` (default): `ops.TuckerQuery`, `2 S dr de^2` FLOP per product - every triple is treated as having its
+      own relation vector.  Nothing is held besides the operands.  Choose it when relations outnumber the batch, or
+      when dr is small (at dr = 30 it is the faster one whatever the relation count).
+    * `"relation"`: the mixed matrices `M = relation_embedding @ core.view(dr, de * de)` of ALL relations are formed
+      once per query (`torch.matmul`), then every row is multiplied by the matrix of its own relation
+      (`ops.RelationQuery`, csrc/relation_query.hip): `2 n_rel dr de^2 + 2 S de^2` FLOP.  Choose it when the relation
+      count is well below the batch size S and dr is large (the paper's de = dr = 200 with a few hundred relations).
+      It holds two `[n_rel, de * de]` fp32 buffers (M and, in training, its gradient), and loses when relations
+      outnumber the batch."""
 
     _scorer_id = nat.DISTMULT  # candidates see a dot product with the query
     supports_fused_segments = True  # ... so their K9 is the dot-product segmented reduction
@@ -965,9 +977,13 @@ class TuckER(_TorchQueryHooks, MatrixDecompositionScoreFunction):
         input_dropout: float = 0.0,
         hidden_dropout: float = 0.0,
         batch_normalization: bool = False,
+        query_route: str = "outer",
         **placement: Any,
     ) -> None:
         super().__init__(negative_sample_sharing)
+        if query_route not in ("outer", "relation"):
+            raise ValueError(f'TuckER: query_route is "outer" or "relation", got {query_route!r}')
+        self.query_route = query_route
         self._allocate(
             sharding, n_relation_type, inverse_relations, entity_initializer,
             relation_initializer, entity_embedding_size, relation_embedding_size,
@@ -993,9 +1009,79 @@ class TuckER(_TorchQueryHooks, MatrixDecompositionScoreFunction):
         return [self.core] + list(self.input_layers.parameters()) + list(self.hidden_layers.parameters())
 
     def _query_torch(self, side: int, rows: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
+        x, swap = self.input_layers(rows.float()), side == nat.CORRUPT_HEAD
+        if self.query_route == "relation":
+            de = self.entity_embedding_size
+            mixed = torch.matmul(rel.float(), self.core.view(self.relation_embedding_size, de * de))
+            return self.hidden_layers(ops.RelationQuery.apply(x, mixed, rel_idx, swap))
         r = torch.index_select(rel, 0, rel_idx.reshape(-1).long()).float()
-        q = ops.TuckerQuery.apply(self.input_layers(rows.float()), r, self.core, side == nat.CORRUPT_HEAD)
+        q = ops.TuckerQuery.apply(x, r, self.core, swap)
         return self.hidden_layers(q)
+
+    def _triple_torch(self, h: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        return torch.sum(self._query_torch(nat.CORRUPT_TAIL, h, rel, rel_idx) * t.float(), dim=-1)
+
+    def score_triple(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._triple_torch(head_emb, self.relation_embedding, relation_id, tail_emb)
+
+    def _score_candidates(self, side: int, kept: torch.Tensor, relation_id: torch.Tensor,
+                          candidates: torch.Tensor) -> torch.Tensor:
+        q = self._query_torch(side, kept, self.relation_embedding, relation_id)
+        return ops.ReduceNegatives.apply(self.kernel_desc(), bool(self.negative_sample_sharing), q.contiguous(),
+                                         self._table_dtype(candidates))
+
+    def score_heads(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_HEAD, tail_emb, relation_id, head_emb)
+
+    def score_tails(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_TAIL, head_emb, relation_id, tail_emb)
+
+
+class RESCAL(_TorchQueryHooks, MatrixDecompositionScoreFunction):
+    """RESCAL (Nickel et al. 2011): `h^T M_r t` with a full matrix per relation - the bilinear model that DistMult
+    (diagonal M_r), ComplEx and TuckER (M_r mixed from a shared core) restrict.  Entity rows are `embedding_size` (de)
+    wide; relation rows are de * de wide and hold M_r row-major, head axis first.
+
+    The query `q = h^T M_r` (tails as candidates) or `M_r t` (heads) is the relation-grouped product of
+    csrc/relation_query.hip on the relation table itself (`ops.RelationQuery`): the batch is grouped by relation and
+    every group is multiplied by its one matrix on the matrix cores; no `[S, de, de]` gather of the table is made.
+    Against the candidates the score is the dot product `<q, e>`: the DistMult kernels, as for ConvE and TuckER.
+    The relation-table gradient is dense (`[n_relation, de * de]`, zero for relations a batch does not name)."""
+
+    _scorer_id = nat.DISTMULT  # candidates see a dot product with the query
+    supports_fused_segments = True  # ... so their K9 is the dot-product segmented reduction
+
+    def __init__(
+        self,
+        negative_sample_sharing: bool,
+        sharding: Sharding,
+        n_relation_type: int,
+        embedding_size: int,
+        entity_initializer: _Init = [init_xavier_norm],
+        relation_initializer: _Init = [init_xavier_norm],
+        inverse_relations: bool = False,
+        **placement: Any,
+    ) -> None:
+        super().__init__(negative_sample_sharing)
+        de = int(embedding_size)
+        if de < 1 or de != embedding_size:
+            raise ValueError(f"RESCAL: embedding_size is a positive integer, got {embedding_size!r}")
+        self._allocate(
+            sharding, n_relation_type, inverse_relations, entity_initializer,
+            relation_initializer, de, de * de,
+            "RESCAL requires `embedding_size` embedding parameters for each entity"
+            " and `embedding_size ** 2` for each relation",
+            placement=placement,
+        )
+        self.embedding_size = de
+
+    def kernel_desc(self) -> nat.ModelDesc:
+        d = super().kernel_desc()
+        d.rel_width = d.width  # the dot-product kernels only see entity rows and queries
+        return d
+
+    def _query_torch(self, side: int, rows: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
+        return ops.RelationQuery.apply(rows.float(), rel, rel_idx, side == nat.CORRUPT_HEAD)
 
     def _triple_torch(self, h: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         return torch.sum(self._query_torch(nat.CORRUPT_TAIL, h, rel, rel_idx) * t.float(), dim=-1)

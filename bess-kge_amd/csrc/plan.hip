@@ -140,6 +140,8 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_pack_exchange),
     BESS_PLAN_FN(bess_tucker_query_fwd),
     BESS_PLAN_FN(bess_tucker_query_bwd),
+    BESS_PLAN_FN(bess_relation_query_fwd),
+    BESS_PLAN_FN(bess_relation_query_bwd),
 };
 #undef BESS_PLAN_FN
 

@@ -18,117 +18,23 @@
 //   k_tucker_bwd_core  d_core[(k, a), b] = sum_m rel[m, k] u[m, a] v[m, b], (u, v) = (x, dq) or, with exchanged axes,
 //                      (dq, x): one 64 x 64 tile of one k per workgroup, reduction over the rows
 //
-// Conventions are gemm_mfma.hip's: 256 threads = 4 waves of one 32 x 32 MFMA tile each on a 64 x 64 output tile,
-// reduction staged through LDS in slices of 32 as [k][m] / [k][n] images (a fragment read is one ds_read_b32 per
-// lane), odd stride 65 for transposing stores and 68 for direct 16-byte stores, global -> register -> LDS staging
-// split around the MFMA phase.  Only 64-tiles: the product has de output columns, so 128-tiles would give
+// Conventions are gemm_mfma.hip's (the tile, its LDS images and their staging helpers: mfma_tile.h), global -> register
+// -> LDS staging split around the MFMA phase.  Only 64-tiles: the product has de output columns, so 128-tiles would give
 // ceil(S / 128) * ceil(de / 128) workgroups - 64 at S = 4096, de = 200, a quarter of the chip.
 // No atomics anywhere: every output element is written once, by one lane, in a fixed order of summation.
 #include <atomic>
 
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace bess {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int TK = 32;         // reduction slice
-constexpr int TT = 64;         // edge of the output tile
-constexpr int LD_T = TT + 1;   // [k][m] image written by transposing stores
-constexpr int LD_D = TT + 4;   // [k][m] image written by direct 16-byte stores
-constexpr int B_IMG = TK * LD_D;                  // floats of one slice image (either stride)
 constexpr int64_t LDS_LIMIT = 160 * 1024;         // per workgroup on gfx950
 constexpr int TUCKER_MAX_DE = 544;                // 17 slices of the resident x image beside the core's two buffers
 
 inline int64_t rows_lds_bytes(int64_t de) { return (2 * B_IMG + ceil_div(de, TK) * TK * LD_T) * 4; }
 static_assert((2 * B_IMG + (TUCKER_MAX_DE / TK) * TK * LD_T) * 4 <= LDS_LIMIT, "the x image of TUCKER_MAX_DE must fit");
-
-// row[c .. c + 3], zeros where the row is not live or the column is at or past c_end.  `row` is a valid row in either
-// case.  VEC4 (c_end % 4 == 0, c_end >= 4, 16-byte aligned rows): one unconditional 16-byte load at a clamped address,
-// then selects - no branch that would make the loads of a slice wait for one another.
-template <bool VEC4>
-__device__ __forceinline__ void load4(const float* __restrict__ row, int64_t c, int64_t c_end, bool live, float (&v)[4]) {
-    if (VEC4) {
-        const float4 t = *reinterpret_cast<const float4*>(row + min(c, c_end - 4));
-        live = live && c < c_end;
-        v[0] = live ? t.x : 0.f;
-        v[1] = live ? t.y : 0.f;
-        v[2] = live ? t.z : 0.f;
-        v[3] = live ? t.w : 0.f;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (live && c + i < c_end) ? row[c + i] : 0.f;
-    }
-}
-
-// One thread's share of a 32 x 64 slice whose rows are the reduction index (contiguous along the tile's 64 columns):
-// rows p * 16 + t / 16, columns (t % 16) * 4 .. + 3; stored with one 16-byte store per pass.
-__device__ __forceinline__ void store_direct(float* img, const float (&v)[2][4]) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-        *reinterpret_cast<float4*>(&img[(p * 16 + (t >> 4)) * LD_D + (t & 15) * 4]) =
-            make_float4(v[p][0], v[p][1], v[p][2], v[p][3]);
-}
-// ... and of a 64 x 32 slice whose rows are the tile's 64 columns (contiguous along the reduction index):
-// rows p * 32 + t / 8, reduction entries (t % 8) * 4 .. + 3; stored transposed.
-__device__ __forceinline__ void store_transposed(float* img, const float (&v)[2][4]) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) img[((t & 7) * 4 + i) * LD_T + p * 32 + (t >> 3)] = v[p][i];
-}
-
-// Slice (k, j0 .. j0 + 32) x (n0 .. n0 + 64) of B_k, through registers into a [j][n] image.
-template <bool SWAP, bool VEC4>
-struct CoreSlice {
-    static constexpr int LD = SWAP ? LD_T : LD_D;
-    float v[2][4];
-    __device__ __forceinline__ void load(const float* __restrict__ core, int64_t de, int64_t k, int64_t j0, int64_t n0) {
-        const int t = threadIdx.x;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            // the core's row (k, r) and the first of four columns: (j, n ..) as stored, (n, j ..) with exchanged axes
-            const int64_t r = SWAP ? n0 + p * 32 + (t >> 3) : j0 + p * 16 + (t >> 4);
-            const int64_t c = SWAP ? j0 + (t & 7) * 4 : n0 + (t & 15) * 4;
-            load4<VEC4>(core + (k * de + min(r, de - 1)) * de, c, de, r < de, v[p]);
-        }
-    }
-    __device__ __forceinline__ void store(float* img) const {
-        if (SWAP) store_transposed(img, v);
-        else store_direct(img, v);
-    }
-};
-
-// the 16 steps of one slice: acc += A(wm .., j) B(j, wn ..) from the two images; SCALE: A times `rk` on the read.
-// Fragments of step kk + 2 are read while the MFMA of step kk issues (two register sets), as in gemm_mfma.hip.
-template <int LDA, int LDB, bool SCALE>
-__device__ __forceinline__ void mfma_slice(const float* a_img, const float* b_img, f32x16& acc, int wm, int wn, int l31,
-                                           int lk, float rk) {
-    float a[2], b[2];
-    a[0] = a_img[lk * LDA + wm + l31];
-    b[0] = b_img[lk * LDB + wn + l31];
-#pragma unroll
-    for (int kk = 0; kk < TK; kk += 2) {
-        const int c = (kk >> 1) & 1;
-        if (kk + 2 < TK) {
-            a[c ^ 1] = a_img[(kk + 2 + lk) * LDA + wm + l31];
-            b[c ^ 1] = b_img[(kk + 2 + lk) * LDB + wn + l31];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(SCALE ? a[c] * rk : a[c], b[c], acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-__device__ __forceinline__ void zero_acc(f32x16& acc) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-}
-// C/D layout of the 32 x 32 MFMA: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-__device__ __forceinline__ int acc_row(int r, int lk) { return (r & 3) + 8 * (r >> 2) + 4 * lk; }
 
 struct RowsArgs {
     const float* x;     // [S, de]: the rows whose tile stays in LDS
@@ -147,7 +53,7 @@ __device__ __forceinline__ void tucker_rows(const RowsArgs& A) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* const Bs = lds;
     float* const Xs = lds + 2 * B_IMG;
-    constexpr int LDB = CoreSlice<SWAP, VEC4>::LD;
+    constexpr int LDB = MatrixSlice<SWAP, VEC4>::LD;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
     const int l31 = lane & 31, lk = lane >> 5;
@@ -165,8 +71,8 @@ __device__ __forceinline__ void tucker_rows(const RowsArgs& A) {
         }
         store_transposed(Xs + j * TK * LD_T, v);
     }
-    CoreSlice<SWAP, VEC4> cs;
-    cs.load(A.core, de, 0, 0, n0);
+    MatrixSlice<SWAP, VEC4> cs;  // of W[k]
+    cs.load(A.core, de, 0, n0);
     cs.store(Bs);
     // the lane's row of rel (clamped: the products of rows past S are never stored)
     const float* relrow = A.rel + min(m0 + wm + l31, S - 1) * A.ldr;
@@ -192,7 +98,7 @@ __device__ __forceinline__ void tucker_rows(const RowsArgs& A) {
         const int jn = j + 1 == spk ? 0 : j + 1, kn = j + 1 == spk ? k + 1 : k;
         float rk_next = rk;
         if (more) {  // issued ahead of this slice's MFMAs
-            cs.load(A.core, de, kn, static_cast<int64_t>(jn) * TK, n0);
+            cs.load(A.core + kn * de * de, de, static_cast<int64_t>(jn) * TK, n0);
             if (!REL && jn == 0) rk_next = relrow[kn];
         }
         mfma_slice<LD_T, LDB, !REL>(Xs + j * TK * LD_T, Bs + cur * B_IMG, acc, wm, wn, l31, lk, rk);
@@ -304,7 +210,6 @@ __global__ __launch_bounds__(256) void k_tucker_bwd_core(const float* __restrict
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int64_t rel_parts(int64_t de) { return 2 * ceil_div(de, TT); }  // one per 32-column wave tile
 inline int64_t rel_ws_bytes(int64_t S, int64_t de, int64_t dr) { return rel_parts(de) * S * dr * 4; }
 

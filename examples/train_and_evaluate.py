@@ -8,7 +8,8 @@ queries and report filtered-free MRR / hits@10.
                                              [--loss ssce --proposal-correction]
                                              [--regularizer n3 --reg-coef 1e-3]
                                              [--training 1vsall | kvsall [--label-smoothing 0.1]]
-                                             [--scorer TuckER --relation-size 16]
+                                             [--scorer TuckER --relation-size 16 [--tucker-route relation]]
+                                             [--scorer RESCAL]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -71,8 +72,11 @@ def main(argv=None) -> dict:
     ap.add_argument("--n-triple", type=int, default=30000)
     ap.add_argument("--n-shard", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
-    ap.add_argument("--scorer", default="TransE", choices=["TransE", "RotatE", "DistMult", "ComplEx", "PairRE", "TranS", "TuckER"])
+    ap.add_argument("--scorer", default="TransE", choices=["TransE", "RotatE", "DistMult", "ComplEx", "PairRE", "TranS", "TuckER",
+                                                                "RESCAL"])
     ap.add_argument("--relation-size", type=int, default=16, help="width of the relation rows of --scorer TuckER")
+    ap.add_argument("--tucker-route", default="outer", choices=["outer", "relation"],
+                    help="TuckER's query_route: per-triple outer product, or one mixed matrix per relation")
     ap.add_argument("--embedding-size", type=int, default=32)
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--negative-weights", default="uniform", choices=["uniform", "degree"],
@@ -98,9 +102,9 @@ def main(argv=None) -> dict:
     k_vs_all = args.training == "kvsall"
     one_vs_all = args.training == "1vsall" or k_vs_all
     if one_vs_all and (args.proposal_correction or args.negative_weights != "uniform" or args.loss != "logsigmoid"
-                       or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx", "TuckER")):
+                       or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx", "TuckER", "RESCAL")):
         ap.error(f"--training {args.training} samples nothing and brings its own loss: TransE / RotatE / DistMult / ComplEx "
-                 "/ TuckER, "
+                 "/ TuckER / RESCAL, "
                  "without --negative-weights / --loss / --proposal-correction")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -116,7 +120,7 @@ def main(argv=None) -> dict:
         fn = getattr(scoring, args.scorer)(True, 1, sharding, args.n_relation, d)
     elif args.scorer == "TuckER":  # (the paper's recipe: --training kvsall --label-smoothing 0.1)
         fn = scoring.TuckER(True, sharding, args.n_relation, d, args.relation_size, batch_normalization=True,
-                            input_dropout=0.2, hidden_dropout=0.2)
+                            input_dropout=0.2, hidden_dropout=0.2, query_route=args.tucker_route)
     else:
         fn = getattr(scoring, args.scorer)(True, sharding, args.n_relation, d)
 

@@ -1172,6 +1172,38 @@ int bess_tucker_query_bwd(const float* x, int64_t ldx, const float* rel, int64_t
                           float* d_rel, int64_t ld_drel, float* d_core, int64_t S, int64_t de, int64_t dr,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the relation-grouped query product (csrc/relation_query.hip) -----------------
+ * A grouped GEMM in which every row of x is multiplied by the matrix of its own relation.  x [S, de] and dq [S, de]
+ * are fp32 rows in batch order; M [n_rel, de * de] holds one row-major matrix per relation, M_r[a, b] with a the head
+ * axis and b the tail axis (RESCAL's relation table; TuckER's rel_table @ core).  Leading dimensions in elements.
+ *   swap_axes == 0 (tail corruption, x = heads):  q[i, b] = sum_a x[i, a] M_{rel[i]}[a, b]
+ *   swap_axes == 1 (head corruption, x = tails):  q[i, a] = sum_b x[i, b] M_{rel[i]}[a, b]
+ *   d_x[i, :]   = the other of the two products, applied to dq
+ *   d_M[r][a, b] = sum_{i : rel[i] = r} u[i, a] v[i, b], (u, v) = (x, dq), with swap_axes (dq, x); rows of d_M of
+ *                  relations that the batch does not name are zero
+ * The relation ids do not enter as a list but grouped: (refs_sorted, seg_rows, seg_offsets, n_seg) as
+ * bess_build_segment_index builds them from the S ids rel[i], all in [0, n_rel) - an id outside is an out-of-bounds
+ * read of M.  *n_seg is read on the device only; nothing synchronises.  Candidates are then scored with the
+ * dot-product kernels (BESS_DISTMULT with an identity query).
+ * Exact fp32 products with fp32 accumulation on the matrix cores; no [S, de, de] tensor, no transposed copy of M, no
+ * float atomics: every output is bitwise reproducible.  bess_relation_query_bwd overwrites its outputs (it clears
+ * d_M itself, also when S == 0); d_x or d_M may be NULL to skip that product, the other is what it would have been.
+ * workspace: bess_relation_query_workspace bytes (the row-tile plan: 16 bytes per tile of at most 64 rows of one
+ * relation, at most ceil(S / 64) + min(S, n_rel) of them, and one word per segment), 16-byte aligned, written by every
+ * call that needs it (the forward; the backward for d_x) - nothing to clear, nothing kept between calls.
+ * Any S >= 0 (< 2^22), 1 <= de <= 32768 (both operands stream: no resident tile limits the width), n_rel >= 1.
+ * Widths, leading dimensions or pointers that are not multiples of 4 floats take scalar loads. */
+int bess_relation_query_workspace(int64_t S, int64_t de, int64_t n_rel, int64_t* bytes);
+int bess_relation_query_fwd(const float* x, int64_t ldx, const float* M, int64_t ldm, int32_t swap_axes,
+                            const int32_t* refs_sorted, const int32_t* seg_rows, const int32_t* seg_offsets,
+                            const int32_t* n_seg, int64_t S, int64_t de, int64_t n_rel, float* q, int64_t ldq,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int bess_relation_query_bwd(const float* x, int64_t ldx, const float* M, int64_t ldm, int32_t swap_axes,
+                            const int32_t* refs_sorted, const int32_t* seg_rows, const int32_t* seg_offsets,
+                            const int32_t* n_seg, int64_t S, int64_t de, int64_t n_rel, const float* dq, int64_t lddq,
+                            float* d_x, int64_t ld_dx, float* d_M, int64_t lddm, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* ---- recorded steps -----------------------------------------------------------
  * A step of this library can be captured into a hipGraph as a whole (every call is asynchronous on the
  * caller's stream, every clear is a kernel).  bess_graph_node_counts tells what a captured graph holds:
