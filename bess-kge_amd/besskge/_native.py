@@ -259,6 +259,13 @@ SIGNATURES = {
     "bess_relation_query_fwd": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],
     "bess_relation_query_bwd": [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64,
                                 _vp, _i64, _vp, _i64, _vp],
+    "bess_conve_query_workspace": [_i64] * 8 + [ctypes.POINTER(_i64)],
+    "bess_conve_query_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64] + [_i64] * 8 + [_vp],
+    "bess_conve_query_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                             _vp] + [_i64] * 8 + [_vp, _i64, _vp],
+    "bess_conve_stats_workspace": [_i64] * 7 + [ctypes.POINTER(_i64)],
+    "bess_conve_stats_fwd": [_vp, _i64, _vp, _vp, _vp] + [_i64] * 7 + [_vp, _i64, _vp],
+    "bess_conve_stats_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp] + [_i64] * 7 + [_vp, _i64, _vp],
 }
 COMM_ID_BYTES = 128
 AFFINE_COUNT_CHUNK_BYTES = 32 << 20  # BESS_AFFINE_COUNT_CHUNK_BYTES
@@ -760,6 +767,106 @@ def tucker_query_bwd(x: torch.Tensor, rel: torch.Tensor, core: torch.Tensor, swa
             dq.data_ptr(), de, _ptr(d_x), de, _ptr(d_rel), dr, _ptr(d_core), S, de, dr, _ptr(ws),
             nbytes.value if ws is not None else 0)
     return d_x, d_rel, d_core
+
+
+def _conve_image(who: str, x: torch.Tensor, K: torch.Tensor) -> Tuple[int, List[int], int, int]:
+    """(S, [Cin, H2, W, Cout, kh, kw], pixels per row, leading dimension of x) of the stacked image x [S, Cin, H2, W]
+    (rows contiguous, padded rows allowed) and the filter K [Cout, Cin, kh, kw]."""
+    if x.dim() != 4 or K.dim() != 4 or K.shape[1] != x.shape[1]:
+        raise ValueError(f"{who}: x [S, Cin, H2, W] and K [Cout, Cin, kh, kw], got {tuple(x.shape)} and {tuple(K.shape)}")
+    _f32(K, "K")
+    S, Cin, H2, W = (int(v) for v in x.shape)
+    P = Cin * H2 * W
+    if any(n > 1 and st != want for n, st, want in zip(x.shape[1:], x.stride()[1:], (H2 * W, W, 1))):
+        raise ValueError(f"{who}: the image of a row of x must be contiguous, got stride {x.stride()}")
+    ldx = _f32_ld(x.as_strided((S, P), (x.stride(0), 1)), "x", (S, P))
+    return S, [Cin, H2, W, int(K.shape[0]), int(K.shape[2]), int(K.shape[3])], P, ldx
+
+
+def _conve_workspace(entry: str, dev: torch.device, *sizes: int) -> Tuple[int, int, Optional[torch.Tensor]]:
+    """(pointer, bytes, the buffer) of the workspace `entry` asks for (the query raises beyond the LDS limit)."""
+    nbytes = ctypes.c_int64(0)
+    _check(getattr(load(), entry)(*sizes, ctypes.byref(nbytes)), entry)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if nbytes.value else None
+    return _ptr(ws), nbytes.value, ws
+
+
+def conve_supported(geometry: Sequence[int], d: int) -> None:
+    """Raise (BESS_EUNSUPPORTED) if images [Cin, H2, W] with a filter [Cout, ., kh, kw] and d outputs are beyond what
+    the ConvE kernels keep resident in LDS (include/besskge_hip.h); host arithmetic, no device needed."""
+    nbytes = ctypes.c_int64(0)
+    lib = load()
+    _check(lib.bess_conve_query_workspace(1, *geometry, d, ctypes.byref(nbytes)), "bess_conve_query_workspace")
+    _check(lib.bess_conve_stats_workspace(1, *geometry, ctypes.byref(nbytes)), "bess_conve_stats_workspace")
+
+
+def _conve_operands(who: str, x: torch.Tensor, K: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+                    m: Optional[torch.Tensor], Wfc: torch.Tensor, dy: Optional[torch.Tensor] = None):
+    """(device, S, geometry, P, F, d, the leading arguments x .. ldw of both query entry points)"""
+    dev = _same_device([("x", x), ("K", K), ("a", a), ("b", b), ("m", m), ("Wfc", Wfc), ("dy", dy)])
+    S, geo, P, ldx = _conve_image(who, x, K)
+    Cout, F = geo[3], geo[3] * (geo[1] - geo[4] + 1) * (geo[2] - geo[5] + 1)
+    _f32s(("a", a), ("b", b))
+    if tuple(a.shape) != (Cout,) or tuple(b.shape) != (Cout,) or Wfc.dim() != 2 or Wfc.shape[1] != F:
+        raise ValueError(f"{who}: a, b [{Cout}] and Wfc [d, {F}], got {tuple(a.shape)}, {tuple(b.shape)}, {tuple(Wfc.shape)}")
+    d = int(Wfc.shape[0])
+    args = [x.data_ptr(), ldx, K.data_ptr(), a.data_ptr(), b.data_ptr(), _ptr(m),
+            Cout if m is None else _f32_ld(m, "m", (S, Cout)), Wfc.data_ptr(), _f32_ld(Wfc, "Wfc", (d, F))]
+    if dy is not None:
+        args += [dy.data_ptr(), _f32_ld(dy, "dy", (S, d))]
+    return dev, S, geo, P, F, d, args
+
+
+def conve_query_fwd(x: torch.Tensor, K: torch.Tensor, a: torch.Tensor, b: torch.Tensor, m: Optional[torch.Tensor],
+                    Wfc: torch.Tensor) -> torch.Tensor:
+    """y [S, d] = (m * relu(a * conv2d(x, K) + b)).flatten(1) @ Wfc.T for the stacked image x [S, Cin, H2, W], the
+    channel affine a, b [Cout] and the channel multiplier m [S, Cout] or None (`bess_conve_query_fwd`): exact fp32 on
+    the matrix cores, the [S, F] feature map is never written.  Matrices may be views with padded rows."""
+    dev, S, geo, P, F, d, args = _conve_operands("conve_query_fwd", x, K, a, b, m, Wfc)
+    y = torch.empty((S, d), dtype=torch.float32, device=dev)
+    _launch("bess_conve_query_fwd", dev, *args, y.data_ptr(), d, S, *geo, d)
+    return y
+
+
+def conve_query_bwd(x: torch.Tensor, K: torch.Tensor, a: torch.Tensor, b: torch.Tensor, m: Optional[torch.Tensor],
+                    Wfc: torch.Tensor, dy: torch.Tensor, want: Sequence[bool] = (True,) * 5
+                    ) -> Tuple[Optional[torch.Tensor], ...]:
+    """(d_Wfc, d_x, d_K, d_a, d_b) of `conve_query_fwd` for dy [S, d]; None where `want` is False.  Bitwise
+    reproducible: no atomics (`bess_conve_query_bwd`)."""
+    dev, S, geo, P, F, d, args = _conve_operands("conve_query_bwd", x, K, a, b, m, Wfc, dy)
+    shapes = ((d, F), tuple(x.shape), tuple(K.shape), tuple(a.shape), tuple(b.shape))
+    outs = [torch.empty(s, dtype=torch.float32, device=dev) if w else None for s, w in zip(shapes, want)]
+    wp, wb, ws = _conve_workspace("bess_conve_query_workspace", dev, S, *geo, d)
+    _launch("bess_conve_query_bwd", dev, *args, _ptr(outs[0]), F, _ptr(outs[1]), P, _ptr(outs[2]), _ptr(outs[3]),
+            _ptr(outs[4]), S, *geo, d, wp, wb)
+    return tuple(outs)
+
+
+def conve_stats_fwd(x: torch.Tensor, K: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mean [Cout], M2 [Cout]) of conv2d(x, K) over batch and positions: the mean and the centred sum of squares
+    (two passes), without the feature map (`bess_conve_stats_fwd`)."""
+    dev = _same_device([("x", x), ("K", K)])
+    S, geo, P, ldx = _conve_image("conve_stats_fwd", x, K)
+    mean, M2 = _carve_f32(dev, geo[3], geo[3])
+    wp, wb, ws = _conve_workspace("bess_conve_stats_workspace", dev, S, *geo)
+    _launch("bess_conve_stats_fwd", dev, x.data_ptr(), ldx, K.data_ptr(), mean.data_ptr(), M2.data_ptr(), S, *geo, wp, wb)
+    return mean, M2
+
+
+def conve_stats_bwd(x: torch.Tensor, K: torch.Tensor, mean: torch.Tensor, d_mean: torch.Tensor, d_M2: torch.Tensor,
+                    want: Sequence[bool] = (True, True)) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(d_x, d_K) of `conve_stats_fwd` for (d_mean, d_M2) [Cout]; None where `want` is False."""
+    dev = _same_device([("x", x), ("K", K), ("mean", mean), ("d_mean", d_mean), ("d_M2", d_M2)])
+    S, geo, P, ldx = _conve_image("conve_stats_bwd", x, K)
+    _f32s(("mean", mean), ("d_mean", d_mean), ("d_M2", d_M2))
+    if not (mean.numel() == d_mean.numel() == d_M2.numel() == geo[3]):
+        raise ValueError(f"conve_stats_bwd: mean, d_mean and d_M2 must be [{geo[3]}]")
+    d_x = torch.empty(x.shape, dtype=torch.float32, device=dev) if want[0] else None
+    d_K = torch.empty(K.shape, dtype=torch.float32, device=dev) if want[1] else None
+    wp, wb, ws = _conve_workspace("bess_conve_stats_workspace", dev, S, *geo)
+    _launch("bess_conve_stats_bwd", dev, x.data_ptr(), ldx, K.data_ptr(), mean.data_ptr(), d_mean.data_ptr(),
+            d_M2.data_ptr(), _ptr(d_x), P, _ptr(d_K), S, *geo, wp, wb)
+    return d_x, d_K
 
 
 def _relation_query_call(who: str, x: torch.Tensor, M: torch.Tensor, seg: "SegmentIndex",

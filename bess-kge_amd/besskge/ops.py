@@ -197,6 +197,55 @@ class RelationQuery(torch.autograd.Function):
         return tuple(None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)) + (None, None)
 
 
+class ConvEQuery(torch.autograd.Function):
+    """ConvE's conv + channel affine + ReLU + channel mask + FC product `(x [S, Cin, H2, W], K [Cout, Cin, kh, kw],
+    a [Cout], b [Cout], m [S, Cout] | None, Wfc [d, F]) -> y [S, d]` (`nat.conve_query_fwd`): the `[S, F]` feature map
+    is never written, forward or backward.  The backward gives the gradients it is asked for (`m` gets none).  No
+    double backward."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, K: torch.Tensor, a: torch.Tensor, b: torch.Tensor,  # type: ignore
+                m: Optional[torch.Tensor], Wfc: torch.Tensor) -> torch.Tensor:
+        ops32 = [None if t is None else t.detach().float().contiguous() for t in (x, K, a, b, m, Wfc)]
+        ctx.has_mask = m is not None
+        ctx.save_for_backward(*(t for t in ops32 if t is not None))
+        ctx.dtypes = (x.dtype, K.dtype, a.dtype, b.dtype, Wfc.dtype)
+        return nat.conve_query_fwd(*ops32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx: Any, dy: torch.Tensor):  # type: ignore
+        saved = list(ctx.saved_tensors)
+        x, K, a, b = saved[:4]
+        m, Wfc = (saved[4] if ctx.has_mask else None), saved[-1]
+        need = ctx.needs_input_grad
+        d_Wfc, d_x, d_K, d_a, d_b = nat.conve_query_bwd(x, K, a, b, m, Wfc, dy.float().contiguous(),
+                                                        (need[5], need[0], need[1], need[2], need[3]))
+        grads = [None if g is None else g.to(dt) for g, dt in zip((d_x, d_K, d_a, d_b, d_Wfc), ctx.dtypes)]
+        return grads[0], grads[1], grads[2], grads[3], None, grads[4]
+
+
+class ConvEChannelStats(torch.autograd.Function):
+    """Training-mode batch statistics of `conv2d(x, K)` per output channel without the feature map:
+    `(x, K) -> (mean [Cout], M2 [Cout])`, M2 the centred sum of squares (`nat.conve_stats_fwd`).  No double backward."""
+
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, K: torch.Tensor):  # type: ignore
+        x32, k32 = x.detach().float().contiguous(), K.detach().float().contiguous()
+        mean, M2 = nat.conve_stats_fwd(x32, k32)
+        ctx.save_for_backward(x32, k32, mean)
+        ctx.dtypes = (x.dtype, K.dtype)
+        return mean, M2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx: Any, d_mean: torch.Tensor, d_M2: torch.Tensor):  # type: ignore
+        x, K, mean = ctx.saved_tensors
+        grads = nat.conve_stats_bwd(x, K, mean, d_mean.float().contiguous(), d_M2.float().contiguous(),
+                                    ctx.needs_input_grad[:2])
+        return tuple(None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes))
+
+
 class Loss(torch.autograd.Function):
     """K8 fused loss + score gradients (`logq`: the sampled softmax's per-candidate log-proposals, see
     `nat.loss_fwd_bwd`)."""

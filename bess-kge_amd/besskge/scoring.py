@@ -830,7 +830,23 @@ class TranS(_AffineScoreFunction):
 
 class ConvE(_TorchQueryHooks, MatrixDecompositionScoreFunction):
     """ConvE: <net(h, r), t> + b_t, scores not passed through a sigmoid; only
-    tails can be corrupted (reference scoring.py:949-1146)."""
+    tails can be corrupted (reference scoring.py:949-1146).
+
+    `query_route` chooses how the query network between the stacked image and the FC output is computed; both read
+    the parameters and buffers of the same `conv_layers` / `fc_layers` modules, so state dicts, checkpoints,
+    `dense_parameters()` and optimiser state are identical and a model can switch route (`fn.query_route = ...`):
+
+    * `"torch"` (default): the `torch.nn.Sequential` modules as they are (MIOpen conv, batch-norm, rocBLAS linear);
+      the `[S, F]` feature map (F = output_channels x output pixels) is written and kept for autograd.
+    * `"fused"`: `ops.ConvEQuery` (csrc/conve.hip): conv, the output-channel batch-norm folded into a channel affine,
+      ReLU, the feature-map dropout as a channel mask and the FC product in one pass on the matrix cores, forward and
+      backward, without ever writing the feature map; training-mode batch statistics come from
+      `ops.ConvEChannelStats`.  What is `[Cout]`-, `[S, d]`- or image-sized (input batch-norm and dropout, the fold,
+      the running statistics, FC bias, the last batch-norm, dropout and ReLU) stays torch.  Train and eval mode, with
+      and without `batch_normalization`, all three dropouts.  Under dropout the two routes draw different masks from
+      the same generator state (the feature-map mask is drawn as `[S, Cout]`, not by `Dropout2d`), so they agree in
+      distribution, not sample by sample.  Images beyond what the kernels keep in LDS (include/besskge_hip.h) are
+      refused at construction."""
 
     _scorer_id = nat.DISTMULT  # candidates see a dot product over [embedding | bias] rows
     supports_fused_segments = True  # ... so their K9 is the dot-product segmented reduction
@@ -854,9 +870,13 @@ class ConvE(_TorchQueryHooks, MatrixDecompositionScoreFunction):
         feature_map_dropout: float = 0.2,
         hidden_dropout: float = 0.3,
         batch_normalization: bool = True,
+        query_route: str = "torch",
         **placement: Any,
     ) -> None:
         super().__init__(negative_sample_sharing)
+        if query_route not in ("torch", "fused"):
+            raise ValueError(f'ConvE: query_route is "torch" or "fused", got {query_route!r}')
+        self.query_route = query_route
         self.sharding = sharding
         if input_channels * embedding_width * embedding_height != embedding_size:
             raise ValueError("`embedding_size` needs to be equal to"
@@ -892,6 +912,9 @@ class ConvE(_TorchQueryHooks, MatrixDecompositionScoreFunction):
             fc_layers.insert(2, torch.nn.BatchNorm1d(embedding_size))
         self.conv_layers = torch.nn.Sequential(*conv_layers)
         self.fc_layers = torch.nn.Sequential(*fc_layers)
+        if query_route == "fused":  # (host arithmetic: raises beyond the LDS-resident image limit)
+            nat.conve_supported([input_channels, 2 * embedding_height, embedding_width, output_channels, kernel_height,
+                                 kernel_width], embedding_size)
 
     def kernel_desc(self) -> nat.ModelDesc:
         d = super().kernel_desc()
@@ -904,7 +927,49 @@ class ConvE(_TorchQueryHooks, MatrixDecompositionScoreFunction):
     def _net(self, head: torch.Tensor, rel: torch.Tensor) -> torch.Tensor:
         shape = (-1, self.inp_channels, self.emb_h, self.emb_w)
         hr = torch.cat([head[..., :-1].reshape(shape), rel.reshape(shape)], dim=-2)
+        if self.query_route == "fused":
+            return self._net_fused(hr)
         return self.fc_layers(self.conv_layers(hr).flatten(start_dim=1))
+
+    def _net_fused(self, x: torch.Tensor) -> torch.Tensor:
+        """`fc_layers(conv_layers(x).flatten(1))` with everything between the conv's input and the FC product in
+        `ops.ConvEQuery`; the modules are read, not called, from the conv on."""
+        layers = list(self.conv_layers)
+        at = next(i for i, m in enumerate(layers) if isinstance(m, torch.nn.Conv2d))
+        for m in layers[:at]:  # input batch-norm and dropout
+            x = m(x)
+        conv, rest = layers[at], layers[at + 1:]
+        norm = rest[0] if isinstance(rest[0], torch.nn.BatchNorm2d) else None
+        drop = rest[-1]
+        K, S = conv.weight, x.shape[0]
+        if norm is None:
+            a, b = torch.ones_like(conv.bias), conv.bias
+        else:
+            if norm.training or norm.running_mean is None:  # batch statistics of conv + bias (the bias cancels in z)
+                mean, m2 = ops.ConvEChannelStats.apply(x, K)
+                count = S * (x.shape[2] - K.shape[2] + 1) * (x.shape[3] - K.shape[3] + 1)
+                var = m2 / count
+                if norm.training and norm.running_mean is not None:
+                    with torch.no_grad():
+                        norm.num_batches_tracked += 1
+                        f = norm.momentum if norm.momentum is not None else 1.0 / float(norm.num_batches_tracked)
+                        norm.running_mean.mul_(1 - f).add_(f * (mean + conv.bias))
+                        norm.running_var.mul_(1 - f).add_(f * m2 / max(count - 1, 1))
+                shift = 0.0 * conv.bias - mean  # (the bias stays in the graph: a zero gradient, as on the torch route)
+            else:
+                var, shift = norm.running_var, conv.bias - norm.running_mean
+            a = torch.rsqrt(var + norm.eps)
+            if norm.weight is not None:
+                a = a * norm.weight
+            b = shift * a if norm.bias is None else shift * a + norm.bias
+        mask = None
+        if drop.training and drop.p > 0:  # Dropout2d: whole channels, kept ones scaled by 1 / (1 - p)
+            mask = torch.nn.functional.dropout(torch.ones(S, K.shape[0], dtype=torch.float32, device=x.device), drop.p)
+        fc = self.fc_layers[0]
+        y = ops.ConvEQuery.apply(x, K, a, b, mask, fc.weight) + fc.bias
+        for m in list(self.fc_layers)[1:]:
+            y = m(y)
+        return y
 
     def _query_torch(self, side: int, rows: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
         if side != nat.CORRUPT_TAIL:

@@ -142,6 +142,10 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_tucker_query_bwd),
     BESS_PLAN_FN(bess_relation_query_fwd),
     BESS_PLAN_FN(bess_relation_query_bwd),
+    BESS_PLAN_FN(bess_conve_query_fwd),
+    BESS_PLAN_FN(bess_conve_query_bwd),
+    BESS_PLAN_FN(bess_conve_stats_fwd),
+    BESS_PLAN_FN(bess_conve_stats_bwd),
 };
 #undef BESS_PLAN_FN
 

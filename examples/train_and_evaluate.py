@@ -10,6 +10,7 @@ queries and report filtered-free MRR / hits@10.
                                              [--training 1vsall | kvsall [--label-smoothing 0.1]]
                                              [--scorer TuckER --relation-size 16 [--tucker-route relation]]
                                              [--scorer RESCAL]
+                                             [--scorer ConvE [--conve-route fused]]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -73,10 +74,12 @@ def main(argv=None) -> dict:
     ap.add_argument("--n-shard", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--scorer", default="TransE", choices=["TransE", "RotatE", "DistMult", "ComplEx", "PairRE", "TranS", "TuckER",
-                                                                "RESCAL"])
+                                                                "RESCAL", "ConvE"])
     ap.add_argument("--relation-size", type=int, default=16, help="width of the relation rows of --scorer TuckER")
     ap.add_argument("--tucker-route", default="outer", choices=["outer", "relation"],
                     help="TuckER's query_route: per-triple outer product, or one mixed matrix per relation")
+    ap.add_argument("--conve-route", default="torch", choices=["torch", "fused"],
+                    help="ConvE's query_route: the torch modules, or the fused conv + FC kernels (no feature map)")
     ap.add_argument("--embedding-size", type=int, default=32)
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--negative-weights", default="uniform", choices=["uniform", "degree"],
@@ -102,9 +105,9 @@ def main(argv=None) -> dict:
     k_vs_all = args.training == "kvsall"
     one_vs_all = args.training == "1vsall" or k_vs_all
     if one_vs_all and (args.proposal_correction or args.negative_weights != "uniform" or args.loss != "logsigmoid"
-                       or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx", "TuckER", "RESCAL")):
+                       or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx", "TuckER", "RESCAL", "ConvE")):
         ap.error(f"--training {args.training} samples nothing and brings its own loss: TransE / RotatE / DistMult / ComplEx "
-                 "/ TuckER / RESCAL, "
+                 "/ TuckER / RESCAL / ConvE, "
                  "without --negative-weights / --loss / --proposal-correction")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -121,6 +124,10 @@ def main(argv=None) -> dict:
     elif args.scorer == "TuckER":  # (the paper's recipe: --training kvsall --label-smoothing 0.1)
         fn = scoring.TuckER(True, sharding, args.n_relation, d, args.relation_size, batch_normalization=True,
                             input_dropout=0.2, hidden_dropout=0.2, query_route=args.tucker_route)
+    elif args.scorer == "ConvE":  # (the paper's recipe: --training kvsall --label-smoothing 0.1)
+        height = max(h for h in range(1, d + 1) if d % h == 0 and h * h <= d)  # the embedding as a height x width image
+        fn = scoring.ConvE(True, sharding, args.n_relation, d, height, d // height, inverse_relations=False,
+                           query_route=args.conve_route)
     else:
         fn = getattr(scoring, args.scorer)(True, sharding, args.n_relation, d)
 
@@ -172,7 +179,7 @@ def main(argv=None) -> dict:
     bs_test = RigidShardedBatchSampler(pts_test, PlaceholderNegativeSampler("t"), shard_bs=256, batches_per_step=2,
                                        seed=0, return_triple_idx=True)
     ev = Evaluation(["mrr", "hits@1", "hits@10"], mode="average", reduction="sum")
-    if args.scorer == "TuckER":
+    if args.scorer in ("TuckER", "ConvE"):
         fn.eval()  # running statistics in its batch-norms, no dropout
     pipe = AllScoresPipeline(bs_test, "t", fn, evaluation=ev, return_scores=False, device=dev)
     res = pipe()

@@ -1204,6 +1204,54 @@ int bess_relation_query_bwd(const float* x, int64_t ldx, const float* M, int64_t
                             float* d_x, int64_t ld_dx, float* d_M, int64_t lddm, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/* ---- ConvE: conv + channel affine + ReLU + channel mask + FC, no feature map (csrc/conve.hip) -----------------
+ * All tensors fp32.  x [S, Cin, H2, W] (rows of Cin H2 W floats, leading dimension ldx): the stacked image.
+ * K [Cout, Cin, kh, kw] the filter, a, b [Cout] the channel affine, m [S, Cout] (ldm) a channel multiplier or NULL,
+ * Wfc [d, F] (ldw) row-major as torch.nn.Linear.weight.  Ho = H2 - kh + 1, Wo = W - kw + 1, F = Cout Ho Wo,
+ * f = (c Ho + i) Wo + j:
+ *
+ *     conv[s, c, i, j] = sum_{ci, u, v} K[c, ci, u, v] x[s, ci, i + u, j + v]     (no bias, no padding, stride 1)
+ *     z = a_c conv + b_c       A[s, f] = m[s, c] max(z, 0)       y[s, n] = sum_f A[s, f] Wfc[n, f]
+ *
+ * bess_conve_query_bwd, for dy [S, d]: d_Wfc [d, F], d_x like x, d_K like K, d_a, d_b [Cout] (relu' = [z > 0]; m
+ * gets no gradient).  It overwrites its outputs, skips a NULL output and takes S = 0 (zero parameter gradients).
+ * Exact fp32 on v_mfma_f32_32x32x2_f32; A is formed from images resident in LDS on its way into the matrix cores and
+ * is never written: no kernel holds an [S, F] buffer.  No float atomics: every output is bitwise reproducible.
+ * d_K, d_a, d_b go through per-tile partial sums in the workspace (bess_conve_query_workspace bytes =
+ * ceil(S / 32) Cout (Cin kh kw + 2) floats), merged in tile order.
+ *
+ * The statistics operator gives training-mode batch statistics of conv without a feature map:
+ * mean_c = (1 / N) sum_{s, i, j} conv, N = S Ho Wo, and M2_c = sum (conv - mean_c)^2, centred (a second pass).
+ * bess_conve_stats_bwd, for (d_mean, d_M2) [Cout]: d_conv = d_mean_c / N + 2 (conv - mean_c) d_M2_c pushed through
+ * the conv to d_x and d_K (either may be NULL).  Workspace: bess_conve_stats_workspace bytes.  S >= 1 in the forward.
+ *
+ * Limit (LDS residency, 160 KiB per workgroup = 40960 floats; KK = Cin kh kw, P = Cin H2 W the image of one row):
+ *     query:   8512 + Cout (KK + 2) + 65 P                                         <= 40960   (64 images, forward)
+ *              4224 + 4 (KK + 2) + Cout (KK + 2) + 33 * 32 ceil(d / 32) + 66 P      <= 40960   (32 images + d_x, backward)
+ *     stats:   8 (2 P + Ho Wo) + Cout KK + 4 KK + 4                                 <= 40960
+ * The paper's ConvE (P = 400, Cout = 32, 3 x 3, d = 200) takes 139,456 and 153,648 bytes.  Beyond the limit every
+ * entry point, the workspace queries included, returns BESS_EUNSUPPORTED.  Widths, leading dimensions or pointers
+ * that are not multiples of 4 floats take scalar loads. */
+int bess_conve_query_workspace(int64_t S, int64_t Cin, int64_t H2, int64_t W, int64_t Cout, int64_t kh, int64_t kw,
+                               int64_t d, int64_t* bytes);
+int bess_conve_query_fwd(const float* x, int64_t ldx, const float* K, const float* a, const float* b, const float* m,
+                         int64_t ldm, const float* Wfc, int64_t ldw, float* y, int64_t ldy, int64_t S, int64_t Cin,
+                         int64_t H2, int64_t W, int64_t Cout, int64_t kh, int64_t kw, int64_t d, void* stream);
+int bess_conve_query_bwd(const float* x, int64_t ldx, const float* K, const float* a, const float* b, const float* m,
+                         int64_t ldm, const float* Wfc, int64_t ldw, const float* dy, int64_t lddy, float* d_Wfc,
+                         int64_t ld_dw, float* d_x, int64_t ld_dx, float* d_K, float* d_a, float* d_b, int64_t S,
+                         int64_t Cin, int64_t H2, int64_t W, int64_t Cout, int64_t kh, int64_t kw, int64_t d,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int bess_conve_stats_workspace(int64_t S, int64_t Cin, int64_t H2, int64_t W, int64_t Cout, int64_t kh, int64_t kw,
+                               int64_t* bytes);
+int bess_conve_stats_fwd(const float* x, int64_t ldx, const float* K, float* mean, float* M2, int64_t S, int64_t Cin,
+                         int64_t H2, int64_t W, int64_t Cout, int64_t kh, int64_t kw, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+int bess_conve_stats_bwd(const float* x, int64_t ldx, const float* K, const float* mean, const float* d_mean,
+                         const float* d_M2, float* d_x, int64_t ld_dx, float* d_K, int64_t S, int64_t Cin, int64_t H2,
+                         int64_t W, int64_t Cout, int64_t kh, int64_t kw, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 /* ---- recorded steps -----------------------------------------------------------
  * A step of this library can be captured into a hipGraph as a whole (every call is asynchronous on the
  * caller's stream, every clear is a kernel).  bess_graph_node_counts tells what a captured graph holds:
