@@ -266,6 +266,10 @@ SIGNATURES = {
     "bess_conve_stats_workspace": [_i64] * 7 + [ctypes.POINTER(_i64)],
     "bess_conve_stats_fwd": [_vp, _i64, _vp, _vp, _vp] + [_i64] * 7 + [_vp, _i64, _vp],
     "bess_conve_stats_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp] + [_i64] * 7 + [_vp, _i64, _vp],
+    "bess_relation_lse_workspace": [_MD, _i64, _i64, ctypes.POINTER(_i64)],
+    "bess_relation_lse_fwd": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
+    "bess_relation_lse_bwd": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
+                              _vp, _i64, _vp, _i64, _vp],
 }
 COMM_ID_BYTES = 128
 AFFINE_COUNT_CHUNK_BYTES = 32 << 20  # BESS_AFFINE_COUNT_CHUNK_BYTES
@@ -918,6 +922,66 @@ def relation_query_bwd(x: torch.Tensor, M: torch.Tensor, seg: "SegmentIndex", sw
     args[4] = int(bool(swap_axes))
     _launch("bess_relation_query_bwd", dev, *args, *rest)
     return d_x, d_M
+
+
+def _table_ld(t: torch.Tensor, name: str, d: ModelDesc) -> int:
+    """Leading dimension, in elements, of a [rows, d.width] matrix of the table type whose rows are contiguous."""
+    if t.dim() != 2 or t.shape[1] != d.width or _dtype_code(t) != d.dtype or (d.width > 1 and t.stride(1) != 1) \
+            or (t.shape[0] > 1 and t.stride(0) < d.width):
+        raise ValueError(f"`{name}` must be a [rows, {d.width}] matrix of the descriptor's table type with contiguous "
+                         f"rows, got {t.dtype} {tuple(t.shape)} stride {t.stride()}")
+    return int(t.stride(0)) if t.shape[0] > 1 else int(d.width)
+
+
+def _relation_lse_operands(who: str, d: ModelDesc, head: RowSource, tail: RowSource, rel_table: torch.Tensor,
+                           more: Sequence[Tuple[str, Optional[torch.Tensor]]] = ()) -> Tuple[torch.device, int, List[Any]]:
+    """(device, S, the arguments desc .. n_rel of both entry points) of the relation softmax."""
+    if int(d.scorer) not in (DISTMULT, COMPLEX):
+        raise ValueError(f"{who}: DistMult or ComplEx only (the score must be a dot product with the relation row)")
+    dev = _same_device([("head rows", head.base), ("head_idx", head.idx), ("tail rows", tail.base), ("tail_idx", tail.idx),
+                        ("relation_embedding", rel_table)] + list(more))
+    S = len(head)
+    if len(tail) != S:
+        raise ValueError(f"{who}: {S} head rows but {len(tail)} tail rows")
+    args = [ctypes.byref(d), head.base.data_ptr(), _table_ld(head.base, "head rows", d), _idx(head.idx, "head_idx"),
+            tail.base.data_ptr(), _table_ld(tail.base, "tail rows", d), _idx(tail.idx, "tail_idx"), rel_table.data_ptr(),
+            _table_ld(rel_table, "relation_embedding", d), int(rel_table.shape[0])]
+    return dev, S, args
+
+
+def relation_lse_fwd(d: ModelDesc, head: RowSource, tail: RowSource, rel_table: torch.Tensor) -> torch.Tensor:
+    """lse [S] f32 = log sum over ALL rows r of `rel_table` of exp(score(h_i, r, t_i)), DistMult / ComplEx
+    (`bess_relation_lse_fwd`): one launch, no workspace, no host read; neither the query g(h, t) nor the [S, n_rel]
+    scores are written.  Row bases and the table may be views of wider buffers."""
+    dev, S, args = _relation_lse_operands("relation_lse_fwd", d, head, tail, rel_table)
+    lse = torch.empty((S,), dtype=torch.float32, device=dev)
+    if S:
+        _launch("bess_relation_lse_fwd", dev, *args, S, lse.data_ptr())
+    return lse
+
+
+def relation_lse_bwd(d: ModelDesc, head: RowSource, tail: RowSource, rel_table: torch.Tensor, rel_idx: torch.Tensor,
+                     lse: torch.Tensor, coef: torch.Tensor, d_head: torch.Tensor, d_tail: torch.Tensor,
+                     d_rel: torch.Tensor) -> None:
+    """Backward of coef_i * (lse_i - score(h_i, rel_idx_i, t_i)) (`bess_relation_lse_bwd`): ADDS the gradients into
+    d_head, d_tail [S, W] (one row per triple) and d_rel [n_rel, W], all float32.  Bitwise reproducible: no atomics."""
+    dev, S, args = _relation_lse_operands("relation_lse_bwd", d, head, tail, rel_table,
+                                          [("relation", rel_idx), ("lse", lse), ("coef", coef), ("d_head", d_head),
+                                           ("d_tail", d_tail), ("d_rel", d_rel)])
+    _idx(rel_idx, "relation", S)
+    _f32s(("lse", lse), ("coef", coef))
+    if lse.numel() != S or coef.numel() != S:
+        raise ValueError("relation_lse_bwd: one lse and one coef per triple")
+    W, n_rel = int(d.width), int(rel_table.shape[0])
+    lds = [_f32_ld(t, name, shape) for t, name, shape in ((d_head, "d_head", (S, W)), (d_tail, "d_tail", (S, W)),
+                                                          (d_rel, "d_rel", (n_rel, W)))]
+    if S == 0:
+        return
+    nbytes = ctypes.c_int64(0)
+    _check(load().bess_relation_lse_workspace(ctypes.byref(d), S, n_rel, ctypes.byref(nbytes)), "bess_relation_lse_workspace")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)  # (kept alive by the stream-ordered allocator)
+    _launch("bess_relation_lse_bwd", dev, *args, rel_idx.data_ptr(), lse.data_ptr(), coef.data_ptr(), S,
+            d_head.data_ptr(), lds[0], d_tail.data_ptr(), lds[1], d_rel.data_ptr(), lds[2], ws.data_ptr(), nbytes.value)
 
 
 def query_width(d: ModelDesc) -> int:

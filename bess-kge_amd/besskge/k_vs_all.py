@@ -53,6 +53,7 @@ class KvsAllBessKGE(OneVsAllBessKGE):
         loss_fn: BaseLossFunction,
         known_triples: Union[KnownTripleFilter, Sequence[np.ndarray]],
         regularizer: Optional[EmbeddingRegularizer] = None,
+        relation_prediction_weight: float = 0.0,
     ) -> None:
         """
         :param negative_sampler: `PlaceholderNegativeSampler("h" | "t")` (nothing is sampled).
@@ -61,8 +62,10 @@ class KvsAllBessKGE(OneVsAllBessKGE):
         :param known_triples: the triples whose completions are positive labels (usually the training set), global
             ids: a `KnownTripleFilter` or a list of [n, 3] arrays; built once, uploaded to each local device.
         :param regularizer: as for the other schemes.
+        :param relation_prediction_weight: as for `OneVsAllBessKGE` (DistMult / ComplEx).
         """
-        super().__init__(negative_sampler, score_fn, loss_fn, None, regularizer)
+        super().__init__(negative_sampler, score_fn, loss_fn, None, regularizer,
+                         relation_prediction_weight=relation_prediction_weight)
         n_relation = int(score_fn.relation_embedding.shape[0])
         if not isinstance(known_triples, KnownTripleFilter):
             known_triples = KnownTripleFilter(known_triples, self.sharding.n_entity, n_relation)

@@ -28,6 +28,11 @@ against its own rows, but what travels back is two floats per (query, shard):
             link) and its share of d_query, which goes to the owners by
             all-to-all and is summed in shard order; `query_bwd`, `triple_bwd`
             with d_pos = -coef, the regulariser on the positives' rows.
+  relation prediction (`relation_prediction_weight` > 0; Chen et al. 2021; DistMult / ComplEx): every triple also
+            pays weight * coef_i * (log sum_{r' < n_relation} exp(score(h_i, r', t_i)) - pos_i).  The owner of the
+            triples holds both rows already: `nat.relation_lse_fwd` right after `triple_fwd`,
+            `nat.relation_lse_bwd` right after `triple_bwd`, added into the same dh, dt and d_rel - nothing new
+            crosses the link.
   update    everything is handed to `BessKGE._hand_over` as `_ShardGrads`:
             the dense gradient is the row list (arange(M_real), d_neg) beside
             the head / tail lists, so every optimiser, update route and
@@ -58,6 +63,7 @@ class OneVsAllBessKGE(BessKGE):
         evaluation: Optional[Any] = None,
         regularizer: Optional[EmbeddingRegularizer] = None,
         return_scores: bool = False,
+        relation_prediction_weight: float = 0.0,
     ) -> None:
         """
         :param negative_sampler: `PlaceholderNegativeSampler("h" | "t")` (nothing is sampled).
@@ -67,8 +73,16 @@ class OneVsAllBessKGE(BessKGE):
             without `proposal_correction`; only its `loss_scale` enters.
         :param evaluation: must be None (ranks over all entities: `AllScoresPipeline`).
         :param regularizer: as for the other schemes.
+        :param relation_prediction_weight: weight of the cross entropy of every triple's relation against all
+            rows of the relation table (inverse relations included), DistMult and ComplEx only; 0: no such term.
         """
         me = type(self).__name__
+        self.relation_prediction_weight = float(relation_prediction_weight)
+        if not self.relation_prediction_weight >= 0.0:
+            raise ValueError(f"{me}: relation_prediction_weight must be >= 0, got {relation_prediction_weight}")
+        if self.relation_prediction_weight > 0.0 and type(score_fn) not in (DistMult, ComplEx):
+            raise ValueError(f"{me}: relation prediction needs a score that is a dot product with the relation row: "
+                             f"DistMult or ComplEx, not {type(score_fn).__name__}")
         if return_scores:
             raise ValueError(f"{me} never holds the [S, n_entity] scores: return_scores=True is refused")
         if not isinstance(negative_sampler, PlaceholderNegativeSampler) or negative_sampler.corruption_scheme not in (
@@ -185,7 +199,7 @@ class OneVsAllBessKGE(BessKGE):
             q_state.append((ent, rel_q, query, qctx, labels))
         ml_back = group.all_to_all(partials)  # [n(shard), S, 2] at the triples' owner
         tails_in = group.all_to_all(tails_out)
-        outs, norms, coefs = [], [], []
+        outs, norms, coefs, rp_lse = [], [], [], []
         d_pos = -1.0
         for st, b, ml, tl in zip(steps, batches, ml_back, tails_in):
             dev = st.table.device
@@ -197,12 +211,20 @@ class OneVsAllBessKGE(BessKGE):
             w = self._triple_weight(b, dev, scale)
             coef = (w * float(self.loss_fn.loss_scale)).expand(term.shape[0]).contiguous()
             loss = (coef * term).sum().reshape(1)
+            rp = None
+            if self.relation_prediction_weight > 0.0:  # the relation of every triple against all relations
+                rp_lse.append(nat.relation_lse_fwd(desc, RowSource(st.table, st.head_idx), st.tail,
+                                                   fn.relation_embedding.data))
+                rp = (coef * (rp_lse[-1] - st.positive_score)).sum().reshape(1)
+                loss = loss + self.relation_prediction_weight * rp
             out: Dict[str, Any] = dict(loss=(loss if scale == 1.0 else loss / scale).reshape(()),
                                        positive_score=st.positive_score.to(fn.relation_embedding.dtype))
+            if rp is not None:
+                out["relation_prediction"] = (rp if scale == 1.0 else rp / scale).reshape(())
             outs.append(out)
             norms.append(norm)
             coefs.append(coef)
-        return dict(steps=steps, q_state=q_state, outs=outs, norm=norms, coef=coefs, d_pos=d_pos)
+        return dict(steps=steps, q_state=q_state, outs=outs, norm=norms, coef=coefs, d_pos=d_pos, rp_lse=rp_lse)
 
     # ---------------------------------------------------------------- forward
     def forward(self, head: torch.Tensor, relation: torch.Tensor, tail: torch.Tensor,  # type: ignore[override]
@@ -241,10 +263,14 @@ class OneVsAllBessKGE(BessKGE):
         shards = [_ShardGrads(st) for st in steps]
         # positives: d loss / d pos = -coef (times the positive label's weight under KvsAll)
         d_tails = []
-        for sh, b, out, coef in zip(shards, batches, outs, fwd["coef"]):
+        for i, (sh, b, out, coef) in enumerate(zip(shards, batches, outs, fwd["coef"])):
             st = sh.step
             dh, dt = fn.triple_bwd(RowSource(st.table, st.head_idx), st.tail, st.rel_idx, st.triple_ctx,
                                    (fwd["d_pos"] * coef).contiguous(), d_rel)
+            if self.relation_prediction_weight > 0.0:
+                nat.relation_lse_bwd(desc, RowSource(st.table, st.head_idx), st.tail, fn.relation_embedding.data,
+                                     st.rel_idx, fwd["rp_lse"][i], (self.relation_prediction_weight * coef).contiguous(),
+                                     dh, dt, d_rel)
             if self.regularizer is not None:
                 self._regularize(st, b, out, grad_scale, dh, dt, d_rel)
             sh.rows.append((st.head_idx, dh))

@@ -33,7 +33,6 @@
 namespace bess {
 namespace {
 
-constexpr int64_t LDS_LIMIT = 160 * 1024;  // per workgroup on gfx950
 constexpr int AT = 32;                     // rows of a k_conve_bwd_act tile
 constexpr int LD_R = AT + 1;               // ... and the stride of its [index][row] images
 constexpr int ACT_COLS = 128;              // columns of G per pass: 4 waves side by side
@@ -537,20 +536,6 @@ int make_geo(const char* who, int64_t S, int64_t Cin, int64_t H2, int64_t W, int
 
 inline int64_t act_parts_bytes(int64_t S, const Geo& g) { return ceil_div(S, AT) * g.Cout * (g.KK + 2) * 4; }
 inline int64_t stats_parts_bytes(int64_t S, const Geo& g) { return ceil_div(S, STAT_ROWS) * g.Cout * (g.KK > 1 ? g.KK : 1) * 4; }
-
-// The resident-image kernels may take all of the CU's LDS: the attribute is set once per (kernel, device).
-template <typename K>
-bool reserve_lds(K kernel, std::atomic<uint64_t>& done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    const uint64_t bit = 1ull << dev;
-    if (done.load(std::memory_order_relaxed) & bit) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(LDS_LIMIT)) != hipSuccess)
-        return false;
-    done.fetch_or(bit, std::memory_order_relaxed);
-    return true;
-}
 
 template <typename K, typename ARGS>
 int launch_resident(const char* what, K kernel, std::atomic<uint64_t>& done, dim3 grid, int64_t lds_floats, const ARGS& A,

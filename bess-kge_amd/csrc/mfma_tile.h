@@ -4,6 +4,8 @@
 // gemm_mfma.hip's conventions, restated here for kernels whose operands are gathered or formed on the way to LDS.
 #pragma once
 
+#include <atomic>
+
 #include "common.h"
 
 namespace bess {
@@ -16,6 +18,8 @@ constexpr int TT = 64;         // edge of the output tile
 constexpr int LD_T = TT + 1;   // [k][m] image written by transposing stores
 constexpr int LD_D = TT + 4;   // [k][m] image written by direct 16-byte stores
 constexpr int B_IMG = TK * LD_D;                  // floats of one slice image (either stride)
+
+constexpr int64_t LDS_LIMIT = 160 * 1024;         // per workgroup on gfx950
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -97,6 +101,21 @@ __device__ __forceinline__ void mfma_slice(const float* a_img, const float* b_im
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(SCALE ? a[c] * rk : a[c], b[c], acc, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+// A kernel whose images stay resident may take all of the CU's LDS.  The attribute belongs to a (kernel, device) pair: it is set once for
+// every device this process launches on (`done`: one bit per device ordinal, one word per instantiation).
+template <typename K>
+inline bool reserve_lds(K kernel, std::atomic<uint64_t>& done) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+    const uint64_t bit = 1ull << dev;
+    if (done.load(std::memory_order_relaxed) & bit) return true;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(LDS_LIMIT)) != hipSuccess)
+        return false;
+    done.fetch_or(bit, std::memory_order_relaxed);
+    return true;
 }
 
 __device__ __forceinline__ void zero_acc(f32x16& acc) {

@@ -146,6 +146,8 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_conve_query_bwd),
     BESS_PLAN_FN(bess_conve_stats_fwd),
     BESS_PLAN_FN(bess_conve_stats_bwd),
+    BESS_PLAN_FN(bess_relation_lse_fwd),
+    BESS_PLAN_FN(bess_relation_lse_bwd),
 };
 #undef BESS_PLAN_FN
 

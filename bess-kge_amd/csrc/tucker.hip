@@ -22,15 +22,12 @@
 // -> LDS staging split around the MFMA phase.  Only 64-tiles: the product has de output columns, so 128-tiles would give
 // ceil(S / 128) * ceil(de / 128) workgroups - 64 at S = 4096, de = 200, a quarter of the chip.
 // No atomics anywhere: every output element is written once, by one lane, in a fixed order of summation.
-#include <atomic>
-
 #include "common.h"
 #include "mfma_tile.h"
 
 namespace bess {
 namespace {
 
-constexpr int64_t LDS_LIMIT = 160 * 1024;         // per workgroup on gfx950
 constexpr int TUCKER_MAX_DE = 544;                // 17 slices of the resident x image beside the core's two buffers
 
 inline int64_t rows_lds_bytes(int64_t de) { return (2 * B_IMG + ceil_div(de, TK) * TK * LD_T) * 4; }
@@ -221,21 +218,6 @@ int check_shape(const char* who, int64_t S, int64_t de, int64_t dr) {
         return fail(BESS_EUNSUPPORTED, "%s: de = %lld is above %d (the 64 x de tile of the rows stays in LDS)", who,
                     static_cast<long long>(de), TUCKER_MAX_DE);
     return BESS_OK;
-}
-
-// The row kernels may take all of the CU's LDS.  The attribute belongs to a (kernel, device) pair: it is set once for
-// every device this process launches on (`done`: one bit per device ordinal, one word per instantiation).
-template <typename K>
-bool reserve_lds(K kernel, std::atomic<uint64_t>& done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    const uint64_t bit = 1ull << dev;
-    if (done.load(std::memory_order_relaxed) & bit) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(LDS_LIMIT)) != hipSuccess)
-        return false;
-    done.fetch_or(bit, std::memory_order_relaxed);
-    return true;
 }
 
 // q (REL false) or the partials of d_rel (REL true) of one product

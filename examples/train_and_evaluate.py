@@ -8,6 +8,7 @@ queries and report filtered-free MRR / hits@10.
                                              [--loss ssce --proposal-correction]
                                              [--regularizer n3 --reg-coef 1e-3]
                                              [--training 1vsall | kvsall [--label-smoothing 0.1]]
+                                            [--relation-prediction 0.5]
                                              [--scorer TuckER --relation-size 16 [--tucker-route relation]]
                                              [--scorer RESCAL]
                                              [--scorer ConvE [--conve-route fused]]
@@ -99,7 +100,12 @@ def main(argv=None) -> dict:
                          "cross entropy over all entities whose positive labels are all known tails of the training "
                          "set (KvsAllBessKGE)")
     ap.add_argument("--label-smoothing", type=float, default=0.0, help="label smoothing of --training kvsall")
+    ap.add_argument("--relation-prediction", type=float, default=0.0, metavar="WEIGHT",
+                    help="with --training 1vsall | kvsall and --scorer DistMult | ComplEx: add WEIGHT x the cross entropy "
+                         "of every triple's relation against ALL relations (Chen et al. 2021)")
     args = ap.parse_args(argv)
+    if args.relation_prediction != 0.0 and args.training == "sampled":
+        ap.error("--relation-prediction needs --training 1vsall or kvsall")
     if args.proposal_correction and (args.negative_weights != "degree" or args.loss != "ssce"):
         ap.error("--proposal-correction needs --negative-weights degree and --loss ssce")
     k_vs_all = args.training == "kvsall"
@@ -154,9 +160,10 @@ def main(argv=None) -> dict:
                    }[args.regularizer]
     if k_vs_all:  # (the filter is the training triples)
         model = KvsAllBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, known_triples=[train],
-                              regularizer=regularizer)
+                              regularizer=regularizer, relation_prediction_weight=args.relation_prediction)
     elif one_vs_all:
-        model = OneVsAllBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)
+        model = OneVsAllBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer,
+                                relation_prediction_weight=args.relation_prediction)
     else:
         model = EmbeddingMovingBessKGE(negative_sampler=ns, score_fn=fn, loss_fn=loss_fn, regularizer=regularizer)
     trainer = runtime.training_model(model, runtime.Options(device_iterations=bs.batches_per_step),

@@ -1252,6 +1252,35 @@ int bess_conve_stats_bwd(const float* x, int64_t ldx, const float* K, const floa
                          int64_t W, int64_t Cout, int64_t kh, int64_t kw, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* ---- relation prediction: the softmax of a triple's relation over ALL relations (csrc/relation_lse.hip) ---------
+ * For the two scorers whose score is linear in the relation row, desc.scorer BESS_DISTMULT or BESS_COMPLEX
+ * (desc.rel_width == desc.width = W, even for ComplEx; rows [re | im]); every other scorer is BESS_EINVAL:
+ *     s[i, r] = <rel[r], g(h_i, t_i)>     DistMult g = h * t;   ComplEx g = [h1 t1 + h2 t2 | h1 t2 - h2 t1]
+ *     lse[i]  = log sum_{r < n_rel} exp(s[i, r])                                        (bess_relation_lse_fwd)
+ * Heads and tails are row sources (base, ld, idx) of the table type (desc.dtype: fp32 or fp16, converted on load),
+ * rel_table [n_rel, W] of the same type; leading dimensions in elements.  One launch, no workspace, no host read
+ * (legal on a capturing stream); g is formed on the way to LDS and never written, the scores never leave the MFMA
+ * accumulators (exact fp32 products, fp32 accumulation) and fold into running (max, sum) pairs in registers.
+ * bess_relation_lse_bwd, with P[i, r] = coef[i] * (exp(s[i, r] - lse[i]) - [r == rel_idx[i]]) (coef[i] == 0: exact
+ * zeros whatever lse[i]), ADDS
+ *     d_head[i] += dg[i] (chain rule through g),  d_tail[i] += ...,  dg[i] = sum_r P[i, r] rel[r]
+ *     d_rel[r]  += sum_i P[i, r] g[i]
+ * into fp32 buffers d_head, d_tail [S, W] (one row per triple, not per table row) and d_rel [n_rel, W].  rel_idx in
+ * [0, n_rel).  Scores are recomputed; two launches; no float atomics: the rows are split into at most 8 shares
+ * whose partial sums of d_rel go through the workspace (bess_relation_lse_workspace bytes = shares * n_rel * W * 4,
+ * 16-byte aligned, nothing to clear) and are merged in share order - every output is bitwise reproducible.
+ * Any 0 <= S < 2^22, 1 <= n_rel < 2^24, 1 <= W <= 32768.  Widths (ComplEx: half widths), leading dimensions or
+ * pointers that are not multiples of 4 scalars take scalar loads. */
+int bess_relation_lse_workspace(const bess_model_desc* d, int64_t S, int64_t n_rel, int64_t* bytes);
+int bess_relation_lse_fwd(const bess_model_desc* d, const void* head_base, int64_t ld_head, const int32_t* head_idx,
+                          const void* tail_base, int64_t ld_tail, const int32_t* tail_idx, const void* rel_table,
+                          int64_t ld_rel, int64_t n_rel, int64_t S, float* lse, void* stream);
+int bess_relation_lse_bwd(const bess_model_desc* d, const void* head_base, int64_t ld_head, const int32_t* head_idx,
+                          const void* tail_base, int64_t ld_tail, const int32_t* tail_idx, const void* rel_table,
+                          int64_t ld_rel, int64_t n_rel, const int32_t* rel_idx, const float* lse, const float* coef,
+                          int64_t S, float* d_head, int64_t ld_dhead, float* d_tail, int64_t ld_dtail, float* d_rel,
+                          int64_t ld_drel, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- recorded steps -----------------------------------------------------------
  * A step of this library can be captured into a hipGraph as a whole (every call is asynchronous on the
  * caller's stream, every clear is a kernel).  bess_graph_node_counts tells what a captured graph holds:
