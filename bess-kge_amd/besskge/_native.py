@@ -121,6 +121,28 @@ class Pcg64State(ctypes.Structure):
 
 _PG = ctypes.POINTER(Pcg64State)
 
+STRUCT_MAX_BLOCKS, STRUCT_MAX_TERMS = 8, 64  # BESS_STRUCT_MAX_BLOCKS, BESS_STRUCT_MAX_TERMS
+
+
+class StructDesc(ctypes.Structure):
+    """struct bess_struct_desc: the term table of a structured bilinear scorer"""
+
+    _fields_ = [
+        ("dtype", _i32),
+        ("n_ent_blocks", _i32),
+        ("n_rel_blocks", _i32),
+        ("block_width", _i32),
+        ("n_terms", _i32),
+        ("relation_unit_norm", _i32),
+        ("reserved", _i32 * 2),
+        ("ti", _i32 * STRUCT_MAX_TERMS),
+        ("tj", _i32 * STRUCT_MAX_TERMS),
+        ("tk", _i32 * STRUCT_MAX_TERMS),
+        ("tc", _f32 * STRUCT_MAX_TERMS),
+    ]
+
+
+_SD = ctypes.POINTER(StructDesc)
 _MD = ctypes.POINTER(ModelDesc)
 _LD = ctypes.POINTER(LossDesc)
 
@@ -270,6 +292,10 @@ SIGNATURES = {
     "bess_relation_lse_fwd": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp],
     "bess_relation_lse_bwd": [_MD, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64,
                               _vp, _i64, _vp, _i64, _vp],
+    "bess_struct_query_workspace": [_SD, _i64, _i64, ctypes.POINTER(_i64)],
+    "bess_struct_query_fwd": [_SD, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "bess_struct_query_bwd": [_SD, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
+                              _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
 }
 COMM_ID_BYTES = 128
 AFFINE_COUNT_CHUNK_BYTES = 32 << 20  # BESS_AFFINE_COUNT_CHUNK_BYTES
@@ -924,13 +950,115 @@ def relation_query_bwd(x: torch.Tensor, M: torch.Tensor, seg: "SegmentIndex", sw
     return d_x, d_M
 
 
-def _table_ld(t: torch.Tensor, name: str, d: ModelDesc) -> int:
-    """Leading dimension, in elements, of a [rows, d.width] matrix of the table type whose rows are contiguous."""
-    if t.dim() != 2 or t.shape[1] != d.width or _dtype_code(t) != d.dtype or (d.width > 1 and t.stride(1) != 1) \
-            or (t.shape[0] > 1 and t.stride(0) < d.width):
-        raise ValueError(f"`{name}` must be a [rows, {d.width}] matrix of the descriptor's table type with contiguous "
+def struct_desc(table: torch.Tensor, n_ent_blocks: int, n_rel_blocks: int, block_width: int,
+                terms: Sequence[Tuple[int, int, int, float]], relation_unit_norm: bool = False) -> StructDesc:
+    """The descriptor of the term table `[(i, j, k, c)]` for tables of `table`'s type.  More than STRUCT_MAX_TERMS
+    terms do not fit the struct; everything else is left to the library's own checks."""
+    if len(terms) > STRUCT_MAX_TERMS:
+        raise ValueError(f"struct_desc: at most {STRUCT_MAX_TERMS} terms, got {len(terms)}")
+    d = StructDesc()
+    d.dtype, d.n_ent_blocks, d.n_rel_blocks, d.block_width = _dtype_code(table), n_ent_blocks, n_rel_blocks, block_width
+    d.n_terms, d.relation_unit_norm = len(terms), int(bool(relation_unit_norm))
+    for n, (i, j, k, c) in enumerate(terms):
+        d.ti[n], d.tj[n], d.tk[n], d.tc[n] = int(i), int(j), int(k), float(c)
+    return d
+
+
+def _struct_rows(d: StructDesc, src: Optional[RowSource], name: str, width: int) -> List[int]:
+    """(base pointer, leading dimension, index pointer) of a row source whose base is a [rows, width] matrix of the
+    descriptor's table type with contiguous rows (a view of a wider buffer is fine); NULLs for None."""
+    if src is None:
+        return [0, width, 0]
+    return [src.base.data_ptr(), _table_ld(src.base, name, d, width), _idx(src.idx, name + " idx")]
+
+
+def _struct_operands(d: StructDesc, side: int, ent: RowSource, other: Optional[RowSource], rel_table: torch.Tensor,
+                     rel_idx: torch.Tensor, more: Sequence[Tuple[str, Optional[torch.Tensor]]] = ()
+                     ) -> Tuple[torch.device, int, int, int, List[Any]]:
+    """(device, S, W, Wr, the arguments desc .. ld_rel of both entry points) of the structured query."""
+    dev = _same_device([("entity rows", ent.base), ("entity idx", ent.idx), ("relation_embedding", rel_table),
+                        ("relation", rel_idx)] + ([("other rows", other.base), ("other idx", other.idx)] if other else [])
+                       + list(more))
+    W, Wr = d.n_ent_blocks * d.block_width, d.n_rel_blocks * d.block_width
+    S = len(ent)
+    if other is not None and len(other) != S:
+        raise ValueError(f"struct_query: {S} entity rows but {len(other)} other rows")
+    _idx(rel_idx, "relation", S)
+    args = [ctypes.byref(d), side, *_struct_rows(d, ent, "entity rows", W), *_struct_rows(d, other, "other rows", W),
+            *_struct_rows(d, RowSource(rel_table), "relation_embedding", Wr)[:2]]
+    return dev, S, W, Wr, args
+
+
+def struct_query_fwd(d: StructDesc, side: int, ent: RowSource, rel_table: torch.Tensor, rel_idx: torch.Tensor,
+                     other: Optional[RowSource] = None, out: Optional[torch.Tensor] = None,
+                     pos_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(q [S, W], pos [S] or None): the query of the term table `d` for the kept rows `ent` (heads for
+    CORRUPT_TAIL, tails for CORRUPT_HEAD) and, with the triples' `other` rows, the positive scores `<q, other>` from
+    the same launch (`bess_struct_query_fwd`).  Row sources may be views with padded rows; `out`, `pos_out`:
+    preallocated outputs."""
+    dev, S, W, Wr, args = _struct_operands(d, side, ent, other, rel_table, rel_idx, [("q", out), ("pos", pos_out)])
+    q = torch.empty((S, W), dtype=torch.float32, device=dev) if out is None else out
+    pos = None if other is None else (torch.empty((S,), dtype=torch.float32, device=dev) if pos_out is None else pos_out)
+    if pos is not None:
+        _f32(pos, "pos")
+        if pos.numel() != S:
+            raise ValueError(f"struct_query_fwd: pos has {pos.numel()} entries, expected {S}")
+    _launch("bess_struct_query_fwd", dev, *args, rel_idx.data_ptr(), S, q.data_ptr(), _f32_ld(q, "q", (S, W)), _ptr(pos))
+    return q, pos
+
+
+def struct_query_workspace(d: StructDesc, S: int, n_rel: int) -> int:
+    """Bytes of scratch `struct_query_bwd` needs for its relation gradient (host arithmetic)."""
+    nbytes = ctypes.c_int64(0)
+    _check(load().bess_struct_query_workspace(ctypes.byref(d), S, n_rel, ctypes.byref(nbytes)), "bess_struct_query_workspace")
+    return int(nbytes.value)
+
+
+def struct_query_bwd(d: StructDesc, side: int, ent: RowSource, rel_table: torch.Tensor, rel_idx: torch.Tensor,
+                     dq: Optional[torch.Tensor], d_rel: Optional[torch.Tensor], other: Optional[RowSource] = None,
+                     d_pos: Optional[torch.Tensor] = None, seg: Optional["SegmentIndex"] = None,
+                     out: Sequence[Optional[torch.Tensor]] = (None, None)
+                     ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(d_ent [S, W], d_other [S, W] or None) of `struct_query_fwd` for the query gradient dq [S, W] and / or the
+    gradient d_pos [S] of the positive scores; the relation-table gradient is ADDED into d_rel [n_rel, Wr] (None: not
+    computed).  `seg`: the `SegmentIndex` of rel_idx (built here if missing).  Bitwise reproducible, no atomics
+    (`bess_struct_query_bwd`)."""
+    dev, S, W, Wr, args = _struct_operands(d, side, ent, other, rel_table, rel_idx,
+                                           [("dq", dq), ("d_pos", d_pos), ("d_rel", d_rel), ("d_ent", out[0]),
+                                            ("d_other", out[1])])
+    if (other is None) != (d_pos is None) or (dq is None and d_pos is None):
+        raise ValueError("struct_query_bwd: d_pos comes with the other rows, and dq or d_pos is needed")
+    n_rel = int(rel_table.shape[0])
+    d_ent = torch.empty((S, W), dtype=torch.float32, device=dev) if out[0] is None else out[0]
+    d_other = None if other is None else (torch.empty((S, W), dtype=torch.float32, device=dev) if out[1] is None else out[1])
+    if d_pos is not None:
+        _f32(d_pos, "d_pos")
+        if d_pos.numel() != S:
+            raise ValueError(f"struct_query_bwd: d_pos has {d_pos.numel()} entries, expected {S}")
+    segs, ws, nbytes = [0, 0, 0, 0], None, 0
+    if d_rel is not None and S:
+        seg = SegmentIndex(rel_idx, n_rel) if seg is None else seg
+        if seg.n_refs != S:
+            raise ValueError(f"struct_query_bwd: the segment index holds {seg.n_refs} ids, expected {S}")
+        segs = [seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr()]
+        nbytes = struct_query_workspace(d, S, n_rel)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # (kept alive by the stream-ordered allocator)
+    ld = lambda t, name, shape: shape[1] if t is None else _f32_ld(t, name, shape)  # noqa: E731
+    _launch("bess_struct_query_bwd", dev, *args, n_rel, rel_idx.data_ptr(), *segs, S, _ptr(dq), ld(dq, "dq", (S, W)),
+            _ptr(d_pos), d_ent.data_ptr(), ld(d_ent, "d_ent", (S, W)), _ptr(d_other), ld(d_other, "d_other", (S, W)),
+            _ptr(d_rel), ld(d_rel, "d_rel", (n_rel, Wr)), _ptr(ws), nbytes)
+    return d_ent, d_other
+
+
+def _table_ld(t: torch.Tensor, name: str, d: Any, width: Optional[int] = None) -> int:
+    """Leading dimension, in elements, of a [rows, width] matrix (width: d.width if not given) of the table type
+    `d.dtype` whose rows are contiguous."""
+    width = int(d.width if width is None else width)
+    if t.dim() != 2 or t.shape[1] != width or _dtype_code(t) != d.dtype or (width > 1 and t.stride(1) != 1) \
+            or (t.shape[0] > 1 and t.stride(0) < width):
+        raise ValueError(f"`{name}` must be a [rows, {width}] matrix of the descriptor's table type with contiguous "
                          f"rows, got {t.dtype} {tuple(t.shape)} stride {t.stride()}")
-    return int(t.stride(0)) if t.shape[0] > 1 else int(d.width)
+    return int(t.stride(0)) if t.shape[0] > 1 else width
 
 
 def _relation_lse_operands(who: str, d: ModelDesc, head: RowSource, tail: RowSource, rel_table: torch.Tensor,

@@ -57,7 +57,7 @@ class KvsAllBessKGE(OneVsAllBessKGE):
     ) -> None:
         """
         :param negative_sampler: `PlaceholderNegativeSampler("h" | "t")` (nothing is sampled).
-        :param score_fn: TransE, RotatE, DistMult, ComplEx, TuckER, RESCAL or ConvE (tails only).
+        :param score_fn: TransE, RotatE, DistMult, ComplEx, TuckER, RESCAL, StructuredBilinear or ConvE (tails only).
         :param loss_fn: `AllEntitiesBCELoss(n_entity=sharding.n_entity, label_smoothing, loss_scale)`.
         :param known_triples: the triples whose completions are positive labels (usually the training set), global
             ids: a `KnownTripleFilter` or a list of [n, 3] arrays; built once, uploaded to each local device.

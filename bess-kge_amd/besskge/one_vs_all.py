@@ -49,7 +49,8 @@ from besskge.bess import BessKGE, _Batch, _PendingUpdate, _ReplicaStep, _ShardGr
 from besskge.loss import BaseLossFunction, SampledSoftmaxCrossEntropyLoss
 from besskge.negative_sampler import PlaceholderNegativeSampler, ShardedNegativeSampler
 from besskge.regularizer import EmbeddingRegularizer
-from besskge.scoring import RESCAL, BaseScoreFunction, ComplEx, ConvE, DistMult, RotatE, TransE, TuckER
+from besskge.scoring import (RESCAL, BaseScoreFunction, ComplEx, ConvE, DistMult, RotatE, StructuredBilinear, TransE,
+                             TuckER)
 
 
 class OneVsAllBessKGE(BessKGE):
@@ -67,8 +68,8 @@ class OneVsAllBessKGE(BessKGE):
     ) -> None:
         """
         :param negative_sampler: `PlaceholderNegativeSampler("h" | "t")` (nothing is sampled).
-        :param score_fn: TransE, RotatE, DistMult or ComplEx; or TuckER / RESCAL / ConvE (their query against
-            DistMult's kernels; ConvE on either query route, tails only: `[embedding | bias]` rows against `[q | 1]`).
+        :param score_fn: TransE, RotatE, DistMult or ComplEx; or TuckER / RESCAL / ConvE / StructuredBilinear (their
+            query against DistMult's kernels; ConvE on either query route, tails only: `[embedding | bias]` rows against `[q | 1]`).
         :param loss_fn: `SampledSoftmaxCrossEntropyLoss(n_entity=sharding.n_entity)`
             without `proposal_correction`; only its `loss_scale` enters.
         :param evaluation: must be None (ranks over all entities: `AllScoresPipeline`).
@@ -89,9 +90,10 @@ class OneVsAllBessKGE(BessKGE):
                 "h", "t"):
             raise ValueError(f'{me} takes PlaceholderNegativeSampler("h") or ("t"): every entity is a '
                              'candidate, nothing is sampled (scheme "ht" is not built)')
-        if type(score_fn) not in (TransE, RotatE, DistMult, ComplEx, TuckER, RESCAL, ConvE):
+        if type(score_fn) not in (TransE, RotatE, DistMult, ComplEx, TuckER, RESCAL, ConvE, StructuredBilinear):
             raise ValueError(f"{me}: TransE, RotatE, DistMult or ComplEx "
-                             f"(the scorers of bess_neg_score_shared_fwd_lse; TuckER, RESCAL and ConvE through DistMult's), "
+                             f"(the scorers of bess_neg_score_shared_fwd_lse; TuckER, RESCAL, ConvE and StructuredBilinear through "
+                             f"DistMult's), "
                              f"not {type(score_fn).__name__}")
         if type(score_fn) is ConvE and negative_sampler.corruption_scheme == "h":
             raise NotImplementedError("ConvE should not be used with head corruption")

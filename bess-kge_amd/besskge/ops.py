@@ -197,6 +197,28 @@ class RelationQuery(torch.autograd.Function):
         return tuple(None if g is None else g.to(dt) for g, dt in zip(grads, ctx.dtypes)) + (None, None)
 
 
+class StructuredQuery(torch.autograd.Function):
+    """The query of a structured bilinear scorer `(desc, side, rows [S, W], rel_table [n_rel, Wr], rel_idx [S]) ->
+    q [S, W]` for the term table `desc` (`nat.struct_query_fwd`); rows and relation table are of the table type, the
+    gradients come back in their dtypes (the relation table's dense, zero for absent relations).  No double backward."""
+
+    @staticmethod
+    def forward(ctx: Any, desc: nat.StructDesc, side: int, rows: torch.Tensor, rel_table: torch.Tensor,  # type: ignore
+                rel_idx: torch.Tensor) -> torch.Tensor:
+        x, r = _as_rows(rows.detach(), rows.shape[-1]), _idx32(rel_idx)
+        ctx.desc, ctx.side, ctx.shape = desc, side, rows.shape
+        ctx.save_for_backward(x, rel_table.detach(), r)
+        return nat.struct_query_fwd(desc, side, RowSource(x), rel_table.detach(), r)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx: Any, dq: torch.Tensor):  # type: ignore
+        x, rel_table, r = ctx.saved_tensors
+        d_rel = torch.zeros(rel_table.shape, dtype=torch.float32, device=dq.device) if ctx.needs_input_grad[3] else None
+        dx, _ = nat.struct_query_bwd(ctx.desc, ctx.side, RowSource(x), rel_table, r, dq.float().contiguous(), d_rel)
+        return None, None, dx.reshape(ctx.shape).to(x.dtype), None if d_rel is None else d_rel.to(rel_table.dtype), None
+
+
 class ConvEQuery(torch.autograd.Function):
     """ConvE's conv + channel affine + ReLU + channel mask + FC product `(x [S, Cin, H2, W], K [Cout, Cin, kh, kw],
     a [Cout], b [Cout], m [S, Cout] | None, Wfc [d, F]) -> y [S, d]` (`nat.conve_query_fwd`): the `[S, F]` feature map

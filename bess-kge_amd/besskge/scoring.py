@@ -1283,3 +1283,183 @@ class BoxE(_TorchQueryHooks, DistanceBasedScoreFunction):
 
     def score_tails(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
         return self._score_candidates(nat.CORRUPT_TAIL, head_emb, relation_id, tail_emb)
+
+
+# --------------------------------------------------------------------------- #
+# structured bilinear scorers: QuatE, SimplE, CP, ANALOGY, AutoSF from one term table
+_Term = Tuple[int, int, int, float]
+
+
+class StructuredBilinear(MatrixDecompositionScoreFunction):
+    """`score(h, r, t) = sum over terms (i, j, k, c) of c * sum_x h[i d + x] r[j d + x] t[k d + x]`: entity rows are
+    `n_entity_blocks` (K) blocks of `block_size` (d) columns, relation rows `n_relation_blocks` (Kr) blocks.
+    DistMult is K = 1 with one term, ComplEx K = 2 with four, QuatE K = 4 with the 16 of the Hamilton product; an
+    AutoSF result is such a list (`from_autosf`); `QuatE`, `SimplE`, `CP` and `ANALOGY` below fill in their tables.
+
+    The score is bilinear in the candidate: the query `[term][column]` transform and its backward are the kernels of
+    csrc/struct_query.hip (`nat.struct_query_fwd / _bwd`, no autograd graph over the batch, the relation gradient
+    summed per relation without atomics: bitwise reproducible), and every candidate-side path is DistMult's.
+    `relation_unit_norm`: every relation column is divided by its norm over the Kr blocks before use (QuatE's unit
+    quaternion); the backward differentiates through it."""
+
+    _scorer_id = nat.DISTMULT  # candidates see a dot product with the query
+    bilinear_candidates = True
+    supports_fused_segments = True
+    supports_fused_forward = False
+    supports_fused_query_triple = False
+
+    def __init__(
+        self,
+        negative_sample_sharing: bool,
+        sharding: Sharding,
+        n_relation_type: int,
+        block_size: int,
+        terms: List[_Term],
+        n_entity_blocks: int,
+        n_relation_blocks: int,
+        entity_initializer: _Init = [init_KGE_normal],
+        relation_initializer: _Init = [init_KGE_normal],
+        inverse_relations: bool = False,
+        relation_unit_norm: bool = False,
+        **placement: Any,
+    ) -> None:
+        super().__init__(negative_sample_sharing)
+        K, Kr, d = int(n_entity_blocks), int(n_relation_blocks), int(block_size)
+        if not (1 <= K <= nat.STRUCT_MAX_BLOCKS and 1 <= Kr <= nat.STRUCT_MAX_BLOCKS and d >= 1):
+            raise ValueError(f"StructuredBilinear: 1 to {nat.STRUCT_MAX_BLOCKS} entity and relation blocks of at least one "
+                             f"column, got {n_entity_blocks}, {n_relation_blocks} blocks of {block_size}")
+        terms = [(int(i), int(j), int(k), float(c)) for i, j, k, c in terms]
+        if not 1 <= len(terms) <= nat.STRUCT_MAX_TERMS:
+            raise ValueError(f"StructuredBilinear: 1 to {nat.STRUCT_MAX_TERMS} terms, got {len(terms)}")
+        for i, j, k, c in terms:
+            if not (0 <= i < K and 0 <= j < Kr and 0 <= k < K):
+                raise ValueError(f"StructuredBilinear: term {(i, j, k)} names a block outside ({K}, {Kr}, {K})")
+            if c != c or c in (float("inf"), float("-inf")):
+                raise ValueError(f"StructuredBilinear: the coefficient of term {(i, j, k)} is not finite")
+        if len({t[:3] for t in terms}) != len(terms):
+            raise ValueError("StructuredBilinear: a block triple (i, j, k) is named twice")
+        self.terms, self.n_entity_blocks, self.n_relation_blocks, self.block_size = terms, K, Kr, d
+        self.relation_unit_norm = bool(relation_unit_norm)
+        self._allocate(
+            sharding, n_relation_type, inverse_relations, entity_initializer, relation_initializer, K * d, Kr * d,
+            "StructuredBilinear requires `n_entity_blocks * block_size` embedding parameters for each entity"
+            " and `n_relation_blocks * block_size` for each relation",
+            placement=placement,
+        )
+
+    @classmethod
+    def from_autosf(cls, negative_sample_sharing: bool, sharding: Sharding, n_relation_type: int, block_size: int,
+                    blocks: List[List[int]], **kwargs: Any) -> "StructuredBilinear":
+        """The scoring function AutoSF prints as a K x K signed block matrix: entry (i, k) = +-(j + 1) puts relation
+        block j between head block i and tail block k with that sign, 0 is no term."""
+        K = len(blocks)
+        if K < 1 or any(len(row) != K for row in blocks):
+            raise ValueError("StructuredBilinear.from_autosf: a square matrix of signed relation block numbers")
+        terms = [(i, abs(int(v)) - 1, k, 1.0 if v > 0 else -1.0) for i, row in enumerate(blocks)
+                 for k, v in enumerate(row) if v]
+        if any(t[1] >= K for t in terms):
+            raise ValueError(f"StructuredBilinear.from_autosf: entries are 0 or +-1 .. +-{K}")
+        return cls(negative_sample_sharing, sharding, n_relation_type, block_size, terms, K, K, **kwargs)
+
+    def kernel_desc(self) -> nat.ModelDesc:
+        d = super().kernel_desc()
+        d.rel_width = d.width  # the dot-product kernels only see entity rows and queries
+        return d
+
+    def struct_desc(self) -> nat.StructDesc:
+        """Descriptor of the term table for the tables' current type (built once per type)."""
+        key = self.relation_embedding.dtype
+        cached = self.__dict__.get("_struct_desc_cache")
+        if cached is None or cached[0] != key:
+            cached = (key, nat.struct_desc(self.relation_embedding, self.n_entity_blocks, self.n_relation_blocks,
+                                           self.block_size, self.terms, self.relation_unit_norm))
+            self.__dict__["_struct_desc_cache"] = cached
+        return cached[1]
+
+    # hooks of the fused step: the native entry points, no autograd graph over S rows
+    def query_fwd(self, side: int, ent: nat.RowSource, rel_idx: torch.Tensor) -> Tuple[torch.Tensor, Any]:
+        return nat.struct_query_fwd(self.struct_desc(), side, ent, self.relation_embedding.data, rel_idx)[0], None
+
+    def query_bwd(self, side: int, ent: nat.RowSource, rel_idx: torch.Tensor, ctx: Any, dq: torch.Tensor,
+                  d_rel: torch.Tensor) -> torch.Tensor:
+        return nat.struct_query_bwd(self.struct_desc(), side, ent, self.relation_embedding.data, rel_idx, dq, d_rel)[0]
+
+    def triple_fwd(self, head: nat.RowSource, tail: nat.RowSource, rel_idx: torch.Tensor) -> Tuple[torch.Tensor, Any]:
+        return nat.struct_query_fwd(self.struct_desc(), nat.CORRUPT_TAIL, head, self.relation_embedding.data, rel_idx,
+                                    other=tail)[1], None
+
+    def triple_bwd(self, head: nat.RowSource, tail: nat.RowSource, rel_idx: torch.Tensor, ctx: Any,
+                   d_pos: torch.Tensor, d_rel: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        return nat.struct_query_bwd(self.struct_desc(), nat.CORRUPT_TAIL, head, self.relation_embedding.data, rel_idx,
+                                    None, d_rel, other=tail, d_pos=d_pos.reshape(-1).contiguous())
+
+    # public API (differentiable: ops.StructuredQuery + ops.ReduceNegatives)
+    def _query(self, side: int, kept: torch.Tensor, relation_id: torch.Tensor) -> torch.Tensor:
+        return ops.StructuredQuery.apply(self.struct_desc(), side, self._table_dtype(kept), self.relation_embedding,
+                                         relation_id)
+
+    def score_triple(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return torch.sum(self._query(nat.CORRUPT_TAIL, head_emb, relation_id) * tail_emb.float(), dim=-1)
+
+    def _score_candidates(self, side: int, kept: torch.Tensor, relation_id: torch.Tensor,
+                          candidates: torch.Tensor) -> torch.Tensor:
+        return ops.ReduceNegatives.apply(self.kernel_desc(), bool(self.negative_sample_sharing),
+                                         self._query(side, kept, relation_id), self._table_dtype(candidates))
+
+    def score_heads(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_HEAD, tail_emb, relation_id, head_emb)
+
+    def score_tails(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_TAIL, head_emb, relation_id, tail_emb)
+
+
+#: h_i r_j enters component k of the Hamilton product h (x) r with this sign; the score is <h (x) r, t>
+QUATE_TERMS: List[_Term] = [
+    (0, 0, 0, 1.0), (0, 1, 1, 1.0), (0, 2, 2, 1.0), (0, 3, 3, 1.0),
+    (1, 0, 1, 1.0), (1, 1, 0, -1.0), (1, 2, 3, 1.0), (1, 3, 2, -1.0),
+    (2, 0, 2, 1.0), (2, 1, 3, -1.0), (2, 2, 0, -1.0), (2, 3, 1, 1.0),
+    (3, 0, 3, 1.0), (3, 1, 2, 1.0), (3, 2, 1, -1.0), (3, 3, 0, -1.0)]
+DISTMULT_TERMS: List[_Term] = [(0, 0, 0, 1.0)]
+#: Re<h r, conj t> on [re | im] rows
+COMPLEX_TERMS: List[_Term] = [(0, 0, 0, 1.0), (1, 1, 0, -1.0), (0, 1, 1, 1.0), (1, 0, 1, 1.0)]
+
+
+def QuatE(negative_sample_sharing: bool, sharding: Sharding, n_relation_type: int, embedding_size: int,
+          relation_unit_norm: bool = True, **kwargs: Any) -> StructuredBilinear:
+    """QuatE (Zhang et al. 2019): `<h (x) r / |r|, t>` on quaternion rows `[a | b | c | d]` of 4 * embedding_size."""
+    return StructuredBilinear(negative_sample_sharing, sharding, n_relation_type, embedding_size, QUATE_TERMS, 4, 4,
+                              relation_unit_norm=relation_unit_norm, **kwargs)
+
+
+def SimplE(negative_sample_sharing: bool, sharding: Sharding, n_relation_type: int, embedding_size: int,
+           **kwargs: Any) -> StructuredBilinear:
+    """SimplE (Kazemi & Poole 2018): entity rows `[head role | tail role]`, relation rows `[r | r_inv]`, the average of
+    `<h_head, r, t_tail>` and `<t_head, r_inv, h_tail>`."""
+    return StructuredBilinear(negative_sample_sharing, sharding, n_relation_type, embedding_size,
+                              [(0, 0, 1, 0.5), (1, 1, 0, 0.5)], 2, 2, **kwargs)
+
+
+def CP(negative_sample_sharing: bool, sharding: Sharding, n_relation_type: int, embedding_size: int,
+       **kwargs: Any) -> StructuredBilinear:
+    """Canonical polyadic decomposition: `<h_head, r, t_tail>` on role-split entity rows `[head role | tail role]`."""
+    return StructuredBilinear(negative_sample_sharing, sharding, n_relation_type, embedding_size, [(0, 0, 1, 1.0)], 2, 1,
+                              **kwargs)
+
+
+def ANALOGY(negative_sample_sharing: bool, sharding: Sharding, n_relation_type: int, embedding_size: int,
+            scalar_share: float = 0.5, **kwargs: Any) -> StructuredBilinear:
+    """ANALOGY (Liu et al. 2017): a DistMult part and a ComplEx part side by side.  Rows are four blocks
+    `[scalar | scalar | re | im]` of `embedding_size // 4` columns: `scalar_share` = 0.5 (two scalar blocks) is the
+    paper's half-and-half split, 0 leaves ComplEx and 1 DistMult on blocks of `embedding_size // 2` and
+    `embedding_size` columns."""
+    if scalar_share == 0.5 and embedding_size % 4 == 0:
+        return StructuredBilinear(negative_sample_sharing, sharding, n_relation_type, embedding_size // 4,
+                                  [(0, 0, 0, 1.0), (1, 1, 1, 1.0)] + [(i + 2, j + 2, k + 2, c) for i, j, k, c in COMPLEX_TERMS],
+                                  4, 4, **kwargs)
+    if scalar_share == 0.0 and embedding_size % 2 == 0:
+        return StructuredBilinear(negative_sample_sharing, sharding, n_relation_type, embedding_size // 2, COMPLEX_TERMS,
+                                  2, 2, **kwargs)
+    if scalar_share == 1.0:
+        return StructuredBilinear(negative_sample_sharing, sharding, n_relation_type, embedding_size, DISTMULT_TERMS, 1, 1,
+                                  **kwargs)
+    raise ValueError("ANALOGY: scalar_share is 0, 0.5 (embedding_size a multiple of 4) or 1")

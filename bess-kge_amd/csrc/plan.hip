@@ -148,6 +148,8 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_conve_stats_bwd),
     BESS_PLAN_FN(bess_relation_lse_fwd),
     BESS_PLAN_FN(bess_relation_lse_bwd),
+    BESS_PLAN_FN(bess_struct_query_fwd),
+    BESS_PLAN_FN(bess_struct_query_bwd),
 };
 #undef BESS_PLAN_FN
 

@@ -10,7 +10,7 @@ queries and report filtered-free MRR / hits@10.
                                              [--training 1vsall | kvsall [--label-smoothing 0.1]]
                                             [--relation-prediction 0.5]
                                              [--scorer TuckER --relation-size 16 [--tucker-route relation]]
-                                             [--scorer RESCAL]
+                                             [--scorer RESCAL | QuatE | SimplE | CP]
                                              [--scorer ConvE [--conve-route fused]]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
@@ -75,7 +75,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--n-shard", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--scorer", default="TransE", choices=["TransE", "RotatE", "DistMult", "ComplEx", "PairRE", "TranS", "TuckER",
-                                                                "RESCAL", "ConvE"])
+                                                                "RESCAL", "ConvE", "QuatE", "SimplE", "CP"])
     ap.add_argument("--relation-size", type=int, default=16, help="width of the relation rows of --scorer TuckER")
     ap.add_argument("--tucker-route", default="outer", choices=["outer", "relation"],
                     help="TuckER's query_route: per-triple outer product, or one mixed matrix per relation")
@@ -111,9 +111,10 @@ def main(argv=None) -> dict:
     k_vs_all = args.training == "kvsall"
     one_vs_all = args.training == "1vsall" or k_vs_all
     if one_vs_all and (args.proposal_correction or args.negative_weights != "uniform" or args.loss != "logsigmoid"
-                       or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx", "TuckER", "RESCAL", "ConvE")):
+                       or args.scorer not in ("TransE", "RotatE", "DistMult", "ComplEx", "TuckER", "RESCAL", "ConvE", "QuatE",
+                                              "SimplE", "CP")):
         ap.error(f"--training {args.training} samples nothing and brings its own loss: TransE / RotatE / DistMult / ComplEx "
-                 "/ TuckER / RESCAL / ConvE, "
+                 "/ TuckER / RESCAL / ConvE / QuatE / SimplE / CP, "
                  "without --negative-weights / --loss / --proposal-correction")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)

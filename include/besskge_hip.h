@@ -1281,6 +1281,58 @@ int bess_relation_lse_bwd(const bess_model_desc* d, const void* head_base, int64
                           int64_t S, float* d_head, int64_t ld_dhead, float* d_tail, int64_t ld_dtail, float* d_rel,
                           int64_t ld_drel, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the structured bilinear query: QuatE, SimplE, CP, ANALOGY, AutoSF from one term table (csrc/struct_query.hip)
+ * Entity rows are n_ent_blocks (K) blocks of block_width (d) columns, W = K d; relation rows n_rel_blocks (Kr)
+ * blocks, Wr = Kr d.  With the n_terms terms (ti, tj, tk, tc)
+ *     score(h, r, t) = sum_terms tc * sum_x h[ti d + x] r[tj d + x] t[tk d + x]
+ * (DistMult: K = 1, one term; ComplEx: K = 2, four; QuatE: K = 4, the 16 of the Hamilton product).  The score is a
+ * dot product of the candidate with the query, so candidates are scored by the BESS_DISTMULT entry points:
+ *     BESS_CORRUPT_TAIL (ent = heads):  q[i, tk d + x] += tc ent[i, ti d + x] r[tj d + x]
+ *     BESS_CORRUPT_HEAD (ent = tails):  q[i, ti d + x] += tc r[tj d + x] ent[i, tk d + x]
+ * relation_unit_norm != 0: column x of the relation row is first divided by sqrt(sum_j r[j d + x]^2) over its Kr
+ * blocks (QuatE's unit quaternion; a zero norm is undefined); the backward differentiates through it.
+ * Entity rows and the optional other rows (the triple's true tail / head) are row sources (base, ld, idx; idx NULL:
+ * row i) of desc.dtype (fp32 or fp16, converted on load), rel_table [n_rel, Wr] of the same type with rel_idx[i] in
+ * [0, n_rel) - an id outside is an out-of-bounds read.  q and every gradient are fp32; leading dimensions in
+ * elements.  With other rows, pos[i] = <q[i], other[i]> comes from the same launch (pos and other_base are both
+ * NULL or neither); q is bitwise the same either way.
+ * bess_struct_query_bwd, for the query gradient g[i] = dq[i] + d_pos[i] other[i] (dq or d_pos may be NULL, not both;
+ * d_pos, other_base and d_other come together): d_ent [S, W] and d_other[i] = d_pos[i] q[i] are written per triple;
+ * d_rel [n_rel, Wr] (may be NULL) is ADDED to, one sum per relation over the triples that name it.  The batch comes
+ * grouped by relation as bess_build_segment_index builds it from rel_idx.  No float atomics: a segment of up to 32
+ * triples is summed by one workgroup in sorted order; a longer one is cut into 16 shares whose partial rows go
+ * through the workspace (bess_struct_query_workspace bytes = (S / 32 + 1) * 16 * Wr * 4, 16-byte aligned, nothing to
+ * clear) and are added in share order.  Every output is bitwise reproducible; nothing reads back to the host.
+ * Limits: more than BESS_STRUCT_MAX_BLOCKS blocks, more than BESS_STRUCT_MAX_TERMS terms, d > 2^21 or S > 2^30 are
+ * BESS_EUNSUPPORTED (before any launch); a term that names a block outside the row, or whose coefficient is not
+ * finite, is BESS_EINVAL.  Terms that name the same (ti, tj, tk) add up.  Block widths, leading dimensions or
+ * pointers that are not multiples of 4 scalars take scalar loads. */
+#define BESS_STRUCT_MAX_BLOCKS 8
+#define BESS_STRUCT_MAX_TERMS 64
+typedef struct bess_struct_desc {
+    int32_t dtype;        /* BESS_F32 | BESS_F16: tables and row sources */
+    int32_t n_ent_blocks; /* K  */
+    int32_t n_rel_blocks; /* Kr */
+    int32_t block_width;  /* d  */
+    int32_t n_terms;
+    int32_t relation_unit_norm;
+    int32_t reserved[2];
+    int32_t ti[BESS_STRUCT_MAX_TERMS], tj[BESS_STRUCT_MAX_TERMS], tk[BESS_STRUCT_MAX_TERMS];
+    float tc[BESS_STRUCT_MAX_TERMS];
+} bess_struct_desc;
+int bess_struct_query_workspace(const bess_struct_desc* desc, int64_t S, int64_t n_rel, int64_t* bytes);
+int bess_struct_query_fwd(const bess_struct_desc* desc, int32_t side, const void* ent_base, int64_t ld_ent,
+                          const int32_t* ent_idx, const void* other_base, int64_t ld_other, const int32_t* other_idx,
+                          const void* rel_table, int64_t ld_rel, const int32_t* rel_idx, int64_t S, float* q,
+                          int64_t ldq, float* pos, void* stream);
+int bess_struct_query_bwd(const bess_struct_desc* desc, int32_t side, const void* ent_base, int64_t ld_ent,
+                          const int32_t* ent_idx, const void* other_base, int64_t ld_other, const int32_t* other_idx,
+                          const void* rel_table, int64_t ld_rel, int64_t n_rel, const int32_t* rel_idx,
+                          const int32_t* refs_sorted, const int32_t* seg_rows, const int32_t* seg_offsets,
+                          const int32_t* n_seg, int64_t S, const float* dq, int64_t lddq, const float* d_pos,
+                          float* d_ent, int64_t ld_dent, float* d_other, int64_t ld_dother, float* d_rel,
+                          int64_t ld_drel, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- recorded steps -----------------------------------------------------------
  * A step of this library can be captured into a hipGraph as a whole (every call is asynchronous on the
  * caller's stream, every clear is a kernel).  bess_graph_node_counts tells what a captured graph holds:
