@@ -90,6 +90,7 @@ OPT_SGD, OPT_ADAGRAD, OPT_ADAM = 0, 1, 2
 FLAG_FP32_MATH = 1  # BESS_FLAG_FP32_MATH (ModelDesc.reserved[0] of the four native scorers)
 FLAG_PREZEROED = 2  # BESS_FLAG_PREZEROED: the targets of bess_neg_score_shared_bwd are zero on entry
 FLAG_DNEG_BY_ROW = 4  # BESS_FLAG_DNEG_BY_ROW: bess_neg_score_pertriple_bwd stores d_neg at row neg_idx[k] of a row-space matrix
+FLAG_GRAM_L2 = 8  # BESS_FLAG_GRAM_L2: TransE / RotatE with p = 2 may score shared candidates through the matrix-core product
 
 
 class KillDesc(ctypes.Structure):

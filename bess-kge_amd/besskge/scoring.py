@@ -95,7 +95,7 @@ class BaseScoreFunction(torch.nn.Module, ABC):
         step asks for it five times."""
         rel, ent = self.relation_embedding, self.entity_embedding
         key = (rel.dtype, int(ent.shape[-1]), int(rel.shape[-1]), int(getattr(self, "scoring_norm", 0)),
-               bool(getattr(self, "fp32_math", False)))
+               bool(getattr(self, "fp32_math", False)), getattr(self, "distance_route", "direct") == "gram")
         cached = self.__dict__.get("_kernel_desc_cache")
         if cached is not None and cached[0] == key:
             return cached[1]
@@ -107,6 +107,8 @@ class BaseScoreFunction(torch.nn.Module, ABC):
         d.rel_width = key[2]
         if 0 <= self._scorer_id <= nat.COMPLEX and key[4]:
             d.reserved[0] = nat.FLAG_FP32_MATH
+        if key[5]:
+            d.reserved[0] |= nat.FLAG_GRAM_L2
         self.__dict__["_kernel_desc_cache"] = (key, d)
         return d
 
@@ -308,6 +310,18 @@ class DistanceBasedScoreFunction(BaseScoreFunction, ABC):
         self.negative_sample_sharing = negative_sample_sharing
         self.scoring_norm = int(scoring_norm)
 
+    def _set_distance_route(self, distance_route: str) -> None:
+        """`distance_route` of TransE / RotatE: "direct" scores shared candidates with the tile kernels of the
+        p-norms; "gram" (p = 2 only) permits ||q - e||^2 = ||q||^2 + ||e||^2 - 2 q.e through the split-fp16 matrix-core
+        product wherever the bilinear scorers take it (`BESS_FLAG_GRAM_L2`: all-entities scores, ranks, pruned stores,
+        log-sum-exp and the backward; not the BCE calls of KvsAll), close pairs recomputed directly in the forward.
+        Parameters and state dicts are those of "direct"; the attribute can be reassigned."""
+        if distance_route not in ("direct", "gram"):
+            raise ValueError(f'{type(self).__name__}: distance_route is "direct" or "gram", got {distance_route!r}')
+        if distance_route == "gram" and self.scoring_norm != 2:
+            raise ValueError(f'{type(self).__name__}: distance_route="gram" is the Euclidean distance, scoring_norm=2')
+        self.distance_route = distance_route
+
     def reduce_embedding(self, v: torch.Tensor) -> torch.Tensor:
         """p-norm over the embedding dimension (reference scoring.py:163-174)."""
         return torch.norm(v, p=self.scoring_norm, dim=-1)
@@ -362,9 +376,11 @@ class TransE(DistanceBasedScoreFunction):
         entity_initializer: _Init = [init_KGE_uniform],
         relation_initializer: _Init = [init_KGE_uniform],
         inverse_relations: bool = False,
+        distance_route: str = "direct",
         **placement: Any,
     ) -> None:
         super().__init__(negative_sample_sharing, scoring_norm)
+        self._set_distance_route(distance_route)
         self._allocate(
             sharding, n_relation_type, inverse_relations, entity_initializer,
             relation_initializer, embedding_size, embedding_size,
@@ -391,9 +407,11 @@ class RotatE(DistanceBasedScoreFunction):
         entity_initializer: _Init = [init_KGE_uniform],
         relation_initializer: _Init = [init_uniform_rotation],
         inverse_relations: bool = False,
+        distance_route: str = "direct",
         **placement: Any,
     ) -> None:
         super().__init__(negative_sample_sharing, scoring_norm)
+        self._set_distance_route(distance_route)
         self._allocate(
             sharding, n_relation_type, inverse_relations, entity_initializer,
             relation_initializer, 2 * embedding_size, embedding_size,

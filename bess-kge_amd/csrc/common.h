@@ -38,6 +38,13 @@ inline int reduce_of(const bess_model_desc* d) {
     if (!is_distance(d->scorer)) return RED_DOT;
     return d->norm_p == 1 ? RED_L1 : RED_L2;
 }
+// the Euclidean distance may go through the split-fp16 product (BESS_FLAG_GRAM_L2; BESS_FLAG_FP32_MATH wins)
+inline bool gram_l2(const bess_model_desc* d) {
+    return (d->scorer == BESS_TRANSE || d->scorer == BESS_ROTATE) && d->norm_p == 2 &&
+           (d->reserved[0] & (BESS_FLAG_GRAM_L2 | BESS_FLAG_FP32_MATH)) == BESS_FLAG_GRAM_L2;
+}
+// scorers whose shared-candidate scores come out of a matrix-core product when shape and workspace fit
+inline bool product_route(const bess_model_desc* d) { return reduce_of(d) == RED_DOT || gram_l2(d); }
 
 // fp32 MFMA GEMMs of the bilinear scorers (gemm_mfma.hip)
 // (run_if: optional device word; the kernels return at once while it is 0 - the conditional fallback of the split path)
@@ -83,12 +90,21 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
                    bool diag = false,  // diag: S == N, out [S, 128] receives the diagonal 128 x 128 tiles only
                    float* lse_state = nullptr,  // [S, 2]: merge every row's log-sum-exp in (the front of ws holds
                                                 // gemm_split_lse_parts bytes of tile partials; nothing is stored)
-                   bool bce = false);  // lse_state is (sum of softplus(s), sum of s) instead, added to
+                   bool bce = false,  // lse_state is (sum of softplus(s), sum of s) instead, added to
+                   // not NULL: the scores are -||q - e||_2 out of the product (wave_tile_distance in front of every
+                   // epilogue; the front of ws, behind the partials, holds gemm_split_norm_bytes of norms).  It receives
+                   // the device word that is non-zero when an operand was outside the fp16 range: nothing was stored
+                   // then and the caller's direct kernels, gated on that word, compute the scores
+                   const int32_t** dist_flag = nullptr);
 int64_t gemm_split_lse_parts(int64_t S, int64_t N);
+int64_t gemm_split_norm_bytes(int64_t S, int64_t N);
 int64_t gemm_split_bwd_workspace(int64_t S, int64_t N, int W);
+int64_t gemm_split_bwd_dist_workspace(int64_t S, int64_t N, int W);
+// (scores: G is the gradient of the distance scores `scores` - the backward of the distance route, through
+// gemm_split_bwd_dist_workspace bytes)
 int gemm_split_bwd(int dtype, const float* G, int64_t ldg, int64_t S, const float* Q, const void* E,
                    const int32_t* idx, int64_t N, int W, float* dQ, float* dE, void* ws, int64_t ws_bytes,
-                   hipStream_t st);
+                   hipStream_t st, const float* scores = nullptr, int64_t ld_scores = 0);
 int gemm_dot_dq(int dtype, const float* G, int64_t ldg, int64_t S, const void* E, const int32_t* idx, int64_t N,
                 int W, float* dQ, hipStream_t st, const int32_t* run_if = nullptr);
 int gemm_dot_de(const float* G, int64_t ldg, int64_t S, const float* Q, int64_t N, int W, float* dE,

@@ -342,6 +342,115 @@ __device__ __forceinline__ void interleave_reads() {
     __builtin_amdgcn_sched_group_barrier(0x008, N_MM - N_RD, 0);
 }
 
+// ---- Euclidean distance out of the product (TransE / RotatE, p = 2, BESS_FLAG_GRAM_L2) ------------------------
+//     ||q - e||^2 = ||q||^2 + ||e||^2 - 2 q.e
+// The pre-pass leaves nq[m] = ||q_m||^2 and ne[n] = ||e_n||^2 (fp32 sums of the values it splits) beside the images;
+// a finished wave tile turns every accumulator `dot` into s = -sqrt(max(0, nq + ne - 2 dot)) IN FRONT of the epilogue,
+// which then stores, prunes, counts or reduces distances instead of products without knowing it.  The expanded form
+// is off by eta ~ c 2^-22 (nq + ne) on d^2 (the product's 2^-22 per term, Cauchy-Schwarz over k, and the fp32 norms),
+// i.e. by eta / (2 d^2) relative on d: harmless for ordinary pairs, unbounded as d -> 0 - where the true completion of
+// a trained query sits.  So a pair with nq + ne - 2 dot < GRAM_TAU (nq + ne) is recomputed by the lane that owns it
+// as sum_k (q_k - e_k)^2 in fp32 from the rows themselves (plain loads, a lane-divergent loop: rare, and an input whose
+// candidates all equal the query is slow, not wrong; an exact duplicate scores exactly 0).  What is not recomputed
+// has d^2 >= GRAM_TAU (nq + ne) and therefore a relative error <= c 2^-22 / (2 GRAM_TAU) = c 2^-15 = c 3.1e-5:
+// inside the parity tolerance (rtol 1e-4) for c <= 3.2 (measured: DESIGN section 38).
+struct DistSrc {
+    const float* nq;     // [rows of A]
+    const float* ne;     // [rows of B]
+    const float* Q;      // the query rows, f32 [M, W]
+    const void* E;       // the candidates' table (B_LO: f32, else f16), rows through idx when there is one
+    const int32_t* idx;
+    int W;
+};
+constexpr float GRAM_TAU = 1.f / 256.f;
+
+template <bool B_LO>
+__device__ __forceinline__ float direct_dist2(const DistSrc& ds, int64_t m, int64_t n) {
+    using T = std::conditional_t<B_LO, float, half_t>;
+    const float* __restrict__ q = ds.Q + m * ds.W;
+    const T* __restrict__ e = static_cast<const T*>(ds.E) + (ds.idx ? static_cast<int64_t>(ds.idx[n]) : n) * ds.W;
+    float s = 0.f;
+    for (int k = 0; k < ds.W; ++k) {
+        const float t = q[k] - to_f32(e[k]);
+        s = fmaf(t, t, s);
+    }
+    return s;
+}
+
+// the accumulators of a finished wave tile, in place: main <- -distance, corr <- 0 (what the epilogues then read as
+// main + corr / 2048).  One load of nq per lane (row m0 + lane, read out per row with v_readlane as the thresholds of
+// the counting epilogue are), two of ne (the lane's two columns); rows / columns past the end are clamped and never
+// marked close - their values are dropped by every epilogue.  Returns the lane's close pairs, whose scores are still
+// the expanded form's.
+__device__ __forceinline__ unsigned long long wave_tile_distance(f32x16 (&accm)[2][2], f32x16 (&accc)[2][2], int64_t m0,
+                                                                 int64_t n0, int64_t M, int64_t N, const DistSrc& ds,
+                                                                 int l31, int lk) {
+    const int l64 = threadIdx.x & 63;
+    const int nqv = __builtin_bit_cast(int, ds.nq[min(m0 + l64, M - 1)]);
+    const int64_t c0 = n0 + l31, c1 = c0 + 32;
+    const float nev[2] = {ds.ne[min(c0, N - 1)], ds.ne[min(c1, N - 1)]};
+    const bool cok[2] = {c0 < N, c1 < N};
+    unsigned long long close = 0;  // bit i * 32 + r * 2 + j: accumulator [i][j][r] of this lane is a close pair
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rr = i * 32 + (r & 3) + 8 * (r >> 2);  // rows rr (lk = 0) and rr + 4 (lk = 1)
+            const float a0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(nqv, rr));
+            const float a1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(nqv, rr + 4));
+            const float a = lk ? a1 : a0;
+            const bool rok = m0 + 4 * lk + rr < M;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const float t = a + nev[j];
+                const float d2 = fmaf(-2.f, accm[i][j][r] + accc[i][j][r] * (1.f / 2048.f), t);
+                if (d2 < GRAM_TAU * t && rok && cok[j]) close |= 1ull << (i * 32 + r * 2 + j);
+                accm[i][j][r] = -__builtin_amdgcn_sqrtf(fmaxf(d2, 0.f));  // (v_sqrt_f32: 1 ulp, exact at 0)
+                accc[i][j][r] = 0.f;
+            }
+            __builtin_amdgcn_sched_barrier(0);  // one row at a time: interleaved, the 64 roots cost more scratch
+        }
+    return close;
+}
+
+// The close pairs of a lane, one per trip of a lane-divergent loop (ONE copy of the row walk: unrolled into the 64
+// places of the transform it cost far more scratch).  The value reaches its accumulator through 64 selects, so no
+// register is indexed.
+template <bool B_LO>
+__device__ __forceinline__ void wave_tile_close_pairs(unsigned long long close, f32x16 (&accm)[2][2], int64_t m0,
+                                                      int64_t n0, const DistSrc& ds, int l31, int lk) {
+    while (close) {
+        const int b = __builtin_ctzll(close);
+        close &= close - 1;
+        const int r = (b >> 1) & 15, rr = (b >> 5) * 32 + (r & 3) + 8 * (r >> 2);
+        const float s = -__builtin_amdgcn_sqrtf(direct_dist2<B_LO>(ds, m0 + 4 * lk + rr, n0 + l31 + (b & 1) * 32));
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    if (b == i * 32 + q * 2 + j) accm[i][j][q] = s;
+    }
+}
+
+template <int EPI>
+__device__ __forceinline__ void wave_tile_epilogue(const f32x16 (&accm)[2][2], const f32x16 (&accc)[2][2], int64_t m0,
+                                                   int64_t n0, float* __restrict__ c0, int64_t ldc, int64_t M, int64_t N,
+                                                   const float* __restrict__ thr, uint8_t* __restrict__ pflags,
+                                                   int64_t ldf, const CountArgs& cnt, int l31, int lk);
+
+// distances instead of products: the transform and the close pairs in front of the epilogue of a finished wave tile
+template <bool B_LO, int EPI>
+__device__ __forceinline__ void wave_tile_distance_epilogue(f32x16 (&accm)[2][2], f32x16 (&accc)[2][2], int64_t m0,
+                                                            int64_t n0, float* __restrict__ c0, int64_t ldc, int64_t M,
+                                                            int64_t N, const float* __restrict__ thr,
+                                                            uint8_t* __restrict__ pflags, int64_t ldf,
+                                                            const CountArgs& cnt, const DistSrc& ds, int l31, int lk) {
+    wave_tile_close_pairs<B_LO>(wave_tile_distance(accm, accc, m0, n0, M, N, ds, l31, lk), accm, m0, n0, ds, l31, lk);
+    wave_tile_epilogue<EPI>(accm, accc, m0, n0, c0, ldc, M, N, thr, pflags, ldf, cnt, l31, lk);
+}
+
 // A finished wave tile (rows m0 .., columns n0 .. of the M x N product): main + corr / 2048 -> C, where c0 points at
 // this lane's first element.  C/D layout of the 32x32 MFMA: col = lane & 31 (l31),
 // row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) (lk).
@@ -490,7 +599,8 @@ __device__ __forceinline__ void wave_tile_epilogue(const f32x16 (&accm)[2][2], c
 }
 
 // A, B: split images of M and N rows (n_slice lines each); C[m, n] = A[m] . B[n]
-template <bool B_LO, int EPI>  // EPI: see wave_tile_epilogue
+// EPI: see wave_tile_epilogue; Dist: nothing (products), or one DistSrc (wave_tile_distance in front of the epilogue)
+template <bool B_LO, int EPI, typename... Dist>
 // Split K (the backward products have few output tiles and a long k): a "tile" index t stands for
 // output tile t / ksplit and the k range [t % ksplit, +1) * n_slice lines; part p of an output
 // tile goes to C + p * part_stride (summed in a fixed order by k_sum_parts: deterministic).
@@ -499,7 +609,8 @@ __global__ __launch_bounds__(512) void k_gemm_split_f16(const char* __restrict__
                                                         float* __restrict__ C, int64_t ldc, int tiles_x,
                                                         int n_tiles, int ksplit, int64_t part_stride,
                                                         const int32_t* __restrict__ range_flag, const float* __restrict__ thr,
-                                                        uint8_t* __restrict__ pflags, int64_t ldf, CountArgs cnt) {
+                                                        uint8_t* __restrict__ pflags, int64_t ldf, CountArgs cnt,
+                                                        Dist... ds) {
     __shared__ __attribute__((aligned(16))) char lds[2][2][IMG_B];  // [buffer][operand]
     if (range_flag && *range_flag) return;  // operands out of the fp16 range: the fp32 kernels take over
     const int slot = blockIdx.x, slots = gridDim.x;
@@ -599,7 +710,11 @@ __global__ __launch_bounds__(512) void k_gemm_split_f16(const char* __restrict__
             const int64_t m0 = static_cast<int64_t>(tiles_x ? ot / tiles_x : ot) * 128 + wm;
             const int64_t n0 = static_cast<int64_t>(tiles_x ? ot % tiles_x : ot) * 128 + wn;
             float* c0 = C + (tile % ksplit) * part_stride + (m0 + 4 * lk) * ldc + (tiles_x ? n0 : wn) + l31;
-            wave_tile_epilogue<EPI>(wt.accm, wt.accc, m0, n0, c0, ldc, M, N, thr, pflags, ldf, cnt, l31, lk);
+            if constexpr (sizeof...(Dist) != 0)
+                wave_tile_distance_epilogue<B_LO, EPI>(wt.accm, wt.accc, m0, n0, c0, ldc, M, N, thr, pflags, ldf, cnt,
+                                                       ds..., l31, lk);
+            else
+                wave_tile_epilogue<EPI>(wt.accm, wt.accc, m0, n0, c0, ldc, M, N, thr, pflags, ldf, cnt, l31, lk);
             wt.zero();
             s = 0;
             tile += slots;
@@ -632,7 +747,7 @@ __global__ __launch_bounds__(512) void k_gemm_split_w8(const char* __restrict__ 
                                                        float* __restrict__ C, int64_t ldc, int tiles_x,
                                                        int n_tiles, int ksplit, int64_t part_stride,
                                                        const int32_t* __restrict__ range_flag, const float* __restrict__ thr,
-                                                        uint8_t* __restrict__ pflags, int64_t ldf, CountArgs cnt) {
+                                                       uint8_t* __restrict__ pflags, int64_t ldf, CountArgs cnt) {
     extern __shared__ __attribute__((aligned(16))) char lds8[];  // [2][A rows 0-255 | B rows 0-127]
     if (range_flag && *range_flag) return;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -727,6 +842,16 @@ static const SplitKernel SPLIT_W8[2][5] = {
      k_gemm_split_w8<false, 4>},
     {k_gemm_split_w8<true, 0>, k_gemm_split_w8<true, 1>, k_gemm_split_w8<true, 2>, k_gemm_split_w8<true, 3>,
      k_gemm_split_w8<true, 4>}};
+// The distance forms, 128 x 128 only, [B_LO][EPI 0 .. 3].  The 256 x 128 kernel (225-242 VGPRs plain) spills 8-172 B
+// a lane under the transform and has none; neither has the BCE epilogue (EPI 4: 20 B of scratch a lane, and an
+// epilogue the route was allowed, not asked, to take): those callers stay on the direct kernels.
+using DistKernel = void (*)(const char*, const char*, int64_t, int64_t, int, float*, int64_t, int, int, int, int64_t,
+                            const int32_t*, const float*, uint8_t*, int64_t, CountArgs, DistSrc);
+static const DistKernel SPLIT_F16_DIST[2][4] = {
+    {k_gemm_split_f16<false, 0, DistSrc>, k_gemm_split_f16<false, 1, DistSrc>, k_gemm_split_f16<false, 2, DistSrc>,
+     k_gemm_split_f16<false, 3, DistSrc>},
+    {k_gemm_split_f16<true, 0, DistSrc>, k_gemm_split_f16<true, 1, DistSrc>, k_gemm_split_f16<true, 2, DistSrc>,
+     k_gemm_split_f16<true, 3, DistSrc>}};
 
 static int n_compute_units() {
     static const int n = [] {
@@ -748,7 +873,7 @@ static int64_t pad_b(int64_t rows) { return ceil_div(rows, W8_B) * W8_B; }
 static int launch_product(const char* A, const char* B, int64_t M, int64_t N, int n_slice, float* C, int64_t ldc,
                           int ksplit, int64_t part_stride, bool b_lo, bool padded, const int32_t* flag,
                           hipStream_t st, const float* thr = nullptr, uint8_t* pflags = nullptr, int64_t ldf = 0,
-                          const CountArgs* count = nullptr, bool diag = false) {
+                          const CountArgs* count = nullptr, bool diag = false, const DistSrc* dist = nullptr) {
     BESS_REQUIRE(!thr || (ksplit == 1 && (pflags || count)),
                  "gemm_split: pruned stores / counts need an unsplit product and a flag or count array");
     BESS_REQUIRE(!count || ksplit == 1, "gemm_split: the reduction epilogues need an unsplit product");
@@ -759,16 +884,20 @@ static int launch_product(const char* A, const char* B, int64_t M, int64_t N, in
     const int64_t t8 = tx * ceil_div(M, W8_A) * ksplit, t4 = tx * ceil_div(M, 128) * ksplit;
     BESS_REQUIRE(t4 < (1ll << 31), "gemm_split: too many tiles");
     // one launch form: `tiles` tiles of kernel k[b_lo][epi], one persistent workgroup per CU at most
-    auto launch = [&](const SplitKernel (&k)[2][5], int64_t tiles, int lds_bytes, int64_t tiles_x, const char* what) {
+    // (`tail`: nothing, or the DistSrc of a distance kernel)
+    auto launch = [&](auto kernel, int64_t tiles, int lds_bytes, int64_t tiles_x, const char* what, auto... tail) {
         const int grid = static_cast<int>(tiles < cus ? tiles : cus);
-        k[b_lo][epi]<<<grid, 512, lds_bytes, st>>>(A, B, M, N, n_slice, C, ldc, static_cast<int>(tiles_x),
-                                                   static_cast<int>(tiles), ksplit, part_stride, flag, thr, pflags, ldf, cnt);
+        kernel<<<grid, 512, lds_bytes, st>>>(A, B, M, N, n_slice, C, ldc, static_cast<int>(tiles_x), static_cast<int>(tiles),
+                                             ksplit, part_stride, flag, thr, pflags, ldf, cnt, tail...);
         return check_launch(what);
     };
+    BESS_REQUIRE(!dist || epi < 4, "gemm_split: the BCE epilogue has no distance form");
     if (diag) {  // the diagonal 128 x 128 tiles only (M == N, tiles_x = 0), C is [M, 128]
         BESS_REQUIRE(M == N && ksplit == 1 && !thr && !count && ldc == 128, "gemm_split: bad diagonal product");
-        return launch(SPLIT_F16, ceil_div(M, 128), 0, 0, "gemm_split_f16 (diagonal tiles)");
+        if (dist) return launch(SPLIT_F16_DIST[b_lo][epi], ceil_div(M, 128), 0, 0, "gemm_split_f16 (diagonal tiles)", *dist);
+        return launch(SPLIT_F16[b_lo][epi], ceil_div(M, 128), 0, 0, "gemm_split_f16 (diagonal tiles)");
     }
+    if (dist) return launch(SPLIT_F16_DIST[b_lo][epi], t4, 0, tx, "gemm_split_f16 (distances)", *dist);
     if (padded && t8 >= cus) {
         static const bool attr = [] {
             bool ok = true;
@@ -779,9 +908,9 @@ static int launch_product(const char* A, const char* B, int64_t M, int64_t N, in
             return ok;
         }();
         BESS_REQUIRE(attr, "gemm_split: cannot reserve %d bytes of LDS", 2 * W8_IMG);
-        return launch(SPLIT_W8, t8, 2 * W8_IMG, tx, "gemm_split_w8");
+        return launch(SPLIT_W8[b_lo][epi], t8, 2 * W8_IMG, tx, "gemm_split_w8");
     }
-    return launch(SPLIT_F16, t4, 0, tx, "gemm_split_f16");
+    return launch(SPLIT_F16[b_lo][epi], t4, 0, tx, "gemm_split_f16");
 }
 
 static int64_t split_pitch(int W) { return ceil_div(W, SK) * ROW_B; }
@@ -820,6 +949,43 @@ static int split_rows(const SplitSrc& a, char* dst_a, int dtype_b, const SplitSr
         else k_split_rows<half_t, false><<<grid, 256, 0, st>>>(a, dst_a, ba, b, dst_b, W, n_blk);
     }
     return check_launch("split_rows");
+}
+
+// nq / ne of the distance transform, launched with k_split_rows on the same sources: one wave per row sums the
+// squares of the fp32 values that get split - lane l takes k = l, l + 64, .., a butterfly joins the lanes (a fixed
+// order).  Blocks [0, blocks_a) take `a`, the rest `b`, four rows each.
+template <typename T>
+__device__ __forceinline__ void row_norm_body(const SplitSrc& src, int W, float* __restrict__ dst, int64_t r) {
+    if (r >= src.rows) return;
+    const int lane = threadIdx.x & 63;
+    const T* row = static_cast<const T*>(src.base) + (src.idx ? static_cast<int64_t>(src.idx[r]) : r) * src.ld;
+    float s = 0.f;
+    for (int k = lane; k < W; k += 64) {
+        const float x = to_f32(row[k]);
+        s = fmaf(x, x, s);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) dst[r] = s;
+}
+template <typename TB>
+__global__ __launch_bounds__(256) void k_row_norms(SplitSrc a, float* __restrict__ na, int blocks_a, SplitSrc b,
+                                                   float* __restrict__ nb, int W) {
+    const int w = threadIdx.x >> 6;
+    if (static_cast<int>(blockIdx.x) < blocks_a) row_norm_body<float>(a, W, na, blockIdx.x * 4ll + w);
+    else row_norm_body<TB>(b, W, nb, (blockIdx.x - blocks_a) * 4ll + w);
+}
+static int row_norms(const SplitSrc& a, float* na, int dtype_b, const SplitSrc& b, float* nb, int W, hipStream_t st) {
+    const int64_t blocks_a = ceil_div(a.rows, 4), blocks_b = ceil_div(b.rows, 4);
+    const unsigned grid = static_cast<unsigned>(blocks_a + blocks_b);
+    const int ba = static_cast<int>(blocks_a);
+    if (dtype_b == BESS_F32) k_row_norms<float><<<grid, 256, 0, st>>>(a, na, ba, b, nb, W);
+    else k_row_norms<half_t><<<grid, 256, 0, st>>>(a, na, ba, b, nb, W);
+    return check_launch("row_norms");
+}
+// bytes of norms in front of the images of a distance pass: one float per (padded) row of a chunk's two operands
+int64_t gemm_split_norm_bytes(int64_t S, int64_t N) {
+    return (pad_a(S) + pad_b(N < SPLIT_CHUNK ? N : SPLIT_CHUNK)) * 4 / 256 * 256 + 256;
 }
 
 // Tile partials of the log-sum-exp epilogue -> state [rows, 2]: one wave per row.  Lane l merges slabs l, l + 64, ..
@@ -895,7 +1061,8 @@ __global__ void k_poison_counts(const int32_t* __restrict__ flag, int32_t* __res
 // out[q, j] = Q[q] . E[idx[j]] through the workspace (>= gemm_split_workspace bytes, 16-B aligned)
 int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const int32_t* idx, int64_t N, int W,
                    float* out, int64_t ld, void* ws, int64_t ws_bytes, hipStream_t st, const float* thr,
-                   uint8_t* pflags, int64_t ldf, const CountArgs* count, bool diag, float* lse_state, bool bce) {
+                   uint8_t* pflags, int64_t ldf, const CountArgs* count, bool diag, float* lse_state, bool bce,
+                   const int32_t** dist_flag) {
     const int64_t pitch = split_pitch(W);
     float* lse_part = nullptr;
     if (lse_state) {
@@ -905,6 +1072,15 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
         lse_part = static_cast<float*>(ws);
         ws = static_cast<char*>(ws) + pb;
         ws_bytes -= pb;
+    }
+    float *nq = nullptr, *ne = nullptr;
+    if (dist_flag) {  // [norms of the queries | norms of a chunk's candidates] in front of the images
+        const int64_t nb = gemm_split_norm_bytes(S, N);
+        BESS_REQUIRE(ws_bytes > nb, "gemm_split: workspace too small");
+        nq = static_cast<float*>(ws);
+        ne = nq + pad_a(S);
+        ws = static_cast<char*>(ws) + nb;
+        ws_bytes -= nb;
     }
     BESS_REQUIRE(!diag || (S == N && idx && !thr && !count && ld == 128), "gemm_split: bad diagonal product");
     BESS_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0, "gemm_split: workspace must be 16-B aligned");
@@ -917,7 +1093,8 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
     }
     int64_t chunk = (ws_bytes / pitch - pad_a(S)) / 128 * 128;  // candidate rows per pass
     BESS_REQUIRE(chunk >= 128, "gemm_split: workspace too small");
-    if (lse_state && chunk > SPLIT_CHUNK) chunk = SPLIT_CHUNK;  // (what the partials in front of the workspace cover)
+    // (what the partials / norms in front of the workspace cover)
+    if ((lse_state || dist_flag) && chunk > SPLIT_CHUNK) chunk = SPLIT_CHUNK;
     if (chunk >= N) chunk = N;
     char* qa = static_cast<char*>(ws);
     char* eb = qa + pad_a(S) * pitch;
@@ -928,14 +1105,18 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
         const int64_t sz = dtype == BESS_F32 ? 4 : 2;
         SplitSrc src{idx ? E : static_cast<const char*>(E) + j0 * W * sz, idx ? idx + j0 : nullptr, nc, W, flag};
         // the query rows ride along with the first chunk
-        if (int e = split_rows(SplitSrc{Q, nullptr, j0 == 0 ? S : 0, W, flag}, qa, dtype, src, eb, W, st)) return e;
+        const SplitSrc sq{Q, nullptr, j0 == 0 ? S : 0, W, flag};
+        if (int e = split_rows(sq, qa, dtype, src, eb, W, st)) return e;
+        const DistSrc ds{nq, ne, Q, src.base, src.idx, W};
+        if (dist_flag)
+            if (int e = row_norms(sq, nq, dtype, src, ne, W, st)) return e;
         // (pruned stores: the chunk's flags start at block j0 / 64 - chunks are multiples of 128 rows)
         CountArgs cj{nullptr, nullptr, 0, 0, lse_part, bce ? 1 : 0};
         if (count) cj = CountArgs{count->excl, count->counts, count->col0 + j0, count->round16, nullptr, 0};
         BESS_REQUIRE(!diag || nc == N, "gemm_split: the diagonal product wants its operands in one pass");
         if (int e = launch_product(qa, eb, S, nc, n_slice, (count || lse_state) ? nullptr : out + (diag ? 0 : j0), ld, 1, 0,
                                    dtype == BESS_F32, true, flag, st, thr, pflags ? pflags + j0 / 64 : nullptr, ldf,
-                                   (count || lse_state) ? &cj : nullptr, diag))
+                                   (count || lse_state) ? &cj : nullptr, diag, dist_flag ? &ds : nullptr))
             return e;
         if (lse_state) {  // (the partials are rewritten by the next chunk: merged per chunk, in chunk order)
             (bce ? k_bce_merge_parts : k_lse_merge_parts)<<<static_cast<unsigned>(ceil_div(S, 4)), 256, 0, st>>>(
@@ -955,6 +1136,10 @@ int gemm_split_fwd(int dtype, const float* Q, int64_t S, const void* E, const in
     // (diagonal form: no fp32 fallback - an operand outside the fp16 range leaves `out` unwritten; the counting pass
     // over the same rows meets the same operand and poisons its counts, which is what the caller acts on)
     if (diag) return BESS_OK;
+    if (dist_flag) {  // distances: the caller queues its direct kernels behind this call, gated on the same flag
+        *dist_flag = flag;
+        return BESS_OK;
+    }
     return gemm_dot_fwd(dtype, Q, S, E, idx, N, W, out, ld, st, flag);
 }
 
@@ -1012,13 +1197,116 @@ static int product(const char* A, const char* B, int64_t M, int64_t N, const Bwd
     return BESS_OK;
 }
 
-// d_query [S, W] and d_neg [N, W] (both dense, leading dimension W) through the workspace
+// ---- backward of the distance route -----------------------------------------------------------------------------
+// With s = -||q - e|| the forward score, G its gradient and C[q, j] = G[q, j] / s[q, j] (0 where s == 0, the
+// convention of the direct kernel):
+//     d_query[q] = rowsum(C)[q] q - (C E)[q]          d_neg[j] = colsum(C)[j] e_j - (C^T Q)[j]
+// so both products are the bilinear ones above with C in the place of G.  k_gram_coef makes C in one pass over G and
+// the scores, one 64 x 64 tile per workgroup, and leaves the tile's row sums and column sums as partials (plain
+// stores); k_gram_sums adds the partials in tile order (no float atomics: bitwise reproducible); k_gram_finish
+// applies the rowsum q / colsum e terms to the finished products.
+struct GramLayout {
+    int64_t c, rowpart, colpart, sums, total;  // bytes: C [S, N] | [N / 64][S] | [S / 64][N] | rowsum [S], colsum [N]
+};
+static GramLayout gram_layout(int64_t S, int64_t N) {
+    const auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    GramLayout g;
+    g.c = up(S * N * 4);
+    g.rowpart = up(ceil_div(N, 64) * S * 4);
+    g.colpart = up(ceil_div(S, 64) * N * 4);
+    g.sums = up((S + N) * 4);
+    g.total = g.c + g.rowpart + g.colpart + g.sums;
+    return g;
+}
+
+__global__ __launch_bounds__(256) void k_gram_coef(const float* __restrict__ G, int64_t ldg, const float* __restrict__ sc,
+                                                   int64_t ldsc, int64_t S, int64_t N, float* __restrict__ C,
+                                                   float* __restrict__ rowpart, float* __restrict__ colpart) {
+    __shared__ float cs[4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t j = blockIdx.x * 64ll + lane, q0 = blockIdx.y * 64ll + w * 16;
+    float csum = 0.f;
+    for (int i = 0; i < 16; ++i) {  // (q0 + i < S is uniform over the wave)
+        const int64_t q = q0 + i;
+        if (q >= S) break;
+        float c = 0.f;
+        if (j < N) {
+            const float s = sc[q * ldsc + j];
+            c = s != 0.f ? G[q * ldg + j] / s : 0.f;
+            C[q * N + j] = c;
+        }
+        csum += c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) rowpart[blockIdx.x * S + q] = c;
+    }
+    cs[w][lane] = csum;
+    __syncthreads();
+    if (w == 0 && j < N) colpart[blockIdx.y * N + j] = ((cs[0][lane] + cs[1][lane]) + cs[2][lane]) + cs[3][lane];
+}
+
+// threads [0, S): rowsum[q] = sum of the q-th entries of the n_cb column-tile partials; [S, S + N): colsum likewise
+__global__ __launch_bounds__(256) void k_gram_sums(const float* __restrict__ rowpart, const float* __restrict__ colpart,
+                                                   int64_t S, int64_t N, int n_cb, int n_rb, float* __restrict__ sums) {
+    const int64_t i = blockIdx.x * 256ll + threadIdx.x;
+    if (i >= S + N) return;
+    const bool row = i < S;
+    const float* p = row ? rowpart + i : colpart + (i - S);
+    const int64_t stride = row ? S : N;
+    float s = 0.f;
+    for (int b = 0; b < (row ? n_cb : n_rb); ++b) s += p[b * stride];
+    sums[i] = s;
+}
+
+// dQ[q, w] = rowsum[q] Q[q, w] - dQ[q, w];  dE[j, w] = colsum[j] E[idx[j], w] - dE[j, w]   (one thread per element)
+template <typename TE>
+__global__ __launch_bounds__(256) void k_gram_finish(const float* __restrict__ sums, const float* __restrict__ Q,
+                                                     const TE* __restrict__ E, const int32_t* __restrict__ idx, int64_t S,
+                                                     int64_t N, int W, float* __restrict__ dQ, float* __restrict__ dE) {
+    const int64_t i = blockIdx.x * 256ll + threadIdx.x;
+    if (i < S * W) {
+        dQ[i] = fmaf(sums[i / W], Q[i], -dQ[i]);
+    } else if (i < (S + N) * W) {
+        const int64_t k = i - S * W, j = k / W;
+        const int64_t r = idx ? static_cast<int64_t>(idx[j]) : j;
+        dE[k] = fmaf(sums[S + j], to_f32(E[r * W + (k - j * W)]), -dE[k]);
+    }
+}
+
+int64_t gemm_split_bwd_dist_workspace(int64_t S, int64_t N, int W) {
+    const int64_t b = gemm_split_bwd_workspace(S, N, W);
+    return b > 0 ? gram_layout(S, N).total + b : 0;
+}
+
+// d_query [S, W] and d_neg [N, W] (both dense, leading dimension W) through the workspace.  `scores` (the forward
+// result, leading dimension ld_scores): G is the gradient of Euclidean distance scores - the backward of the distance
+// route, whose workspace (gemm_split_bwd_dist_workspace) starts with the coefficient matrix and its sums.
 int gemm_split_bwd(int dtype, const float* G, int64_t ldg, int64_t S, const float* Q, const void* E,
                    const int32_t* idx, int64_t N, int W, float* dQ, float* dE, void* ws, int64_t ws_bytes,
-                   hipStream_t st) {
+                   hipStream_t st, const float* scores, int64_t ld_scores) {
     BwdLayout L;
-    BESS_REQUIRE(bwd_layout(S, N, W, L) && ws_bytes >= L.total, "gemm_split_bwd: workspace too small");
     BESS_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0, "gemm_split: workspace must be 16-B aligned");
+    const float* sums = nullptr;
+    if (scores) {
+        const GramLayout g = gram_layout(S, N);
+        BESS_REQUIRE(ws_bytes > g.total, "gemm_split_bwd: workspace too small");
+        char* base = static_cast<char*>(ws);
+        float* C = reinterpret_cast<float*>(base);
+        float* rowpart = reinterpret_cast<float*>(base + g.c);
+        float* colpart = reinterpret_cast<float*>(base + g.c + g.rowpart);
+        float* sm = reinterpret_cast<float*>(base + g.c + g.rowpart + g.colpart);
+        const int64_t n_cb = ceil_div(N, 64), n_rb = ceil_div(S, 64);
+        BESS_REQUIRE(n_rb < 65536 && n_cb < (1ll << 31), "gemm_split_bwd: problem too large for one launch");
+        k_gram_coef<<<dim3(static_cast<unsigned>(n_cb), static_cast<unsigned>(n_rb)), 256, 0, st>>>(
+            G, ldg, scores, ld_scores, S, N, C, rowpart, colpart);
+        k_gram_sums<<<static_cast<unsigned>(ceil_div(S + N, 256)), 256, 0, st>>>(
+            rowpart, colpart, S, N, static_cast<int>(n_cb), static_cast<int>(n_rb), sm);
+        if (int e = check_launch("gram_coef")) return e;
+        G = C, ldg = N, sums = sm;
+        ws = base + g.total;
+        ws_bytes -= g.total;
+    }
+    BESS_REQUIRE(bwd_layout(S, N, W, L) && ws_bytes >= L.total, "gemm_split_bwd: workspace too small");
     char* gp = static_cast<char*>(ws);
     char* gt = gp + L.g_plain;
     char* et = gt + L.g_trans;
@@ -1061,7 +1349,14 @@ int gemm_split_bwd(int dtype, const float* G, int64_t ldg, int64_t S, const floa
     if (int e = product(gt, qt, N, W, L.pe, dE, W, parts, flag, st)) return e;
     // (k_sum_parts has then summed garbage into dQ / dE: overwritten by the fp32 kernels, which run only if the flag is up)
     if (int e = gemm_dot_dq(dtype, G, ldg, S, E, idx, N, W, dQ, st, flag)) return e;
-    return gemm_dot_de(G, ldg, S, Q, N, W, dE, st, flag);
+    if (int e = gemm_dot_de(G, ldg, S, Q, N, W, dE, st, flag)) return e;
+    if (!sums) return BESS_OK;
+    const unsigned grid = static_cast<unsigned>(ceil_div((S + N) * W, 256));
+    if (dtype == BESS_F32)
+        k_gram_finish<float><<<grid, 256, 0, st>>>(sums, Q, static_cast<const float*>(E), idx, S, N, W, dQ, dE);
+    else
+        k_gram_finish<half_t><<<grid, 256, 0, st>>>(sums, Q, static_cast<const half_t*>(E), idx, S, N, W, dQ, dE);
+    return check_launch("gram_finish");
 }
 
 }  // namespace bess

@@ -13,7 +13,8 @@
 // LDS tile (never materialised in HBM).  The p-norm forms have no matrix-core
 // formulation (|a - b| is not bilinear) and run on the VALU: these kernels.  The
 // dot form of DistMult / ComplEx runs on the matrix cores (gemm_split.hip,
-// gemm_mfma.hip); the entry points below send it there.
+// gemm_mfma.hip); the entry points below send it there - and, where BESS_FLAG_GRAM_L2 permits it, the Euclidean
+// distance (p = 2) as ||q||^2 + ||e||^2 - 2 q.e with a transform in front of that product's epilogues.
 //
 // Backward reuses one tiled kernel:
 //   dX[a, w] = sum_b coef[a, b] * f'(X[a, w], Y[b, w])
@@ -81,9 +82,10 @@ __device__ __forceinline__ void stage_store(float (*tile)[LDP], int kc, int m, c
 template <typename T, int RED, bool ALIGNED, int MI>
 __global__ __launch_bounds__(256) void k_neg_shared_fwd(RowSrc<float> Q, RowSrc<T> E, int W,
                                                         float sign, float* __restrict__ out,
-                                                        int64_t ld_out, float p) {
+                                                        int64_t ld_out, float p, const int32_t* __restrict__ run_if) {
     __shared__ __attribute__((aligned(16))) float Qs[KT][LDP];
     __shared__ __attribute__((aligned(16))) float Es[KT][LDP];
+    if (run_if && !*run_if) return;  // queued behind the distance route: runs only when that route stood back
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int64_t q0 = static_cast<int64_t>(blockIdx.y) * (16 * MI);
     const int64_t j0 = static_cast<int64_t>(blockIdx.x) * TN;
@@ -708,7 +710,7 @@ static int run_l1_bwd_both(const bess_model_desc* d, RowSrc<float> Q, RowSrc<TE>
 
 template <typename T>
 static int run_fwd(const bess_model_desc* d, RowSrc<float> Q, RowSrc<T> E, float* out, int64_t ld,
-                   hipStream_t st) {
+                   hipStream_t st, const int32_t* run_if = nullptr) {
     // 32-row tiles when the 64-row grid would leave most CUs without a workgroup
     const bool small = ceil_div(E.n, TN) * ceil_div(Q.n, TM) < 192;
     const dim3 grid(static_cast<unsigned>(ceil_div(E.n, TN)), static_cast<unsigned>(ceil_div(Q.n, small ? TM / 2 : TM)));
@@ -717,7 +719,7 @@ static int run_fwd(const bess_model_desc* d, RowSrc<float> Q, RowSrc<T> E, float
         with_flag(d->width % KT == 0, [&](auto aligned) {
             with_constant<2, 4>(small ? 2 : 4, [&](auto mi) {
                 k_neg_shared_fwd<T, decltype(red)::value, decltype(aligned)::value, decltype(mi)::value>
-                    <<<grid, 256, 0, st>>>(Q, E, d->width, score_sign(d), out, ld, static_cast<float>(d->norm_p));
+                    <<<grid, 256, 0, st>>>(Q, E, d->width, score_sign(d), out, ld, static_cast<float>(d->norm_p), run_if);
             });
         });
     });
@@ -838,13 +840,39 @@ static int with_candidates(const bess_model_desc* d, const void* base, const int
     });
 }
 
+// Workspace of the split-fp16 products for a scorer on the product route (the bilinear scorers; TransE / RotatE with
+// p = 2 and BESS_FLAG_GRAM_L2, whose distance route adds norms in front of the forward images and the coefficient
+// matrix in front of the backward ones); 0 = not a shape for it
+static int64_t product_fwd_workspace(const bess_model_desc* d, int64_t S, int64_t N) {
+    const int64_t want = gemm_split_workspace(S, N, d->width);
+    return (want > 0 && gram_l2(d)) ? want + gemm_split_norm_bytes(S, N) : want;
+}
+static int64_t product_bwd_workspace(const bess_model_desc* d, int64_t S, int64_t N) {
+    return gram_l2(d) ? gemm_split_bwd_dist_workspace(S, N, d->width) : gemm_split_bwd_workspace(S, N, d->width);
+}
 // The split-fp16 product takes the call when the caller brought the workspace the shape wants (`wants`:
-// gemm_split_workspace or gemm_split_bwd_workspace; 0 = not a shape for it) and did not ask for the exact fp32 kernels
-static bool split_fits(const bess_model_desc* d, int64_t (*wants)(int64_t, int64_t, int), int64_t S, int64_t N,
-                       const void* workspace, int64_t workspace_bytes) {
+// product_fwd_workspace or product_bwd_workspace) and did not ask for the exact fp32 kernels
+static bool split_fits(const bess_model_desc* d, int64_t (*wants)(const bess_model_desc*, int64_t, int64_t), int64_t S,
+                       int64_t N, const void* workspace, int64_t workspace_bytes) {
     if (!workspace || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return false;
-    const int64_t want = wants(S, N, d->width);
+    const int64_t want = wants(d, S, N);
     return want > 0 && workspace_bytes >= want;
+}
+
+// The scores of the distance route: the split product with the distance transform, then the direct kernel queued
+// behind it on the flag the pre-pass raises for operands outside the fp16 range (no host round trip).  thr / flags /
+// diag as gemm_split_fwd takes them (the direct kernel writes every score, which is what a set block flag promises).
+static int gram_fwd(const bess_model_desc* d, const float* query, int64_t n_query, const void* neg_base,
+                    const int32_t* neg_idx, int64_t n_neg, float* out, int64_t ld_out, void* workspace,
+                    int64_t workspace_bytes, hipStream_t st, const float* thr = nullptr, uint8_t* flags = nullptr,
+                    int64_t ld_flags = 0) {
+    const int32_t* range_flag = nullptr;
+    if (int e = gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, out, ld_out, workspace,
+                               workspace_bytes, st, thr, flags, ld_flags, nullptr, false, nullptr, false, &range_flag))
+        return e;
+    return with_candidates(d, neg_base, neg_idx, n_neg, [&](auto E) {
+        return run_fwd(d, RowSrc<float>{query, nullptr, n_query}, E, out, ld_out, st, range_flag);
+    });
 }
 
 // f(j0, nc, base, idx) for every chunk of at most `chunk` of the n candidates, until one returns an error: indexed
@@ -913,9 +941,9 @@ extern "C" int bess_neg_score_shared_fwd_loss(const bess_model_desc* d, const fl
 
 extern "C" int64_t bess_neg_score_shared_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
     if (!d || check_desc(d) || n_query <= 0 || n_neg <= 0) return 0;
-    if (d->scorer == BESS_BOXE || d->scorer == BESS_AFFINE || reduce_of(d) != RED_DOT) return 0;
+    if (d->scorer == BESS_BOXE || d->scorer == BESS_AFFINE || !product_route(d)) return 0;
     if (d->reserved[0] & BESS_FLAG_FP32_MATH) return 0;  // the exact fp32 MFMA kernels are asked for
-    return gemm_split_workspace(n_query, n_neg, d->width);
+    return product_fwd_workspace(d, n_query, n_neg);
 }
 
 extern "C" int bess_neg_score_shared_fwd_ws(const bess_model_desc* d, const float* query, int64_t n_query,
@@ -936,12 +964,15 @@ extern "C" int bess_neg_score_shared_fwd_ws(const bess_model_desc* d, const floa
                                  as_stream(stream));
     }
     if (reduce_of(d) == RED_DOT) {  // bilinear scorers: matrix cores
-        if (split_fits(d, gemm_split_workspace, n_query, n_neg, workspace, workspace_bytes))
+        if (split_fits(d, product_fwd_workspace, n_query, n_neg, workspace, workspace_bytes))
             return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, out, ld_out,
                                   workspace, workspace_bytes, as_stream(stream));
         return gemm_dot_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, out, ld_out,
                             as_stream(stream));
     }
+    if (gram_l2(d) && split_fits(d, product_fwd_workspace, n_query, n_neg, workspace, workspace_bytes))
+        return gram_fwd(d, query, n_query, neg_base, neg_idx, n_neg, out, ld_out, workspace, workspace_bytes,
+                        as_stream(stream));
     if (use_l1_pk(d, query, neg_base))
         return l1_pk_fwd(d, query, n_query, neg_base, neg_idx, n_neg, out, ld_out, nullptr, as_stream(stream));
     return with_candidates(d, neg_base, neg_idx, n_neg, [&](auto E) {
@@ -970,9 +1001,13 @@ extern "C" int bess_neg_score_shared_fwd_pruned(const bess_model_desc* d, const 
     }
     if (d->scorer <= BESS_COMPLEX) {
         if (reduce_of(d) == RED_DOT) {
-            if (split_fits(d, gemm_split_workspace, n_query, n_neg, workspace, workspace_bytes))
+            if (split_fits(d, product_fwd_workspace, n_query, n_neg, workspace, workspace_bytes))
                 return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, out, ld_out,
                                       workspace, workspace_bytes, st, thr, flags, ld_flags);
+        } else if (gram_l2(d)) {
+            if (split_fits(d, product_fwd_workspace, n_query, n_neg, workspace, workspace_bytes))
+                return gram_fwd(d, query, n_query, neg_base, neg_idx, n_neg, out, ld_out, workspace, workspace_bytes, st,
+                                thr, flags, ld_flags);
         } else if (use_l1_pk(d, query, neg_base)) {
             return l1_pk_fwd(d, query, n_query, neg_base, neg_idx, n_neg, out, ld_out, nullptr, st, thr, flags, ld_flags);
         }
@@ -1024,7 +1059,11 @@ static bool counts_in_epilogue(const bess_model_desc* d, const float* query, con
     if (d->scorer > BESS_COMPLEX) return false;
     if (reduce_of(d) == RED_DOT) {
         if (d->reserved[0] & BESS_FLAG_FP32_MATH) return false;
-        *ws_want = gemm_split_workspace(n_query, n_neg, d->width);
+        *ws_want = product_fwd_workspace(d, n_query, n_neg);
+        return *ws_want > 0;
+    }
+    if (gram_l2(d)) {  // (p = 2: never a shape of the packed L1 kernel)
+        *ws_want = product_fwd_workspace(d, n_query, n_neg);
         return *ws_want > 0;
     }
     return !query || use_l1_pk(d, query, neg_base);
@@ -1058,10 +1097,12 @@ extern "C" int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const 
                               nullptr, st, thr, &cnt);
     int64_t want = 0;
     if (counts_in_epilogue(d, query, neg_base, n_query, n_neg, &want)) {
-        if (reduce_of(d) == RED_DOT) {
+        if (product_route(d)) {  // (the distance route: a raised range flag poisons the counts as it does for a product)
+            const int32_t* range_flag = nullptr;
             if (workspace && workspace_bytes >= want)
                 return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, nullptr, 0,
-                                      workspace, workspace_bytes, st, thr, nullptr, 0, &cnt);
+                                      workspace, workspace_bytes, st, thr, nullptr, 0, &cnt, false, nullptr, false,
+                                      gram_l2(d) ? &range_flag : nullptr);
         } else {
             // one launch per 65,536 candidates (32 MiB of fp16 rows at W = 256): the launch's rows stay in the
             // Infinity Cache while its query tiles pass over them - over all 2.5 M rows of a wikikg2 shard in one
@@ -1154,16 +1195,25 @@ static int64_t softmax_default_cols(int64_t n_query, int64_t n_neg) {
 }
 // the fused log-sum-exp epilogue takes the shapes the counting epilogue of the split product takes
 static int64_t lse_fused_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
-    if (reduce_of(d) != RED_DOT || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return 0;
-    const int64_t want = gemm_split_workspace(n_query, n_neg, d->width);
+    if (!product_route(d) || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return 0;
+    const int64_t want = product_fwd_workspace(d, n_query, n_neg);
     return want > 0 ? align256(gemm_split_lse_parts(n_query, n_neg)) + want : 0;
 }
 // the tile paths score in fp32 arithmetic throughout: the packed-fp16 L1 kernel rounds the query to fp16, which a
-// sum over all entities would carry into every row's normaliser
+// sum over all entities would carry into every row's normaliser (the distance route of p = 2 keeps fp32 accuracy
+// and stays permitted)
 static bess_model_desc tile_path_desc(const bess_model_desc* d) {
     bess_model_desc t = *d;
     t.reserved[0] &= ~BESS_FLAG_PREZEROED;
-    if (reduce_of(d) != RED_DOT) t.reserved[0] |= BESS_FLAG_FP32_MATH;
+    if (!product_route(d)) t.reserved[0] |= BESS_FLAG_FP32_MATH;
+    return t;
+}
+// The multi-label BCE calls (KvsAll) leave the distance route alone: under the transform their epilogue costs 20 B of
+// scratch a lane, so a flagged p = 2 descriptor scores and differentiates through the direct
+// kernels there, exactly as an unflagged one does.
+static bess_model_desc bce_path_desc(const bess_model_desc* d) {
+    bess_model_desc t = tile_path_desc(d);
+    if (gram_l2(d)) t.reserved[0] |= BESS_FLAG_FP32_MATH;
     return t;
 }
 
@@ -1188,9 +1238,11 @@ extern "C" int bess_neg_score_shared_fwd_lse(const bess_model_desc* d, const flo
     hipStream_t st = as_stream(stream);
     const int64_t fused = lse_fused_workspace(d, n_query, n_neg);
     if (fused > 0 && workspace_bytes >= fused) {
-        // [tile partials | images of the split product]
+        // [tile partials | norms of the distance route | images of the split product]
+        const int32_t* range_flag = nullptr;
         return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, nullptr, 0, workspace,
-                              workspace_bytes, st, nullptr, nullptr, 0, nullptr, false, state_ml);
+                              workspace_bytes, st, nullptr, nullptr, 0, nullptr, false, state_ml, false,
+                              gram_l2(d) ? &range_flag : nullptr);
     }
     // no epilogue for this scorer / shape: score tiles through the workspace, folded by a second kernel
     const int64_t cols = softmax_tile_cols(workspace_bytes, 1, n_query, n_neg);
@@ -1211,8 +1263,8 @@ static int64_t softmax_bwd_fixed(const bess_model_desc* d, int64_t n_query) {
     return align256(n_query * static_cast<int64_t>(d->width) * 4);
 }
 static int64_t softmax_bwd_gemm_ws(const bess_model_desc* d, int64_t n_query, int64_t cols) {
-    if (reduce_of(d) != RED_DOT || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return 0;
-    const int64_t f = gemm_split_workspace(n_query, cols, d->width), b = gemm_split_bwd_workspace(n_query, cols, d->width);
+    if (!product_route(d) || (d->reserved[0] & BESS_FLAG_FP32_MATH)) return 0;
+    const int64_t f = product_fwd_workspace(d, n_query, cols), b = product_bwd_workspace(d, n_query, cols);
     return f > b ? f : b;
 }
 
@@ -1436,7 +1488,7 @@ extern "C" int bess_neg_score_shared_fwd_bce(const bess_model_desc* d, const flo
     BESS_REQUIRE(workspace && reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
                  "neg_score_shared_fwd_bce: workspace missing (bess_neg_score_shared_fwd_bce_workspace) or misaligned");
     hipStream_t st = as_stream(stream);
-    const int64_t fused = lse_fused_workspace(d, n_query, n_neg);
+    const int64_t fused = gram_l2(d) ? 0 : lse_fused_workspace(d, n_query, n_neg);  // (bce_path_desc)
     if (fused > 0 && workspace_bytes >= fused) {
         // [tile partials | images of the split product]
         return gemm_split_fwd(d->dtype, query, n_query, neg_base, neg_idx, n_neg, d->width, nullptr, 0, workspace,
@@ -1445,7 +1497,7 @@ extern "C" int bess_neg_score_shared_fwd_bce(const bess_model_desc* d, const flo
     const int64_t cols = softmax_tile_cols(workspace_bytes, 1, n_query, n_neg);
     BESS_REQUIRE(cols >= 64, "neg_score_shared_fwd_bce: workspace holds less than 64 columns of scores "
                              "(bess_neg_score_shared_fwd_bce_workspace)");
-    const bess_model_desc td = tile_path_desc(d);
+    const bess_model_desc td = bce_path_desc(d);
     float* tile = static_cast<float*>(workspace);
     return for_each_candidate_chunk(neg_base, neg_idx, n_neg, cols, row_bytes_of(d),
                                     [&](int64_t, int64_t nc, const void* base, const int32_t* idx) {
@@ -1487,7 +1539,7 @@ extern "C" int bess_neg_score_shared_bwd_bce(const bess_model_desc* d, const flo
     float* P = sc + n_query * cols;
     void* gws = ws + fixed + 2 * n_query * cols * 4;
     const int64_t gws_bytes = workspace_bytes - fixed - 2 * n_query * cols * 4;
-    const bess_model_desc td = tile_path_desc(d);
+    const bess_model_desc td = bce_path_desc(d);
     const unsigned rows4 = static_cast<unsigned>(ceil_div(n_query, 4));
     const int64_t nqw = n_query * W;
     return for_each_candidate_chunk(neg_base, neg_idx, n_neg, cols, row_bytes_of(d),
@@ -1523,7 +1575,8 @@ extern "C" int64_t bess_neg_score_shared_fwd_pairs_workspace(const bess_model_de
     if (d->scorer == BESS_BOXE) return 0;
     int64_t want = 0;
     if (counts_in_epilogue(d, nullptr, nullptr, like_n_query, like_n_neg, &want) && want > 0)
-        return PAIR_DIAG_CHUNK * 128 * 4 + gemm_split_workspace_any(PAIR_DIAG_CHUNK, PAIR_DIAG_CHUNK, d->width);
+        return PAIR_DIAG_CHUNK * 128 * 4 + gemm_split_workspace_any(PAIR_DIAG_CHUNK, PAIR_DIAG_CHUNK, d->width) +
+               (gram_l2(d) ? gemm_split_norm_bytes(PAIR_DIAG_CHUNK, PAIR_DIAG_CHUNK) : 0);
     const int64_t blocks = PAIR_CHUNK * PAIR_CHUNK * 4, diag = PAIR_DIAG_CHUNK * 64 * 4;
     return blocks > diag ? blocks : diag;
 }
@@ -1550,7 +1603,7 @@ extern "C" int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const f
     float* tile = static_cast<float*>(workspace);
     int64_t want = 0;
     const bool epi = counts_in_epilogue(d, query, neg_base, like_n_query, like_n_neg, &want);
-    const bool gemm = epi && reduce_of(d) == RED_DOT;
+    const bool gemm = epi && product_route(d);
     const int64_t qw = query_width(d);
     const int64_t chunk = epi ? PAIR_DIAG_CHUNK : PAIR_CHUNK;
     const int64_t block = gemm ? 128 : (epi ? 64 : PAIR_CHUNK);  // columns of `tile`
@@ -1560,9 +1613,10 @@ extern "C" int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const f
         const int64_t np = n_pair - p0 < chunk ? n_pair - p0 : chunk;
         const float* q = query + p0 * qw;
         int rc;
+        const int32_t* range_flag = nullptr;
         if (gemm)
             rc = gemm_split_fwd(d->dtype, q, np, neg_base, neg_idx + p0, np, d->width, tile, 128, gws, gws_bytes, st,
-                                nullptr, nullptr, 0, nullptr, true);
+                                nullptr, nullptr, 0, nullptr, true, nullptr, false, gram_l2(d) ? &range_flag : nullptr);
         else if (epi)
             rc = l1_pk_fwd(d, q, np, neg_base, neg_idx + p0, np, tile, 64, nullptr, st, nullptr, nullptr, 0, nullptr, true);
         else
@@ -1662,9 +1716,9 @@ extern "C" int bess_neg_score_shared_fwd(const bess_model_desc* d, const float* 
 
 extern "C" int64_t bess_neg_score_shared_bwd_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
     if (!d || check_desc(d) || n_query <= 0 || n_neg <= 0) return 0;
-    if (d->scorer == BESS_BOXE || d->scorer == BESS_AFFINE || reduce_of(d) != RED_DOT) return 0;
+    if (d->scorer == BESS_BOXE || d->scorer == BESS_AFFINE || !product_route(d)) return 0;
     if (d->reserved[0] & BESS_FLAG_FP32_MATH) return 0;
-    return gemm_split_bwd_workspace(n_query, n_neg, d->width);
+    return product_bwd_workspace(d, n_query, n_neg);
 }
 
 extern "C" int bess_neg_score_shared_bwd_parts_plan(const bess_model_desc* d, int64_t n_query, int64_t n_neg,
@@ -1728,13 +1782,18 @@ extern "C" int bess_neg_score_shared_bwd_ws(const bess_model_desc* d, const floa
                                  ld_dout, d_query, d_neg, st);
     }
     if (reduce_of(d) == RED_DOT) {
-        if (split_fits(d, gemm_split_bwd_workspace, n_query, n_neg, workspace, workspace_bytes))
+        if (split_fits(d, product_bwd_workspace, n_query, n_neg, workspace, workspace_bytes))
             return gemm_split_bwd(d->dtype, d_out, ld_dout, n_query, query, neg_base, neg_idx, n_neg, d->width,
                                   d_query, d_neg, workspace, workspace_bytes, st);
         if (int e = gemm_dot_dq(d->dtype, d_out, ld_dout, n_query, neg_base, neg_idx, n_neg, d->width, d_query, st))
             return e;
         return gemm_dot_de(d_out, ld_dout, n_query, query, n_neg, d->width, d_neg, st);
     }
+    // the distance route: both products of the p = 2 backward on the matrix cores (d_query and d_neg are overwritten
+    // whole, so BESS_FLAG_PREZEROED asks nothing of it)
+    if (gram_l2(d) && split_fits(d, product_bwd_workspace, n_query, n_neg, workspace, workspace_bytes))
+        return gemm_split_bwd(d->dtype, d_out, ld_dout, n_query, query, neg_base, neg_idx, n_neg, d->width, d_query,
+                              d_neg, workspace, workspace_bytes, st, out, ld_out);
     // the packed-fp16 forward (fp16 tables only) scores the query rounded to fp16: differentiate that function
     const bool r16 = use_l1_pk(d, query, neg_base);
     if (int e = with_candidates(d, neg_base, neg_idx, n_neg, [&](auto E) {

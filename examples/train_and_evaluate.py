@@ -81,6 +81,9 @@ def main(argv=None) -> dict:
                     help="TuckER's query_route: per-triple outer product, or one mixed matrix per relation")
     ap.add_argument("--conve-route", default="torch", choices=["torch", "fused"],
                     help="ConvE's query_route: the torch modules, or the fused conv + FC kernels (no feature map)")
+    ap.add_argument("--distance-route", default="direct", choices=["direct", "gram"],
+                    help="TransE's / RotatE's distance_route: gram scores with scoring_norm=2 through the matrix-core "
+                         "product where shape and scratch fit")
     ap.add_argument("--embedding-size", type=int, default=32)
     ap.add_argument("--lr", type=float, default=0.05)
     ap.add_argument("--negative-weights", default="uniform", choices=["uniform", "degree"],
@@ -126,7 +129,11 @@ def main(argv=None) -> dict:
 
     # ---- model (same constructors as the reference)
     d = args.embedding_size
-    if args.scorer in ("TransE", "RotatE", "PairRE", "TranS"):
+    if args.distance_route == "gram":  # (the Euclidean distance through the matrix-core product: p = 2)
+        if args.scorer not in ("TransE", "RotatE"):
+            ap.error("--distance-route gram is TransE's / RotatE's")
+        fn = getattr(scoring, args.scorer)(True, 2, sharding, args.n_relation, d, distance_route="gram")
+    elif args.scorer in ("TransE", "RotatE", "PairRE", "TranS"):
         fn = getattr(scoring, args.scorer)(True, 1, sharding, args.n_relation, d)
     elif args.scorer == "TuckER":  # (the paper's recipe: --training kvsall --label-smoothing 0.1)
         fn = scoring.TuckER(True, sharding, args.n_relation, d, args.relation_size, batch_normalization=True,

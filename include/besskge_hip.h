@@ -100,6 +100,13 @@ extern "C" {
 #define BESS_FLAG_FP32_MATH 1 /* shared negatives with the plain fp32 kernels only: no packed-fp16 L1 forward
                                  (TransE / RotatE on f16 tables), no split-fp16 matrix-core products (DistMult /
                                  ComplEx) */
+#define BESS_FLAG_GRAM_L2 8 /* TransE / RotatE with norm_p == 2: the shared-candidate calls MAY take the matrix-core
+                             * route ||q - e||^2 = ||q||^2 + ||e||^2 - 2 q.e (the split-fp16 product with a distance
+                             * transform in front of its epilogues; pairs closer than 2^-8 (||q||^2 + ||e||^2) are
+                             * recomputed from the rows in fp32) where the bilinear scorers take that product, and
+                             * bess_neg_score_shared_workspace and its siblings then ask for its scratch.  Never
+                             * forced: shapes or scratch that do not fit, BESS_FLAG_FP32_MATH and operands outside the
+                             * fp16 range run the direct kernels.  Ignored for every other norm_p */
 /* bess_model_desc.reserved[1] of TransE / RotatE / DistMult / ComplEx: the row count of the table that
  * bess_neg_score_pertriple_fwd's neg_base / neg_idx name (0 = unknown), see bess_neg_pertriple_sweep */
 
