@@ -297,6 +297,10 @@ SIGNATURES = {
     "bess_struct_query_fwd": [_SD, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "bess_struct_query_bwd": [_SD, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                               _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
+    "bess_boxe_query_workspace": [_MD, _i64, _i64, ctypes.POINTER(_i64)],
+    "bess_boxe_query_fwd": [_MD, _i32, _f32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
+    "bess_boxe_query_bwd": [_MD, _i32, _f32, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                            _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
 }
 COMM_ID_BYTES = 128
 AFFINE_COUNT_CHUNK_BYTES = 32 << 20  # BESS_AFFINE_COUNT_CHUNK_BYTES
@@ -1046,6 +1050,87 @@ def struct_query_bwd(d: StructDesc, side: int, ent: RowSource, rel_table: torch.
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # (kept alive by the stream-ordered allocator)
     ld = lambda t, name, shape: shape[1] if t is None else _f32_ld(t, name, shape)  # noqa: E731
     _launch("bess_struct_query_bwd", dev, *args, n_rel, rel_idx.data_ptr(), *segs, S, _ptr(dq), ld(dq, "dq", (S, W)),
+            _ptr(d_pos), d_ent.data_ptr(), ld(d_ent, "d_ent", (S, W)), _ptr(d_other), ld(d_other, "d_other", (S, W)),
+            _ptr(d_rel), ld(d_rel, "d_rel", (n_rel, Wr)), _ptr(ws), nbytes)
+    return d_ent, d_other
+
+
+def _boxe_operands(d: ModelDesc, side: int, eps: float, ent: RowSource, other: Optional[RowSource],
+                   rel_table: torch.Tensor, rel_idx: torch.Tensor,
+                   more: Sequence[Tuple[str, Optional[torch.Tensor]]] = ()) -> Tuple[torch.device, int, List[Any]]:
+    """(device, S, the arguments desc .. ld_rel of both entry points) of BoxE's query."""
+    dev = _same_device([("entity rows", ent.base), ("entity idx", ent.idx), ("relation_embedding", rel_table),
+                        ("relation", rel_idx)] + ([("other rows", other.base), ("other idx", other.idx)] if other else [])
+                       + list(more))
+    S = len(ent)
+    if other is not None and len(other) != S:
+        raise ValueError(f"boxe_query: {S} entity rows but {len(other)} other rows")
+    _idx(rel_idx, "relation", S)
+    args = [ctypes.byref(d), side, float(eps), *_struct_rows(d, ent, "entity rows", d.width),
+            *_struct_rows(d, other, "other rows", d.width),
+            *_struct_rows(d, RowSource(rel_table), "relation_embedding", d.rel_width)[:2]]
+    return dev, S, args
+
+
+def boxe_query_fwd(d: ModelDesc, side: int, eps: float, ent: RowSource, rel_table: torch.Tensor, rel_idx: torch.Tensor,
+                   other: Optional[RowSource] = None, want_query: bool = True, out: Optional[torch.Tensor] = None,
+                   pos_out: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(q [S, 6 d] or None, pos [S] or None) of BoxE (`d`: the scorer's `kernel_desc()`, width 2 d): the query matrix
+    of the candidate kernels for the kept rows `ent` (heads for CORRUPT_TAIL, tails for CORRUPT_HEAD) and, with the
+    triples' `other` rows, the triples' scores from the same launch (`bess_boxe_query_fwd`); `want_query=False`: the
+    scores alone.  Rows are read through their index, no gather.  `out`, `pos_out`: preallocated outputs."""
+    dev, S, args = _boxe_operands(d, side, eps, ent, other, rel_table, rel_idx, [("q", out), ("pos", pos_out)])
+    if other is None and not want_query:
+        raise ValueError("boxe_query_fwd: nothing is asked for (no other rows and want_query=False)")
+    W = 3 * d.width
+    q = None if not want_query else (torch.empty((S, W), dtype=torch.float32, device=dev) if out is None else out)
+    pos = None if other is None else (torch.empty((S,), dtype=torch.float32, device=dev) if pos_out is None else pos_out)
+    if pos is not None:
+        _f32(pos, "pos")
+        if pos.numel() != S:
+            raise ValueError(f"boxe_query_fwd: pos has {pos.numel()} entries, expected {S}")
+    _launch("bess_boxe_query_fwd", dev, *args, rel_idx.data_ptr(), S, _ptr(q), W if q is None else _f32_ld(q, "q", (S, W)),
+            _ptr(pos))
+    return q, pos
+
+
+def boxe_query_workspace(d: ModelDesc, S: int, n_rel: int) -> int:
+    """Bytes of scratch `boxe_query_bwd` needs for its relation gradient (host arithmetic)."""
+    nbytes = ctypes.c_int64(0)
+    _check(load().bess_boxe_query_workspace(ctypes.byref(d), S, n_rel, ctypes.byref(nbytes)), "bess_boxe_query_workspace")
+    return int(nbytes.value)
+
+
+def boxe_query_bwd(d: ModelDesc, side: int, eps: float, ent: RowSource, rel_table: torch.Tensor, rel_idx: torch.Tensor,
+                   dq: Optional[torch.Tensor], d_rel: Optional[torch.Tensor], other: Optional[RowSource] = None,
+                   d_pos: Optional[torch.Tensor] = None, seg: Optional["SegmentIndex"] = None,
+                   out: Sequence[Optional[torch.Tensor]] = (None, None)
+                   ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """(d_ent [S, 2 d], d_other [S, 2 d] or None) of `boxe_query_fwd` for the query gradient dq [S, 6 d] and / or the
+    gradient d_pos [S] of the triples' scores; the relation-table gradient is ADDED into d_rel [n_rel, 4 d + 2] (None:
+    not computed).  `seg`: the `SegmentIndex` of rel_idx (built here if missing).  Bitwise reproducible, no atomics
+    (`bess_boxe_query_bwd`)."""
+    dev, S, args = _boxe_operands(d, side, eps, ent, other, rel_table, rel_idx,
+                                  [("dq", dq), ("d_pos", d_pos), ("d_rel", d_rel), ("d_ent", out[0]), ("d_other", out[1])])
+    if (other is None) != (d_pos is None) or (dq is None and d_pos is None):
+        raise ValueError("boxe_query_bwd: d_pos comes with the other rows, and dq or d_pos is needed")
+    n_rel, W, Wr = int(rel_table.shape[0]), int(d.width), int(d.rel_width)
+    d_ent = torch.empty((S, W), dtype=torch.float32, device=dev) if out[0] is None else out[0]
+    d_other = None if other is None else (torch.empty((S, W), dtype=torch.float32, device=dev) if out[1] is None else out[1])
+    if d_pos is not None:
+        _f32(d_pos, "d_pos")
+        if d_pos.numel() != S:
+            raise ValueError(f"boxe_query_bwd: d_pos has {d_pos.numel()} entries, expected {S}")
+    segs, ws, nbytes = [0, 0, 0, 0], None, 0
+    if d_rel is not None and S:
+        seg = SegmentIndex(rel_idx, n_rel) if seg is None else seg
+        if seg.n_refs != S:
+            raise ValueError(f"boxe_query_bwd: the segment index holds {seg.n_refs} ids, expected {S}")
+        segs = [seg.refs.data_ptr(), seg.seg_rows.data_ptr(), seg.seg_offsets.data_ptr(), seg.n_seg.data_ptr()]
+        nbytes = boxe_query_workspace(d, S, n_rel)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # (kept alive by the stream-ordered allocator)
+    ld = lambda t, name, shape: shape[1] if t is None else _f32_ld(t, name, shape)  # noqa: E731
+    _launch("bess_boxe_query_bwd", dev, *args, n_rel, rel_idx.data_ptr(), *segs, S, _ptr(dq), ld(dq, "dq", (S, 3 * W)),
             _ptr(d_pos), d_ent.data_ptr(), ld(d_ent, "d_ent", (S, W)), _ptr(d_other), ld(d_other, "d_other", (S, W)),
             _ptr(d_rel), ld(d_rel, "d_rel", (n_rel, Wr)), _ptr(ws), nbytes)
     return d_ent, d_other

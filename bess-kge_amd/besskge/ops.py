@@ -219,6 +219,38 @@ class StructuredQuery(torch.autograd.Function):
         return None, None, dx.reshape(ctx.shape).to(x.dtype), None if d_rel is None else d_rel.to(rel_table.dtype), None
 
 
+class BoxEQuery(torch.autograd.Function):
+    """BoxE's S-row work `(desc, side, eps, rows [S, 2 d], rel_table [n_rel, 4 d + 2], rel_idx [S], other [S, 2 d] |
+    None)`: the query `q [S, 6 d]` of the kept `rows` without `other`, the triples' scores `[S]` with it
+    (`nat.boxe_query_fwd`).  Rows and relation table are of the table type, the gradients come back in their dtypes
+    (the relation table's dense, zero for absent relations).  No double backward."""
+
+    @staticmethod
+    def forward(ctx: Any, desc: nat.ModelDesc, side: int, eps: float, rows: torch.Tensor,  # type: ignore
+                rel_table: torch.Tensor, rel_idx: torch.Tensor, other: Optional[torch.Tensor]) -> torch.Tensor:
+        W = rows.shape[-1]
+        x, r = _as_rows(rows.detach(), W), _idx32(rel_idx)
+        o = None if other is None else _as_rows(other.detach(), W)
+        ctx.desc, ctx.side, ctx.eps, ctx.shape, ctx.scores = desc, side, eps, rows.shape, other is not None
+        ctx.save_for_backward(x, rel_table.detach(), r, *(() if o is None else (o,)))
+        q, pos = nat.boxe_query_fwd(desc, side, eps, RowSource(x), rel_table.detach(), r,
+                                    other=None if o is None else RowSource(o), want_query=o is None)
+        return q if o is None else pos.reshape(rows.shape[:-1])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx: Any, g: torch.Tensor):  # type: ignore
+        x, rel_table, r = ctx.saved_tensors[:3]
+        o = ctx.saved_tensors[3] if ctx.scores else None
+        d_rel = torch.zeros(rel_table.shape, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[4] else None
+        g = g.float().contiguous()
+        dx, do = nat.boxe_query_bwd(ctx.desc, ctx.side, ctx.eps, RowSource(x), rel_table, r, None if ctx.scores else g,
+                                    d_rel, other=None if o is None else RowSource(o),
+                                    d_pos=g.reshape(-1) if ctx.scores else None)
+        return (None, None, None, dx.reshape(ctx.shape).to(x.dtype), None if d_rel is None else d_rel.to(rel_table.dtype),
+                None, None if do is None else do.reshape(ctx.shape).to(o.dtype))
+
+
 class ConvEQuery(torch.autograd.Function):
     """ConvE's conv + channel affine + ReLU + channel mask + FC product `(x [S, Cin, H2, W], K [Cout, Cin, kh, kw],
     a [Cout], b [Cout], m [S, Cout] | None, Wfc [d, F]) -> y [S, d]` (`nat.conve_query_fwd`): the `[S, F]` feature map

@@ -1188,8 +1188,16 @@ class RESCAL(_TorchQueryHooks, MatrixDecompositionScoreFunction):
 class BoxE(_TorchQueryHooks, DistanceBasedScoreFunction):
     """BoxE (reference scoring.py:1149-1415): entities are [base | bump]; the head is
     bumped by the tail's bump and vice versa, and each bumped point is scored by a
-    piecewise distance to its relation box."""
+    piecewise distance to its relation box.
 
+    `query_route` chooses who does the S-row work of a step (box normalisation, query, positive score and their
+    backward); parameters and state dicts are the same and a model can switch route (`fn.query_route = ...`):
+      "torch"   torch ops and autograd over gathered rows (the default);
+      "native"  the kernels of csrc/boxe_query.hip (`nat.boxe_query_fwd / _bwd`): rows read through their index, no
+                autograd graph over the batch, the relation gradient summed per relation without atomics (bitwise
+                reproducible); the public `score_*` methods are differentiable through `ops.BoxEQuery`.  The
+                kernels' widths are the candidate kernels': `embedding_size` <= 512, <= 128 when not a multiple
+                of 4 - a wider one is refused here."""
 
     _scorer_id = nat.BOXE
 
@@ -1208,9 +1216,16 @@ class BoxE(_TorchQueryHooks, DistanceBasedScoreFunction):
         dist_func_per_dim: bool = True,
         eps: float = 1e-6,
         inverse_relations: bool = False,
+        query_route: str = "torch",
         **placement: Any,
     ) -> None:
         super().__init__(negative_sample_sharing, scoring_norm)
+        if query_route not in ("torch", "native"):
+            raise ValueError(f'BoxE: query_route is "torch" or "native", got {query_route!r}')
+        if query_route == "native" and (embedding_size > 512 or (embedding_size % 4 != 0 and embedding_size > 128)):
+            raise ValueError(f'BoxE: query_route="native" takes embedding_size <= 512 (<= 128 when not a multiple of 4),'
+                             f" got {embedding_size}")
+        self.query_route = query_route
         self.apply_tanh = apply_tanh
         self.dist_func_per_dim = dist_func_per_dim
         self.eps = eps
@@ -1270,29 +1285,73 @@ class BoxE(_TorchQueryHooks, DistanceBasedScoreFunction):
         center, half = self._boxes(rel.reshape(-1, rel.shape[-1]).float())
         return self._box_distance(bumped_ht.float(), center.reshape(*lead, 2, -1), half.reshape(*lead, 2, -1))
 
+    @staticmethod
+    def _wide(x: torch.Tensor) -> torch.Tensor:
+        """fp32 for the arithmetic; a float64 operand (the tests' reference) stays as it is"""
+        return x if x.dtype == torch.float64 else x.float()
+
     def _triple_torch(self, h: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         d = self.embedding_size
-        center, half = self._boxes(torch.index_select(rel, 0, rel_idx.reshape(-1).long()).float())
+        center, half = self._boxes(self._wide(torch.index_select(rel, 0, rel_idx.reshape(-1).long())))
         # head box sees h_base + t_bump, tail box sees t_base + h_bump
-        point = h.float().reshape(-1, 2, d) + t.float().reshape(-1, 2, d).flip(-2)
+        point = self._wide(h).reshape(-1, 2, d) + self._wide(t).reshape(-1, 2, d).flip(-2)
         return self._box_distance(point, center, half)
 
     def _query_torch(self, side: int, rows: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
         d = self.embedding_size
-        center, half = self._boxes(torch.index_select(rel, 0, rel_idx.reshape(-1).long()).float())
-        kept = rows.float().reshape(-1, 2, d)
+        center, half = self._boxes(self._wide(torch.index_select(rel, 0, rel_idx.reshape(-1).long())))
+        kept = self._wide(rows).reshape(-1, 2, d)
         # candidate part 0 (base) is shifted by the kept bump, part 1 (bump) by the kept base; the
         # base of a candidate tail meets the tail box, the base of a candidate head the head box
         box = (1, 0) if side == nat.CORRUPT_TAIL else (0, 1)
         return torch.cat([kept[:, 1], center[:, box[0]], half[:, box[0]],
                           kept[:, 0], center[:, box[1]], half[:, box[1]]], dim=-1)
 
+    # hooks of the fused step, route "native": the entry points of csrc/boxe_query.hip, no autograd graph over S rows
+    def _rows(self, src: nat.RowSource) -> nat.RowSource:
+        dt = self.relation_embedding.dtype
+        return src if src.base.dtype == dt else nat.RowSource(src.base.to(dt), src.idx)
+
+    def query_fwd(self, side: int, ent: nat.RowSource, rel_idx: torch.Tensor) -> Tuple[torch.Tensor, Any]:
+        if self.query_route != "native":
+            return super().query_fwd(side, ent, rel_idx)
+        return nat.boxe_query_fwd(self.kernel_desc(), side, self.eps, self._rows(ent), self.relation_embedding.data,
+                                  rel_idx)[0], None
+
+    def query_bwd(self, side: int, ent: nat.RowSource, rel_idx: torch.Tensor, ctx: Any, dq: torch.Tensor,
+                  d_rel: torch.Tensor) -> torch.Tensor:
+        if self.query_route != "native":
+            return super().query_bwd(side, ent, rel_idx, ctx, dq, d_rel)
+        return nat.boxe_query_bwd(self.kernel_desc(), side, self.eps, self._rows(ent), self.relation_embedding.data,
+                                  rel_idx, dq, d_rel)[0]
+
+    def triple_fwd(self, head: nat.RowSource, tail: nat.RowSource, rel_idx: torch.Tensor) -> Tuple[torch.Tensor, Any]:
+        if self.query_route != "native":
+            return super().triple_fwd(head, tail, rel_idx)
+        return nat.boxe_query_fwd(self.kernel_desc(), nat.CORRUPT_TAIL, self.eps, self._rows(head),
+                                  self.relation_embedding.data, rel_idx, other=self._rows(tail), want_query=False)[1], None
+
+    def triple_bwd(self, head: nat.RowSource, tail: nat.RowSource, rel_idx: torch.Tensor, ctx: Any,
+                   d_pos: torch.Tensor, d_rel: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.query_route != "native":
+            return super().triple_bwd(head, tail, rel_idx, ctx, d_pos, d_rel)
+        return nat.boxe_query_bwd(self.kernel_desc(), nat.CORRUPT_TAIL, self.eps, self._rows(head),
+                                  self.relation_embedding.data, rel_idx, None, d_rel, other=self._rows(tail),
+                                  d_pos=d_pos.reshape(-1).contiguous())
+
     def score_triple(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        if self.query_route == "native":
+            return ops.BoxEQuery.apply(self.kernel_desc(), nat.CORRUPT_TAIL, self.eps, self._table_dtype(head_emb),
+                                       self.relation_embedding, relation_id, self._table_dtype(tail_emb))
         return self._triple_torch(head_emb, self.relation_embedding, relation_id, tail_emb)
 
     def _score_candidates(self, side: int, kept: torch.Tensor, relation_id: torch.Tensor,
                           cand: torch.Tensor) -> torch.Tensor:
-        q = self._query_torch(side, kept, self.relation_embedding, relation_id)
+        if self.query_route == "native":
+            q = ops.BoxEQuery.apply(self.kernel_desc(), side, self.eps, self._table_dtype(kept), self.relation_embedding,
+                                    relation_id, None)
+        else:
+            q = self._query_torch(side, kept, self.relation_embedding, relation_id)
         return ops.ReduceNegatives.apply(self.kernel_desc(), bool(self.negative_sample_sharing), q.contiguous(),
                                          self._table_dtype(cand))
 

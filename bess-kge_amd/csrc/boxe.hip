@@ -23,13 +23,11 @@
 // candidate rows stay cache resident) and an atomic d_neg.
 #include <algorithm>
 
+#include "box_math.h"
 #include "common.h"
 #include "segment_pass.h"
 
 namespace bess {
-
-static const char* const BOX_TOO_WIDE =
-    "BoxE: embedding size %d too wide for the kernels (max 512; 128 when not a multiple of 4)";
 
 struct BoxArgs {
     const float* query;  // [n_query, 6 d]
@@ -74,20 +72,7 @@ __device__ __forceinline__ const int32_t* box_idx(const BoxArgs& a, int64_t q) {
     return a.idx ? a.idx + q * a.idx_stride : nullptr;
 }
 
-// per element: bumped point (after tanh), distance to the centre, inside flag
-template <bool TANH>
-__device__ __forceinline__ void box_point(float e, float s, float c, float h, float& xp, float& dist, bool& inside) {
-    xp = e + s;
-    if (TANH) xp = tanhf(xp);
-    dist = fabsf(xp - c);
-    inside = dist <= h;
-}
-
-__device__ __forceinline__ float box_final(float dist, float h, bool inside) {
-    const float B = 1.f + 2.f * h;
-    const float A = 1.f / B;
-    return inside ? dist * A : dist * B - h * (B - A);
-}
+// (box_point, box_final - per element: bumped point, distance to the centre, inside flag, f - are box_math.h's)
 
 // COUNT: the counting variant (CountArgs of common.h; shared candidates only) - no score is stored; every 16-lane
 // group counts its candidates against thr[q], the wave adds the four groups up and lane 0 issues at most one

@@ -150,6 +150,8 @@ static const PlanFn PLAN_FNS[] = {
     BESS_PLAN_FN(bess_relation_lse_bwd),
     BESS_PLAN_FN(bess_struct_query_fwd),
     BESS_PLAN_FN(bess_struct_query_bwd),
+    BESS_PLAN_FN(bess_boxe_query_fwd),
+    BESS_PLAN_FN(bess_boxe_query_bwd),
 };
 #undef BESS_PLAN_FN
 

@@ -12,6 +12,7 @@ queries and report filtered-free MRR / hits@10.
                                              [--scorer TuckER --relation-size 16 [--tucker-route relation]]
                                              [--scorer RESCAL | QuatE | SimplE | CP]
                                              [--scorer ConvE [--conve-route fused]]
+                                             [--scorer BoxE [--boxe-route native]]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -75,12 +76,15 @@ def main(argv=None) -> dict:
     ap.add_argument("--n-shard", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--scorer", default="TransE", choices=["TransE", "RotatE", "DistMult", "ComplEx", "PairRE", "TranS", "TuckER",
-                                                                "RESCAL", "ConvE", "QuatE", "SimplE", "CP"])
+                                                                "RESCAL", "ConvE", "QuatE", "SimplE", "CP", "BoxE"])
     ap.add_argument("--relation-size", type=int, default=16, help="width of the relation rows of --scorer TuckER")
     ap.add_argument("--tucker-route", default="outer", choices=["outer", "relation"],
                     help="TuckER's query_route: per-triple outer product, or one mixed matrix per relation")
     ap.add_argument("--conve-route", default="torch", choices=["torch", "fused"],
                     help="ConvE's query_route: the torch modules, or the fused conv + FC kernels (no feature map)")
+    ap.add_argument("--boxe-route", default="torch", choices=["torch", "native"],
+                    help="BoxE's query_route: torch ops and autograd over the batch's rows, or the query / positive-score "
+                         "kernels (no gather, no autograd graph, reproducible relation gradient)")
     ap.add_argument("--distance-route", default="direct", choices=["direct", "gram"],
                     help="TransE's / RotatE's distance_route: gram scores with scoring_norm=2 through the matrix-core "
                          "product where shape and scratch fit")
@@ -135,6 +139,8 @@ def main(argv=None) -> dict:
         fn = getattr(scoring, args.scorer)(True, 2, sharding, args.n_relation, d, distance_route="gram")
     elif args.scorer in ("TransE", "RotatE", "PairRE", "TranS"):
         fn = getattr(scoring, args.scorer)(True, 1, sharding, args.n_relation, d)
+    elif args.scorer == "BoxE":
+        fn = scoring.BoxE(True, 2, sharding, args.n_relation, d, query_route=args.boxe_route)
     elif args.scorer == "TuckER":  # (the paper's recipe: --training kvsall --label-smoothing 0.1)
         fn = scoring.TuckER(True, sharding, args.n_relation, d, args.relation_size, batch_normalization=True,
                             input_dropout=0.2, hidden_dropout=0.2, query_route=args.tucker_route)

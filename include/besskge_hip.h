@@ -1340,6 +1340,46 @@ int bess_struct_query_bwd(const bess_struct_desc* desc, int32_t side, const void
                           float* d_ent, int64_t ld_dent, float* d_other, int64_t ld_dother, float* d_rel,
                           int64_t ld_drel, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- BoxE: query, positive score and their backward (csrc/boxe_query.hip) -----------------------------------------
+ * desc is the BESS_BOXE descriptor of the candidate entry points: width = 2 d (entity rows [base | bump]), rel_width =
+ * 4 d + 2 (relation rows [head centre | tail centre | head width | tail width | head size, tail size]), norm_p,
+ * reserved[0] bit 0 = tanh, bit 1 = inside / outside chosen per dimension.  Per box, over its d columns,
+ *     w = |width| / max(gm, eps) * (1 + elu(size)),  gm = exp(mean log max(|width|, eps))
+ *     tanh: low = tanh(centre - w / 2), up = tanh(low + w): C = (low + up) / 2, H = (up - low) / 2;  else C = centre,
+ *     H = w / 2
+ * and the query of the kept rows `ent` (heads for BESS_CORRUPT_TAIL, tails for BESS_CORRUPT_HEAD) is
+ *     q [S, 6 d] = [S_0 | C_0 | H_0 | S_1 | C_1 | H_1],  S_0 = the kept bump, S_1 = the kept base,
+ * slot 0 with the tail box and slot 1 with the head box for tail corruption, the other way round for head corruption:
+ * the query matrix of the BESS_BOXE candidate kernels.  With the triples' other rows, pos[i] = the score of triple i
+ * (the candidate arithmetic with the other row as the one candidate) comes from the same launch; pos and other_base
+ * are both NULL or neither, q may be NULL when only pos is wanted.  Row sources are (base, ld, idx; idx NULL: row i) of
+ * desc.dtype (fp32 or fp16, converted on load), rel_table [n_rel, 4 d + 2] of the same type with rel_idx[i] in
+ * [0, n_rel) - an id outside is an out-of-bounds read.  q and every gradient are fp32; leading dimensions in elements.
+ * bess_boxe_query_bwd, for dq [S, 6 d] and / or d_pos [S] (not both NULL; d_pos, other_base and d_other come together):
+ * d_ent [S, 2 d] and d_other [S, 2 d] are written per triple; d_rel [n_rel, 4 d + 2] (may be NULL) is ADDED to.  The
+ * batch comes grouped by relation as bess_build_segment_index builds it from rel_idx.  The gradient with respect to
+ * (C, H) is summed over a relation's triples - the C and H blocks of dq as they are, the d_pos part recomputed from the
+ * rows - and the Jacobian of the normalisation is applied to the sum.  At the kinks: abs'(0) = 0, a clamped value
+ * passes no gradient, the inside / outside choice is a constant, a zero norm gives a zero gradient.  No float atomics:
+ * a segment of up to 32 triples is summed by one workgroup in sorted order; a longer one is cut into 16 shares that go
+ * through the workspace (bess_boxe_query_workspace bytes = min(n_rel, S / 32 + 1) * 16 * (4 d + 2) * 4, nothing to
+ * clear) and are added in share order.  Every output is bitwise reproducible; nothing reads back to the host.
+ * Limits (BESS_EUNSUPPORTED before any launch): d > 512, d > 128 when d % 4 != 0 or when an operand is not on a
+ * 16-byte boundary (fp16 tables 8, relation rows half of that; leading dimensions multiples of 4, ld_rel of 2);
+ * S > 2^30 is BESS_EINVAL. */
+int bess_boxe_query_workspace(const bess_model_desc* desc, int64_t S, int64_t n_rel, int64_t* bytes);
+int bess_boxe_query_fwd(const bess_model_desc* desc, int32_t side, float eps, const void* ent_base, int64_t ld_ent,
+                        const int32_t* ent_idx, const void* other_base, int64_t ld_other, const int32_t* other_idx,
+                        const void* rel_table, int64_t ld_rel, const int32_t* rel_idx, int64_t S, float* q, int64_t ldq,
+                        float* pos, void* stream);
+int bess_boxe_query_bwd(const bess_model_desc* desc, int32_t side, float eps, const void* ent_base, int64_t ld_ent,
+                        const int32_t* ent_idx, const void* other_base, int64_t ld_other, const int32_t* other_idx,
+                        const void* rel_table, int64_t ld_rel, int64_t n_rel, const int32_t* rel_idx,
+                        const int32_t* refs_sorted, const int32_t* seg_rows, const int32_t* seg_offsets,
+                        const int32_t* n_seg, int64_t S, const float* dq, int64_t lddq, const float* d_pos,
+                        float* d_ent, int64_t ld_dent, float* d_other, int64_t ld_dother, float* d_rel,
+                        int64_t ld_drel, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- recorded steps -----------------------------------------------------------
  * A step of this library can be captured into a hipGraph as a whole (every call is asynchronous on the
  * caller's stream, every clear is a kernel).  bess_graph_node_counts tells what a captured graph holds:
