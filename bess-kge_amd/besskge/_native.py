@@ -22,7 +22,7 @@ import torch
 LIB_NAME = "libbesskge_hip.so"
 ABI_VERSION = 3
 
-TRANSE, ROTATE, DISTMULT, COMPLEX, AFFINE, BOXE = 0, 1, 2, 3, 4, 5
+TRANSE, ROTATE, DISTMULT, COMPLEX, AFFINE, BOXE, HAKE = 0, 1, 2, 3, 4, 5, 6
 F32, F16 = 0, 1
 CORRUPT_HEAD, CORRUPT_TAIL = 0, 1
 LOSS_LOGSIGMOID, LOSS_MARGIN, LOSS_SSCE = 0, 1, 2
@@ -1205,6 +1205,8 @@ def query_width(d: ModelDesc) -> int:
         return (n_part + 1) * (d.width // n_part)
     if d.scorer == BOXE:  # [S | C | H] for each of the two candidate parts
         return 3 * d.width
+    if d.scorer == HAKE:  # [U | R | Q_p]: d-wide vectors against rows [phase | modulus]
+        return 3 * (d.width // 2)
     return int(d.width)
 
 
@@ -1424,7 +1426,7 @@ def neg_score_pertriple_bwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, n
     """Returns (d_query [nq, W] or None, d_neg [nq*n_neg, W] or None).  `want_d_query=False` (TransE / RotatE /
     DistMult / ComplEx; d_query came out of the fused forward): DistMult / ComplEx then do not read the candidate
     rows at all - their d_neg rows are coefficient x query.  `d_neg_rows` ([rows of neg.base, W] f32; the four
-    native scorers): the gradient of reference k is STORED at row neg.idx[k] of it (BESS_FLAG_DNEG_BY_ROW) - only for
+    native scorers and HAKE): the gradient of reference k is STORED at row neg.idx[k] of it (BESS_FLAG_DNEG_BY_ROW) - only for
     lists that name a row at most once; d_neg is not returned then."""
     nq = int(query.shape[0])
     dev = _neg_operands(d, query, neg, nq * n_neg)
@@ -1437,10 +1439,10 @@ def neg_score_pertriple_bwd(d: ModelDesc, query: torch.Tensor, neg: RowSource, n
     dq = torch.empty((nq, query_width(d)), dtype=torch.float32, device=dev) if want_d_query else None
     dn = torch.empty((nq * n_neg, d.width), dtype=torch.float32, device=dev) if want_d_neg else None
     if d_neg_rows is not None:
-        if (int(d.scorer) > COMPLEX or not want_d_neg or d_neg_rows.dtype != torch.float32 or not d_neg_rows.is_contiguous()
+        if (not (int(d.scorer) <= COMPLEX or int(d.scorer) == HAKE) or not want_d_neg or d_neg_rows.dtype != torch.float32 or not d_neg_rows.is_contiguous()
                 or tuple(d_neg_rows.shape) != (int(neg.base.shape[0]), int(d.width)) or d_neg_rows.device != dev):
             raise ValueError("neg_score_pertriple_bwd: `d_neg_rows` must be a contiguous f32 [rows of neg.base, W] "
-                             "tensor (native scorers)")
+                             "tensor (native scorers, HAKE)")
         d = copy_desc(d)
         d.reserved[0] |= FLAG_DNEG_BY_ROW
         dn = d_neg_rows

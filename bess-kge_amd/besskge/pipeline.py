@@ -31,7 +31,7 @@ def _counting_scorer(score_fn: BaseScoreFunction) -> bool:
     """Every scorer with a kernel descriptor: their all-entity kernels count ranks in their epilogues (TransE /
     RotatE / DistMult / ComplEx - ConvE rides DistMult's -, the affine family's tile kernel, BoxE's)."""
     try:
-        return nat.TRANSE <= int(score_fn.kernel_desc().scorer) <= nat.BOXE
+        return nat.TRANSE <= int(score_fn.kernel_desc().scorer) <= nat.HAKE
     except (AttributeError, NotImplementedError, ValueError):
         return False
 

@@ -36,6 +36,10 @@ rows with the query `[net(h, r) | 1]`, i.e. the DistMult kernels.
 BoxE (`scoring.py:1149-1415`): the relation-side preprocessing (width
 normalisation, box size, tanh of the box) and the positive score are torch ops
 over S rows; candidates are scored by the `csrc/boxe.hip` kernels.
+
+HAKE (Zhang et al. 2020; not in the reference): the modulus + phase distance.
+The query `[U | R | Q_p]` and the positive score are torch ops over S rows;
+candidates are scored by the `csrc/hake.hip` kernels.
 """
 
 import struct
@@ -1352,6 +1356,124 @@ class BoxE(_TorchQueryHooks, DistanceBasedScoreFunction):
                                     relation_id, None)
         else:
             q = self._query_torch(side, kept, self.relation_embedding, relation_id)
+        return ops.ReduceNegatives.apply(self.kernel_desc(), bool(self.negative_sample_sharing), q.contiguous(),
+                                         self._table_dtype(cand))
+
+    def score_heads(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_HEAD, tail_emb, relation_id, head_emb)
+
+    def score_tails(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._score_candidates(nat.CORRUPT_TAIL, head_emb, relation_id, tail_emb)
+
+
+def init_hake_modulus(embedding_table: torch.Tensor) -> torch.Tensor:
+    """Relation moduli of HAKE start at 1."""
+    return torch.nn.init.ones_(embedding_table)
+
+
+class HAKE(_TorchQueryHooks, DistanceBasedScoreFunction):
+    """HAKE (Zhang et al. 2020): entities are [phase | modulus], relations [phase | modulus | bias];
+
+        score = -( modulus_weight * || h_m * (|r_m| + b') - t_m * (1 - b') ||_2
+                   + phase_weight * || sin(phase_scale * (h_p - t_p) / 2 + r_p / 2) ||_1 ),   b' = max(min(b, 1), -|r_m|)
+
+    Candidates are scored by the kernels of csrc/hake.hip against the query matrix `[U | R | Q_p]`; the S-row work
+    (the query and the positive score) is torch ops.  Both weights are fixed hyperparameters (buffers), not learned;
+    `modulus_weight` >= 0 is folded into the query.  `fp32_math = True` scores shared candidates with the
+    row-streaming kernels (one hardware sine per element) instead of the LDS tile kernel."""
+
+    _scorer_id = nat.HAKE
+    supports_fused_segments = True  # csrc/hake.hip: k_hake_grad_segments
+
+    def __init__(
+        self,
+        negative_sample_sharing: bool,
+        sharding: Sharding,
+        n_relation_type: int,
+        embedding_size: int,
+        modulus_weight: float = 1.0,
+        phase_weight: float = 0.5,
+        phase_scale: float = 1.0,
+        entity_initializer: _Init = [init_uniform_rotation, init_KGE_uniform],
+        relation_initializer: _Init = [init_uniform_rotation, init_hake_modulus, torch.nn.init.zeros_],
+        inverse_relations: bool = False,
+        **placement: Any,
+    ) -> None:
+        super().__init__(negative_sample_sharing, 2)
+        if modulus_weight < 0:
+            raise ValueError(f"HAKE: modulus_weight must be >= 0 (it is folded into the query), got {modulus_weight!r}")
+        limit = 512 if embedding_size % 4 == 0 else (256 if embedding_size % 2 == 0 else 128)
+        if embedding_size > limit:
+            raise ValueError(f"HAKE: the row kernels take embedding_size <= 512 (<= 256 when not a multiple of 4, <= 128 "
+                             f"when odd), got {embedding_size}")
+        self.sharding = sharding
+        pl = _placement(placement)
+        # [phase | modulus]
+        self.entity_embedding = initialize_entity_embedding(sharding, entity_initializer, [embedding_size] * 2, **pl)
+        # [phase | modulus | bias]
+        self.relation_embedding = initialize_relation_embedding(
+            n_relation_type, inverse_relations, relation_initializer, [embedding_size] * 3,
+            device=pl["device"], dtype=pl["dtype"])
+        assert 3 * self.entity_embedding.shape[-1] == 2 * self.relation_embedding.shape[-1] == 6 * embedding_size, (
+            "HAKE requires `2*embedding_size` embedding parameters for each entity"
+            " and `3*embedding_size` embedding parameters for each relation")
+        self.embedding_size = embedding_size
+        for name, value in (("modulus_weight", modulus_weight), ("phase_weight", phase_weight), ("phase_scale", phase_scale)):
+            self.register_buffer(name, torch.tensor(float(value), dtype=torch.float32))
+
+    @property
+    def _weights(self) -> Tuple[float, float, float]:
+        """(modulus_weight, phase_weight, phase_scale) as Python floats, read from the buffers ONCE per version of
+        them (a loaded state dict changes them): `float(device tensor)` is a host sync on every step, and an error
+        inside a hipGraph capture."""
+        bufs = (self.modulus_weight, self.phase_weight, self.phase_scale)
+        key = tuple((b.data_ptr(), b._version, b.device) for b in bufs)
+        cached = self.__dict__.get("_weights_cache")
+        if cached is None or cached[0] != key:
+            cached = (key, tuple(float(b) for b in bufs))
+            self.__dict__["_weights_cache"] = cached
+        return cached[1]
+
+    def kernel_desc(self) -> nat.ModelDesc:
+        d = super().kernel_desc()
+        d.reserved[0] = nat.FLAG_FP32_MATH if self.fp32_math else 0
+        d.reserved[1] = struct.unpack("i", struct.pack("f", self._weights[1]))[0]
+        d.reserved[2] = struct.unpack("i", struct.pack("f", self._weights[2]))[0]
+        return d
+
+    def _relation_parts(self, rel: torch.Tensor, rel_idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(r_p, |r_m| + b', 1 - b') of the triples' relations [S, d]"""
+        r = BoxE._wide(torch.index_select(rel, 0, rel_idx.reshape(-1).long()))
+        r_p, r_m, b = torch.split(r, self.embedding_size, dim=-1)
+        r_m = r_m.abs()
+        b = torch.maximum(torch.clamp(b, max=1.0), -r_m)
+        return r_p, r_m + b, 1.0 - b
+
+    def _triple_torch(self, h: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+        lm, lp, ps = self._weights
+        r_p, scale_h, scale_t = self._relation_parts(rel, rel_idx)
+        h_p, h_m = torch.split(BoxE._wide(h), self.embedding_size, dim=-1)
+        t_p, t_m = torch.split(BoxE._wide(t), self.embedding_size, dim=-1)
+        modulus = torch.norm(h_m * scale_h - t_m * scale_t, p=2, dim=-1)
+        phase = torch.sin((ps * (h_p - t_p) + r_p) / 2).abs().sum(-1)
+        return -(lm * modulus + lp * phase)
+
+    def _query_torch(self, side: int, rows: torch.Tensor, rel: torch.Tensor, rel_idx: torch.Tensor) -> torch.Tensor:
+        lm, _, ps = self._weights
+        r_p, scale_h, scale_t = self._relation_parts(rel, rel_idx)
+        k_p, k_m = torch.split(BoxE._wide(rows), self.embedding_size, dim=-1)
+        if side == nat.CORRUPT_TAIL:  # modulus difference U * t_m + R, phase difference Q_p - phase_scale * t_p
+            return torch.cat([-lm * scale_t, lm * k_m * scale_h, ps * k_p + r_p], dim=-1)
+        # the norm and |sin| are even: the head's modulus difference is taken as U * h_m + R with R = -t_m (1 - b'),
+        # its phase difference as (phase_scale * t_p - r_p) - phase_scale * h_p
+        return torch.cat([lm * scale_h, -lm * k_m * scale_t, ps * k_p - r_p], dim=-1)
+
+    def score_triple(self, head_emb: torch.Tensor, relation_id: torch.Tensor, tail_emb: torch.Tensor) -> torch.Tensor:
+        return self._triple_torch(head_emb, self.relation_embedding, relation_id, tail_emb).float()
+
+    def _score_candidates(self, side: int, kept: torch.Tensor, relation_id: torch.Tensor,
+                          cand: torch.Tensor) -> torch.Tensor:
+        q = self._query_torch(side, kept, self.relation_embedding, relation_id).float()
         return ops.ReduceNegatives.apply(self.kernel_desc(), bool(self.negative_sample_sharing), q.contiguous(),
                                          self._table_dtype(cand))
 

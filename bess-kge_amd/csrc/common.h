@@ -28,7 +28,8 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // scorer properties
 inline bool is_complex_entity(int scorer) { return scorer == BESS_ROTATE || scorer == BESS_COMPLEX; }
 inline bool is_distance(int scorer) {
-    return scorer == BESS_TRANSE || scorer == BESS_ROTATE || scorer == BESS_AFFINE || scorer == BESS_BOXE;
+    return scorer == BESS_TRANSE || scorer == BESS_ROTATE || scorer == BESS_AFFINE || scorer == BESS_BOXE ||
+           scorer == BESS_HAKE;
 }
 int check_desc(const bess_model_desc* d);
 
@@ -144,6 +145,20 @@ int boxe_negatives(const bess_model_desc* d, bool fwd, bool shared, const float*
                    const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* out, const float* d_out,
                    int64_t ld, float* dq, float* dn, hipStream_t st, const float* thr = nullptr,
                    const CountArgs* count = nullptr);
+
+// HAKE (hake.hip): the row form for per-triple negatives and every backward, the tile form for the forward over shared
+// candidates (BESS_FLAG_FP32_MATH: the row form there too); hake_pairs: single (query, candidate) scores in the
+// arithmetic of the shared forward
+int hake_negatives(const bess_model_desc* d, bool fwd, bool shared, const float* query, int64_t n_query,
+                   const void* neg_base, const int32_t* neg_idx, int64_t n_neg, float* out, const float* d_out,
+                   int64_t ld, float* dq, float* dn, hipStream_t st, const float* thr = nullptr,
+                   const CountArgs* count = nullptr);
+int64_t hake_shared_bwd_workspace(const bess_model_desc* d, int64_t S, int64_t N);
+int hake_shared_bwd(const bess_model_desc* d, const float* query, int64_t S, const void* base, const int32_t* idx,
+                    int64_t N, const float* d_out, int64_t ld_dout, float* dq, float* dn, void* ws, int64_t ws_bytes,
+                    hipStream_t st);
+int hake_pairs(const bess_model_desc* d, const float* query, const void* neg_base, const int32_t* neg_idx, int64_t n_pair,
+               float* out, hipStream_t st);
 
 // ---- device side ------------------------------------------------------------
 typedef _Float16 half_t;
@@ -403,7 +418,7 @@ auto with_table_type(int dtype, F&& f) {
 }
 template <typename F>
 void dispatch_scorer_class(const bess_model_desc* d, F&& f) {
-    if (d->scorer > BESS_COMPLEX) return;  // (check_desc came first: 0 .. BESS_BOXE)
+    if (d->scorer > BESS_COMPLEX) return;  // (check_desc came first: 0 .. BESS_HAKE)
     with_table_type(d->dtype, [&](auto t) {
         with_constant<BESS_TRANSE, BESS_ROTATE, BESS_DISTMULT, BESS_COMPLEX>(d->scorer, [&](auto sc) { f(t, sc); });
     });

@@ -743,6 +743,9 @@ static int run(const bess_model_desc* d, bool fwd, const float* query, int64_t n
     if (d->scorer == BESS_BOXE)
         return boxe_negatives(d, fwd, false, query, n_query, neg_base, neg_idx, n_neg, out, d_out, ld, dq, dn,
                               as_stream(stream));
+    if (d->scorer == BESS_HAKE)
+        return hake_negatives(d, fwd, false, query, n_query, neg_base, neg_idx, n_neg, out, d_out, ld, dq, dn,
+                              as_stream(stream));
     if (d->scorer == BESS_AFFINE)
         return affine_pertriple(d, fwd, query, n_query, neg_base, neg_idx, n_neg, out, d_out, ld, dq, dn,
                                 as_stream(stream));

@@ -819,6 +819,7 @@ static bool use_l1_pk(const bess_model_desc* d, const void* query, const void* n
 static int64_t query_width(const bess_model_desc* d) {
     if (d->scorer == BESS_AFFINE) return static_cast<int64_t>(d->reserved[0] + 1) * (d->width / d->reserved[0]);
     if (d->scorer == BESS_BOXE) return 3ll * d->width;
+    if (d->scorer == BESS_HAKE) return 3ll * (d->width / 2);
     return d->width;
 }
 
@@ -958,6 +959,9 @@ extern "C" int bess_neg_score_shared_fwd_ws(const bess_model_desc* d, const floa
     if (d->scorer == BESS_BOXE)
         return boxe_negatives(d, true, true, query, n_query, neg_base, neg_idx, n_neg, out, nullptr, ld_out, nullptr,
                               nullptr, as_stream(stream));
+    if (d->scorer == BESS_HAKE)
+        return hake_negatives(d, true, true, query, n_query, neg_base, neg_idx, n_neg, out, nullptr, ld_out, nullptr,
+                              nullptr, as_stream(stream));
     if (d->scorer == BESS_AFFINE) {
         BESS_REQUIRE(!neg_idx, "neg_score_shared_fwd: affine scorers take dense f32 candidates (bess_normalize_rows)");
         return affine_shared_fwd(d, query, n_query, static_cast<const float*>(neg_base), n_neg, out, ld_out,
@@ -1072,7 +1076,7 @@ static bool counts_in_epilogue(const bess_model_desc* d, const float* query, con
 extern "C" int64_t bess_neg_score_shared_fwd_counts_workspace(const bess_model_desc* d, int64_t n_query,
                                                               int64_t n_neg) {
     if (!d || check_desc(d) || n_query <= 0 || n_neg <= 0) return 0;
-    if (d->scorer == BESS_BOXE) return 0;  // counts in its own kernel (k_box_fwd, COUNT)
+    if (d->scorer == BESS_BOXE || d->scorer == BESS_HAKE) return 0;  // count in their own kernels (COUNT variants)
     int64_t want = 0;
     if (counts_in_epilogue(d, nullptr, nullptr, n_query, n_neg, &want) && want > 0) return want;
     // (the packed L1 kernel needs none, but whether it applies depends on the pointers' alignment: the tile is
@@ -1095,6 +1099,13 @@ extern "C" int bess_neg_score_shared_fwd_counts(const bess_model_desc* d, const 
     if (d->scorer == BESS_BOXE)
         return boxe_negatives(d, true, true, query, n_query, neg_base, neg_idx, n_neg, nullptr, nullptr, 0, nullptr,
                               nullptr, st, thr, &cnt);
+    if (d->scorer == BESS_HAKE)  // one launch per chunk of rows that stays in the Infinity Cache, as the affine pass
+        return for_each_candidate_chunk(neg_base, neg_idx, n_neg, affine_chunk_rows(d), row_bytes_of(d),
+                                        [&](int64_t j0, int64_t nc, const void* base, const int32_t* idx) {
+            const CountArgs cj{excl, counts, j0, cnt.round16};
+            return hake_negatives(d, true, true, query, n_query, base, idx, nc, nullptr, nullptr, 0, nullptr, nullptr, st,
+                                  thr, &cj);
+        });
     int64_t want = 0;
     if (counts_in_epilogue(d, query, neg_base, n_query, n_neg, &want)) {
         if (product_route(d)) {  // (the distance route: a raised range flag poisons the counts as it does for a product)
@@ -1572,7 +1583,7 @@ __global__ void k_take_diagonal(const float* __restrict__ tile, int64_t ld, int6
 extern "C" int64_t bess_neg_score_shared_fwd_pairs_workspace(const bess_model_desc* d, int64_t like_n_query,
                                                              int64_t like_n_neg) {
     if (!d || check_desc(d) || like_n_query <= 0 || like_n_neg <= 0) return 0;
-    if (d->scorer == BESS_BOXE) return 0;
+    if (d->scorer == BESS_BOXE || d->scorer == BESS_HAKE) return 0;
     int64_t want = 0;
     if (counts_in_epilogue(d, nullptr, nullptr, like_n_query, like_n_neg, &want) && want > 0)
         return PAIR_DIAG_CHUNK * 128 * 4 + gemm_split_workspace_any(PAIR_DIAG_CHUNK, PAIR_DIAG_CHUNK, d->width) +
@@ -1596,6 +1607,7 @@ extern "C" int bess_neg_score_shared_fwd_pairs(const bess_model_desc* d, const f
     if (d->scorer == BESS_BOXE)
         return boxe_negatives(d, true, false, query, n_pair, neg_base, neg_idx, 1, out, nullptr, 1, nullptr, nullptr,
                               as_stream(stream));
+    if (d->scorer == BESS_HAKE) return hake_pairs(d, query, neg_base, neg_idx, n_pair, out, as_stream(stream));
     BESS_REQUIRE(workspace && workspace_bytes >= bess_neg_score_shared_fwd_pairs_workspace(d, like_n_query, like_n_neg) &&
                      reinterpret_cast<uintptr_t>(workspace) % 16 == 0,
                  "neg_score_shared_fwd_pairs: workspace too small (bess_neg_score_shared_fwd_pairs_workspace) or misaligned");
@@ -1716,6 +1728,7 @@ extern "C" int bess_neg_score_shared_fwd(const bess_model_desc* d, const float* 
 
 extern "C" int64_t bess_neg_score_shared_bwd_workspace(const bess_model_desc* d, int64_t n_query, int64_t n_neg) {
     if (!d || check_desc(d) || n_query <= 0 || n_neg <= 0) return 0;
+    if (d->scorer == BESS_HAKE) return hake_shared_bwd_workspace(d, n_query, n_neg);
     if (d->scorer == BESS_BOXE || d->scorer == BESS_AFFINE || !product_route(d)) return 0;
     if (d->reserved[0] & BESS_FLAG_FP32_MATH) return 0;
     return product_bwd_workspace(d, n_query, n_neg);
@@ -1775,6 +1788,9 @@ extern "C" int bess_neg_score_shared_bwd_ws(const bess_model_desc* d, const floa
     if (d->scorer == BESS_BOXE)
         return boxe_negatives(d, false, true, query, n_query, neg_base, neg_idx, n_neg, nullptr, d_out, ld_dout,
                               d_query, d_neg, st);
+    if (d->scorer == BESS_HAKE)
+        return hake_shared_bwd(d, query, n_query, neg_base, neg_idx, n_neg, d_out, ld_dout, d_query, d_neg, workspace,
+                               workspace_bytes, st);
     if (d->scorer == BESS_AFFINE) {
         BESS_REQUIRE(!neg_idx, "neg_score_shared_bwd: affine scorers take dense f32 candidates (bess_normalize_rows)");
         BESS_REQUIRE(d->norm_p == 1 || out, "neg_score_shared_bwd: p != 1 needs the forward scores");

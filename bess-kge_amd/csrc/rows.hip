@@ -34,13 +34,20 @@ int check_launch(const char* what) {
 
 int check_desc(const bess_model_desc* d) {
     if (!d) return fail(BESS_EINVAL, "model descriptor is NULL");
-    if (d->scorer < BESS_TRANSE || d->scorer > BESS_BOXE)
+    if (d->scorer < BESS_TRANSE || d->scorer > BESS_HAKE)
         return fail(BESS_EINVAL, "unknown scorer %d", d->scorer);
     if (d->dtype != BESS_F32 && d->dtype != BESS_F16)
         return fail(BESS_EINVAL, "unknown dtype %d", d->dtype);
     if (d->scorer == BESS_BOXE) {
         if (d->width <= 0 || d->width % 2) return fail(BESS_EINVAL, "BoxE: entity width %d is not 2 d", d->width);
         if (d->norm_p < 1) return fail(BESS_EINVAL, "scoring norm %d is not a p >= 1", d->norm_p);
+        return BESS_OK;
+    }
+    if (d->scorer == BESS_HAKE) {
+        if (d->width <= 0 || d->width % 2) return fail(BESS_EINVAL, "HAKE: entity width %d is not 2 d", d->width);
+        if (d->rel_width != d->width / 2 * 3)
+            return fail(BESS_EINVAL, "HAKE: rel_width %d is not 3 d (want %d)", d->rel_width, d->width / 2 * 3);
+        if (d->norm_p != 2) return fail(BESS_EINVAL, "HAKE: norm_p %d is not 2 (the modulus distance)", d->norm_p);
         return BESS_OK;
     }
     if (d->scorer == BESS_AFFINE) {

@@ -1,4 +1,4 @@
-// K9 of the per-triple negatives (segments.hip, affine.hip, boxe.hip): operands, launches, the long tier's tickets
+// K9 of the per-triple negatives (segments.hip, affine.hip, boxe.hip, hake.hip): operands, launches, the long tier's tickets
 #pragma once
 
 #include <algorithm>
@@ -32,6 +32,7 @@ struct SegPass {  // where the sums go, and the scratch of the long tier (zero o
 };
 int affine_grad_segments(const bess_model_desc* d, const SegRefs& refs, const SegPass& pass, hipStream_t st);
 int boxe_grad_segments(const bess_model_desc* d, const SegRefs& refs, const SegPass& pass, hipStream_t st);
+int hake_grad_segments(const bess_model_desc* d, const SegRefs& refs, const SegPass& pass, hipStream_t st);
 
 // launch(blocks, false): 16 segments per 256-thread workgroup, grid-stride over the (device-side) segment count, the
 // workgroups in sets of n_conc; then, with a list of long segments, launch(1024, true) for the rows left out (usually

@@ -1227,6 +1227,7 @@ static int grad_segments_impl(const bess_model_desc* d, const float* query, int6
     const SegPass pass{max_seg, grad_seg, fused_sgd_lr, long_cap, long_grad, long_count};
     if (d->scorer == BESS_AFFINE) return affine_grad_segments(d, refs, pass, st);
     if (d->scorer == BESS_BOXE) return boxe_grad_segments(d, refs, pass, st);
+    if (d->scorer == BESS_HAKE) return hake_grad_segments(d, refs, pass, st);
     BESS_REQUIRE(d->scorer <= BESS_COMPLEX, "grad_segments: scorer %d has no segmented form", d->scorer);
     const int W = d->width;
     const int vec = vec_of(d);

@@ -13,6 +13,7 @@ queries and report filtered-free MRR / hits@10.
                                              [--scorer RESCAL | QuatE | SimplE | CP]
                                              [--scorer ConvE [--conve-route fused]]
                                              [--scorer BoxE [--boxe-route native]]
+                                             [--scorer HAKE [--modulus-weight 1.0 --phase-weight 0.5]]
 
 The graph is synthetic but learnable: entities and relations get hidden TransE
 embeddings and the tail of (h, r) is the entity nearest to h + r, so a trained
@@ -76,7 +77,9 @@ def main(argv=None) -> dict:
     ap.add_argument("--n-shard", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--scorer", default="TransE", choices=["TransE", "RotatE", "DistMult", "ComplEx", "PairRE", "TranS", "TuckER",
-                                                                "RESCAL", "ConvE", "QuatE", "SimplE", "CP", "BoxE"])
+                                                                "RESCAL", "ConvE", "QuatE", "SimplE", "CP", "BoxE", "HAKE"])
+    ap.add_argument("--modulus-weight", type=float, default=1.0, help="weight of the modulus distance of --scorer HAKE")
+    ap.add_argument("--phase-weight", type=float, default=0.5, help="weight of the phase distance of --scorer HAKE")
     ap.add_argument("--relation-size", type=int, default=16, help="width of the relation rows of --scorer TuckER")
     ap.add_argument("--tucker-route", default="outer", choices=["outer", "relation"],
                     help="TuckER's query_route: per-triple outer product, or one mixed matrix per relation")
@@ -141,6 +144,9 @@ def main(argv=None) -> dict:
         fn = getattr(scoring, args.scorer)(True, 1, sharding, args.n_relation, d)
     elif args.scorer == "BoxE":
         fn = scoring.BoxE(True, 2, sharding, args.n_relation, d, query_route=args.boxe_route)
+    elif args.scorer == "HAKE":
+        fn = scoring.HAKE(True, sharding, args.n_relation, d, modulus_weight=args.modulus_weight,
+                          phase_weight=args.phase_weight)
     elif args.scorer == "TuckER":  # (the paper's recipe: --training kvsall --label-smoothing 0.1)
         fn = scoring.TuckER(True, sharding, args.n_relation, d, args.relation_size, batch_normalization=True,
                             input_dropout=0.2, hidden_dropout=0.2, query_route=args.tucker_route)

@@ -70,6 +70,19 @@ extern "C" {
  * [S_0 | C_0 | H_0 | S_1 | C_1 | H_1] (shift, box centre, half width met by candidate part
  * 0 / 1); desc.reserved[0] bit 0 = apply_tanh, bit 1 = dist_func_per_dim.  See csrc/boxe.hip. */
 #define BESS_BOXE 5
+/* HAKE (Zhang et al. 2020) as seen by the negative-scoring kernels: entity rows [phase | modulus]
+ * (desc.width = 2 d), relation rows [phase | modulus | bias] (desc.rel_width = 3 d, checked; the kernels never
+ * read them), desc.norm_p = 2, query matrix [n_query, 3 d] = [U | R | Q_p]:
+ *     score = -( || U * c_m + R ||_2 + phase_weight * || sin((Q_p - phase_scale * c_p) / 2) ||_1 )
+ * desc.reserved[1] / [2] hold the bits of the floats phase_weight and phase_scale; the modulus weight (>= 0) is
+ * folded into U and R by whoever builds the query.  desc.reserved[0]: flag bits - BESS_FLAG_DNEG_BY_ROW as for the
+ * native scorers; BESS_FLAG_FP32_MATH: the shared-candidate forward calls (scores, counts, pairs) run the
+ * row-streaming kernels (one hardware sine per element) instead of the LDS tile kernel, whose inner loop works on
+ * sin / cos images of the half phases.  Served by the bess_neg_score_* entry points the affine family and BoxE are
+ * served by (not the 1vsAll / KvsAll ones).  Workspaces 0, but bess_neg_score_shared_bwd_workspace: n_query * n_neg
+ * floats for the tile kernels of the backward (the recomputed modulus norms); without them the row kernels run.  Phase differences beyond 512 pi are outside the
+ * hardware sine's domain.  See csrc/hake.hip. */
+#define BESS_HAKE 6
 
 /* table element types */
 #define BESS_F32 0
